@@ -20,6 +20,13 @@ committed in profiles/pmc_<config>.json (traffic_source names the file and the F
 calibrated by tools/fetch_calib.hip).  cpu_baseline = the oracle (oracle/cpu_ref.c, a C port of
 the reference's CPU TileRenderer) built -O3 -march=native on this host and timed on a bounded
 sample with the host's CPU share of threads (model, nproc and flags recorded).
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line.
+The legs that take runs of their own -- the CPU baseline, the issued-bytes probe (one render through the
+diagnostic library) and, at N > 1, rank 0's frame through one multi-device context -- run only with
+`--full` (where `--no-cpu-baseline`, `--no-issued` and `--no-capi-multi` still drop one each).
+`--dump-outputs DIR` writes what the last timed step left in the caller's buffer: DIR/frame.npy, the
+accumulated RGBA frame in image order (float32; frames over 64 MB as a fixed seeded sample of pixels).
 """
 from __future__ import annotations
 
@@ -332,6 +339,21 @@ def stdout_to_stderr():
         os.close(saved)
 
 
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, frame: np.ndarray) -> None:
+    """--dump-outputs: DIR/frame.npy, the (H*W, 4) float32 frame in image order; a frame over DUMP_MAX_BYTES
+    as the rows of a fixed sample of pixels (default_rng(0), in ascending pixel order), the same in every run."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    keep = DUMP_MAX_BYTES // (frame.shape[1] * frame.itemsize)
+    if frame.shape[0] > keep:
+        frame = frame[np.sort(np.random.default_rng(0).choice(frame.shape[0], keep, replace=False))]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "frame.npy", frame)
+
+
 def scene_contents(sc) -> str:
     if sc.blocks is not None:  # block-value leaves (DESIGN.md C23)
         return f"{len(sc.cells)} voxel cells as block-value leaves ({len(sc.blocks)} block kinds)"
@@ -349,11 +371,18 @@ def main():
                     help="build the octree with OCTPT_BUILD_COMPACT (is_compactable merge, DESIGN.md C22)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=None, help="default: the host's CPU share (host_cpu)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-issued", action="store_true", help="skip the issued-bytes probe (diagnostic library)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the CPU baseline, the "
+                         "issued-bytes probe and, with N > 1 ranks, the multi-device-context frame")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full, skip the CPU baseline")
+    ap.add_argument("--no-issued", action="store_true",
+                    help="with --full, skip the issued-bytes probe (diagnostic library)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: host-staged gather (rehearses N ranks on fewer GPUs); nccl = RCCL over xGMI")
     ap.add_argument("--dump-frame", default=None, help="rank 0 saves the gathered frame (.npy) after the last step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's output to DIR/frame.npy (the frame in image order, "
+                         "float32; at most 64 MB: a larger frame as a fixed seeded sample of pixels)")
     ap.add_argument("--capi-devices", default=None,
                     help="one process, one multi-device context (octpt_create_multi) over N devices or a list of "
                          "HIP ids: the C-ABI path a Rust host calls (DESIGN.md §9); ids repeat on a one-GPU box")
@@ -362,10 +391,12 @@ def main():
                          "warmup step's per-tile segment counts instead of the round-robin deal (DESIGN.md §9: "
                          "measured equal on C3 / C5b, so round robin stays the default)")
     ap.add_argument("--no-capi-multi", action="store_true",
-                    help="with N > 1 ranks, skip rank 0's extra measurement of the same frame through one "
+                    help="with --full and N > 1 ranks, skip rank 0's extra measurement of the same frame through one "
                          "multi-device context over the N devices (after the timed steps; the other ranks wait on a "
                          "gloo group, so no RCCL kernel sits on the GPUs it renders on)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU without torchrun: spawn the ranks before anything touches the GPU
@@ -557,7 +588,7 @@ def main():
     # After the timed steps and the gather, rank 0 alone runs the extra legs (the C-ABI multi-device frame, the
     # CPU baseline) while the other ranks wait on a gloo group: a wait on the RCCL group would leave an RCCL kernel
     # resident on the GPUs the multi-device leg renders on.
-    if world > 1 and not args.no_capi_multi:
+    if world > 1 and args.full and not args.no_capi_multi:
         # the same frame through the C-ABI path a Rust host calls: one process (rank 0), one multi-device
         # context over the N devices, tiles gathered inside liboctpt.  (gloo rehearsals of N ranks
         # on fewer GPUs repeat device ids, as the ranks do)
@@ -569,10 +600,10 @@ def main():
             except Exception as e:  # reported, never fatal to the bench line
                 out["capi_multi"] = {"error": f"{type(e).__name__}: {e}"}
         dist.barrier(group=host_group)
-    if rank == 0 and world == 1 and not args.no_issued and not multi:
+    if rank == 0 and world == 1 and args.full and not args.no_issued and not multi:
         out["roofline"]["issued"] = issued_probe(sc, cam, rs, dev_idx, ext_s)
     # the reference's CPU path timed in the same run next to the N-GPU figure (north_star), on rank 0 only
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(sc, cam, rs, args.cpu_seconds, args.cpu_threads)
         out["cpu_baseline"]["gpu_over_cpu"] = round(out["value"] / max(out["cpu_baseline"]["value"], 1e-9), 1)
     else:
@@ -580,8 +611,7 @@ def main():
     if world > 1:
         dist.barrier(group=host_group)
     if rank == 0:
-        print(json.dumps(out), flush=True)
-        if args.dump_frame:  # the frame in image order (a single rank's buffer is tile-major too)
+        if args.dump_frame or args.dump_outputs:  # the frame in image order (a single rank's buffer is tile-major too)
             if multi:
                 frame = accum
             elif world == 1:
@@ -589,7 +619,12 @@ def main():
                 r.unshard_device(W, H, 1, accum.data_ptr(), stride, frame.data_ptr(),
                                  torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
-            np.save(args.dump_frame, frame.cpu().numpy())
+            image = frame.cpu().numpy()
+            if args.dump_frame:
+                np.save(args.dump_frame, image)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, image)
+        print(json.dumps(out), flush=True)
     r.close()
     if world > 1:
         dist.destroy_process_group()

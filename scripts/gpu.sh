@@ -39,7 +39,7 @@ for task in "$@"; do
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail "$task" $O/smoke.log
            cat $O/smoke.log ;;
     bench|fast)
-      X=""; [ $kind = fast ] && X="--no-cpu-baseline"
+      X="--full"; [ $kind = fast ] && X="--full --no-cpu-baseline"
       timeout -k 10 600 python3 bench.py --config ${a:-C3} --steps ${b:-5} --warmup 1 $X > $O/bench_${a:-C3}.json \
           2> $O/bench_${a:-C3}.err || fail "$task" $O/bench_${a:-C3}.err
       cat $O/bench_${a:-C3}.json ;;
@@ -47,7 +47,7 @@ for task in "$@"; do
       V=$a; if [ -n "$c" ]; then V=${a}_$(basename $(dirname $c)); fi
       (cd /tmp && export TMPDIR=/tmp && if [ -n "$c" ]; then export OCTPT_LIB=$R/$c; fi \
           && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/stats_$V -o run \
-          --output-format csv -- python3 $R/bench.py --config $a --steps ${b:-5} --warmup 1 --no-cpu-baseline \
+          --output-format csv -- python3 $R/bench.py --config $a --steps ${b:-5} --warmup 1 --full --no-cpu-baseline \
           > $O/stats_$V.json 2> $O/stats_$V.err) || fail "$task" $O/stats_$V.err
       cat $O/stats_$V.json ;;
     pmc)
@@ -76,15 +76,15 @@ for task in "$@"; do
           2> $O/shard_$a.err || fail "$task" $O/shard_$a.err
       tail -1 $O/shard_$a.json ;;
     n8)
-      timeout -k 10 600 python3 bench.py --gpus 8 --dist-backend gloo --steps 2 --warmup 1 --no-cpu-baseline \
+      timeout -k 10 600 python3 bench.py --gpus 8 --dist-backend gloo --steps 2 --warmup 1 --full --no-cpu-baseline \
           > $O/bench_n8_gloo.json 2> $O/bench_n8_gloo.err || fail "$task" $O/bench_n8_gloo.err
       cat $O/bench_n8_gloo.json ;;
     nrank)  # nrank:N[:CFG[:STEPS]]: the driver's N-rank command as gloo ranks time-sharing this GPU, CPU baseline
             # included; the command's wall time goes to nrank_N_CFG.time
       t0=$(date +%s.%N)
-      timeout -k 10 900 python3 bench.py --gpus $a --config ${b:-C3} --dist-backend gloo --steps ${c:-2} --warmup 1 \
+      timeout -k 10 900 python3 bench.py --gpus $a --config ${b:-C3} --dist-backend gloo --steps ${c:-2} --warmup 1 --full \
           > $O/nrank_${a}_${b:-C3}.json 2> $O/nrank_${a}_${b:-C3}.err || fail "$task" $O/nrank_${a}_${b:-C3}.err
-      echo "{\"command\": \"python3 bench.py --gpus $a --config ${b:-C3} --dist-backend gloo --steps ${c:-2} --warmup 1\", \"wall_s\": $(python3 -c "print(round($(date +%s.%N) - $t0, 1))")}" > $O/nrank_${a}_${b:-C3}.time
+      echo "{\"command\": \"python3 bench.py --gpus $a --config ${b:-C3} --dist-backend gloo --steps ${c:-2} --warmup 1 --full\", \"wall_s\": $(python3 -c "print(round($(date +%s.%N) - $t0, 1))")}" > $O/nrank_${a}_${b:-C3}.time
       cat $O/nrank_${a}_${b:-C3}.time; tail -c 600 $O/nrank_${a}_${b:-C3}.json ;;
     ab)
       timeout -k 10 1000 bash scripts/ab.sh "$(echo ${a//,/ } | tr / :)" ${b//,/ } > $O/ab_$n.txt 2>&1 || fail "$task" $O/ab_$n.txt

@@ -2,7 +2,7 @@
 # Usage: scripts/gpu_profile.sh TAG  -- run on the GPU box (via gpurun) from the repo root.
 # 1) (CALIB=1) FETCH_SIZE calibration (tools/fetch_calib) under rocprofv3;
 # 2) PMC passes (FETCH_SIZE, WRITE_SIZE, SQ, TCC) of a 1-step bench;
-# 3) the bench (default args, with CPU baseline) and kernel-trace/stats of the same bench command.
+# 3) the bench (--full: with CPU baseline) and kernel-trace/stats of the same bench command.
 # The traffic JSON (profiles/pmc_C3.json) is computed afterwards from the returned CSVs.
 set -o pipefail
 TAG=${1:-r02}
@@ -24,11 +24,11 @@ timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $OUT/pmc_tcc -o ru
 [ -n "$CALIB" ] && { python3 $R/scripts/fetch_calib.py $OUT/calib.out $OUT/calib $OUT/fetch_calib.json > /dev/null || echo "fetch calibration summary failed" >&2; }
 python3 $R/scripts/pmc_traffic.py $OUT/pmc_fetch $OUT/pmc_write C3 $OUT/pmc_C3.json 1.0 "calibrated by tools/fetch_calib.hip (profiles/fetch_calib.json): scattered 8-B and 16-B reads are counted at 64 B per request, factor 1; 16-B coalesced streams at half, factor 2" $OUT/pmc_tcc > /dev/null || exit $?
 cp $OUT/pmc_C3.json $R/profiles/pmc_C3.json
-timeout -k 10 400 python3 $R/bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $R/bench.py --steps 10 --warmup 2 > $OUT/trace_bench.json 2> $OUT/trace.err || exit $?
+timeout -k 10 400 python3 $R/bench.py --steps 10 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $R/bench.py --steps 10 --warmup 2 --full > $OUT/trace_bench.json 2> $OUT/trace.err || exit $?
 # the two 4K configs at full size on this one GPU (the 8-GPU cases of BASELINE.json)
 if [ -n "$FULL" ]; then
-  timeout -k 10 400 python3 $R/bench.py --config C4 --steps 2 --warmup 1 > $OUT/bench_full_C4.json 2> $OUT/bench_full_C4.err || exit $?
-  timeout -k 10 400 python3 $R/bench.py --config C5 --steps 2 --warmup 1 > $OUT/bench_full_C5.json 2> $OUT/bench_full_C5.err || exit $?
+  timeout -k 10 400 python3 $R/bench.py --config C4 --steps 2 --warmup 1 --full > $OUT/bench_full_C4.json 2> $OUT/bench_full_C4.err || exit $?
+  timeout -k 10 400 python3 $R/bench.py --config C5 --steps 2 --warmup 1 --full > $OUT/bench_full_C5.json 2> $OUT/bench_full_C5.err || exit $?
 fi
 echo done

@@ -27,7 +27,8 @@ def _bench(tmp_path, n, extra=(), spp=("--spp", "2"), cpu=("--no-cpu-baseline",)
 def test_two_ranks_gather_equals_one(tmp_path):
     one, f1 = _bench(tmp_path, 1)
     # one warmup step: its per-tile segment counts give the balanced tile deal of the timed step
-    two, f2 = _bench(tmp_path, 2, ("--dist-backend", "gloo", "--warmup", "1", "--balance"))
+    # (--full: the capi_multi leg below runs after the timed steps)
+    two, f2 = _bench(tmp_path, 2, ("--dist-backend", "gloo", "--warmup", "1", "--balance", "--full"))
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["config"]["parallelism"] == "tiles2-gloo" and two["config"]["tile_deal"].startswith("balanced")
     assert f1.shape == f2.shape == (1280 * 720, 4)
@@ -62,12 +63,26 @@ def test_capi_devices_bench(tmp_path):
     assert one["config"]["segments_per_step"] == two["config"]["segments_per_step"]
 
 
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A run without --full times its steps only (no CPU baseline, no issued-bytes probe), --steps sets the
+    number of timed steps, and --dump-outputs writes the last step's frame: what --dump-frame saves."""
+    d = tmp_path / "outputs"
+    line, frame = _bench(tmp_path, 1, ("--steps", "2", "--dump-outputs", str(d)), cpu=())
+    assert line["cpu_baseline"] is None and "issued" not in line["roofline"]
+    assert line["steps"] == 2 and line["stats_rank0"]["paths"] == 2 * line["config"]["paths_per_step"]
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Mrays/s" and line["dtype"] == "f32"
+    assert [p.name for p in d.iterdir()] == ["frame.npy"]
+    out = np.load(d / "frame.npy")
+    assert out.dtype == np.float32 and np.array_equal(out, frame)
+
+
 def test_two_rank_line_complete(tmp_path):
     """The N-rank line carries everything the one-GPU line does: traffic and the measured
     read / write GB/s from a profile of the same rank count (profiles/pmc_C2_n2.json, rank 0's shard), and the
     CPU baseline timed on rank 0 in the same run, after the timed steps."""
-    one, f1 = _bench(tmp_path, 1, spp=(), cpu=("--cpu-seconds", "1"))
-    two, f2 = _bench(tmp_path, 2, ("--dist-backend", "gloo", "--no-capi-multi"), spp=(), cpu=("--cpu-seconds", "1"))
+    one, f1 = _bench(tmp_path, 1, spp=(), cpu=("--full", "--cpu-seconds", "1"))
+    two, f2 = _bench(tmp_path, 2, ("--dist-backend", "gloo", "--no-capi-multi"), spp=(),
+                     cpu=("--full", "--cpu-seconds", "1"))
     assert np.array_equal(f1, f2)
     for line, n in ((one, 1), (two, 2)):
         rf = line["roofline"]

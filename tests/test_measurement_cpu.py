@@ -156,6 +156,26 @@ def test_measured_rates_from_same_n_profiles():
     assert bench.measured_rates("C3", 1, 0.0) is None
 
 
+def test_dump_outputs_whole_or_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: a frame within the size limit is written whole as float32; a larger one as the same
+    seeded sample of pixels in every run, in ascending pixel order, within the limit."""
+    import numpy as np
+
+    import bench
+
+    frame = np.arange(1000 * 4, dtype=np.float64).reshape(1000, 4)
+    bench.dump_outputs(tmp_path / "a", frame)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * 16 + 7)
+    bench.dump_outputs(tmp_path / "b", frame)
+    bench.dump_outputs(tmp_path / "c", frame)
+    b, c = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "c" / "frame.npy")
+    assert b.shape == (100, 4) and b.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(b, c)
+    pix = b[:, 0] / 4  # row i of `frame` starts with 4 i
+    assert np.all(np.diff(pix) > 0) and np.array_equal(b, frame[pix.astype(np.int64)].astype(np.float32))
+
+
 def test_stdout_to_stderr_catches_native_writes():
     """bench.stdout_to_stderr: output written to fd 1 by native code (gloo's connect messages) goes to stderr, so the
     bench's stdout carries its one JSON line alone."""
