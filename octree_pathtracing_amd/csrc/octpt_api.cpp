@@ -1045,12 +1045,12 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         const uint32_t n_seed = (uint32_t)std::min<uint64_t>(pool, chunk_items);
         const bool regen = n_seed < chunk_items;  // else the seed claimed every item of the chunk
         // the lean 24-B path state: L stays 0 until the path ends, item = slot
-        // (and, OCTPT_LEAN_STRICT, no branch schedule: the lean shade instances carry no first-reflection split)
-        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !(OCTPT_LEAN_STRICT && R.subs)) ? 1u : 0u;
+        // (and no branch schedule: the lean shade instances carry no first-reflection split)
+        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs) ? 1u : 0u;
         const int grid_shade = grid_shade_of(shade_mode(regen, ctx->wb.lean != 0u));
         // the seed writes its camera rays as 16-B records (store_cam_ray) when every item has its pixel: the first
         // extend (cam) and shade (first = 2) decode them
-        const bool cam_rec = OCTPT_CAM_RECORDS && !regen && ((Rc.W | Rc.H) & (kTile - 1u)) == 0u;
+        const bool cam_rec = !regen &&((Rc.W | Rc.H) & (kTile - 1u)) == 0u;
         HIP_TRY(ctx, launch_wf_seed(ctx->C, Rc, B, n_seed, chunk_items, ctx->d_stats, s));
         for (uint32_t it = 0;; ++it) {
             if (cancel && cancel->load()) return fail(ctx, OCTPT_CANCELLED, "render cancelled");
@@ -1069,15 +1069,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             // iteration over an empty queue exits at once).  The queue only empties once every
             // chunk item is claimed: finished paths regenerate in the same shade pass.
             const uint32_t slot = it % (kLookahead + 1);
-#ifdef OCTPT_SNAPSHOT_MEMCPY  // (A/B build: the two strided copies the snapshot kernel replaced)
-            uint32_t *hs = ctx->h_count + slot * kCountSpan;
-            HIP_TRY(ctx, hipMemcpy2DAsync(hs, sizeof(uint32_t), B.ctrl + ctr_count(q ^ 1u, 0), kCtrStride * sizeof(uint32_t),
-                                          sizeof(uint32_t), kSegs, hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipMemcpy2DAsync(hs + kSegs, sizeof(uint32_t), B.ctrl + ctr_item(0), kCtrStride * sizeof(uint32_t),
-                                          sizeof(uint32_t), kSegs, hipMemcpyDeviceToHost, s));
-#else
             HIP_TRY(ctx, launch_wf_snapshot(B, q ^ 1u, ctx->d_count + slot * kCountSpan, s));
-#endif
             HIP_TRY(ctx, hipEventRecord(ctx->count_ev[slot], s));
             if (it >= kLookahead) {
                 const uint32_t old = (it - kLookahead) % (kLookahead + 1);

@@ -21,15 +21,6 @@ constexpr uint32_t kPrimIndexMask = 0x07FFFFFFu;  // primitive indices < 2^27 (h
 #define OCTPT_BEAM_TILE 2
 #endif
 constexpr uint32_t kBeamTile = OCTPT_BEAM_TILE;
-// the seed's camera rays as 16-B records when every chunk item has its pixel (store_cam_ray; A/B knob; the
-// seed-ticket A/B build writes store_ray's records)
-#ifndef OCTPT_CAM_RECORDS
-#ifdef OCTPT_SEED_TICKET
-#define OCTPT_CAM_RECORDS 0
-#else
-#define OCTPT_CAM_RECORDS 1
-#endif
-#endif
 constexpr uint32_t kTile = 8;          // 8x8 pixel tiles = one wave64 of primary rays
 constexpr uint32_t kBlock = 256;       // threads per block (4 waves)
 constexpr uint32_t kMaxDepth = 21;     // new_octree.rs:14
@@ -228,10 +219,6 @@ struct WaveBuffers {
     // pool holding the chunk (item = slot), set per chunk by the host
     uint32_t lean;
 };
-// the lean path state's chunks exclude branch schedules (C20) as well as emission and sun sampling (A/B knob)
-#ifndef OCTPT_LEAN_STRICT
-#define OCTPT_LEAN_STRICT 1
-#endif
 // shade instance: 0 = 40-B path state, 1 = with regeneration (pool smaller than the chunk), 2 = lean
 inline int shade_mode(bool regen, bool lean) { return regen ? 1 : (lean ? 2 : 0); }
 

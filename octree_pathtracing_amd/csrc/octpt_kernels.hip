@@ -934,31 +934,8 @@ __device__ __forceinline__ void esvo_descend(Esvo &E, const StackT<kS> &stk, uin
     E.idx = (dx ? 1u : 0u) | (dy ? 2u : 0u) | (dz ? 4u : 0u);
 }
 
-
-#ifndef OCTPT_LEAD_LOOP
-#define OCTPT_LEAD_LOOP 0
-#endif
-// The descends a ray's ESVO takes before its first other iteration, as a loop of exact descend replicas
-// (esvo_descend: the same stop tests, t-values, push and child choice as esvo_step's descend), each one
-// dependent node-slot load.  A lane leaves the loop at the first iteration that would not descend.
-template <class Stk>
-__device__ __forceinline__ void lead_descends(const DevScene &S, Esvo &E, const Stk &stk) {
-    const float max_dst = MAX_DST_WORLD * S.octree_scale;
-    for (;;) {
-        const uint32_t cidx = E.idx ^ E.mirror;
-        const v3 tc = vsub(vmul(E.pos, E.t_coef), E.t_bias);
-        const float tc_max = tmin3(tc);
-        const float tv_max = tmn_nc(E.t_max, tc_max);
-        const bool d = (((E.pmask >> cidx) & 0x101u) == 0x001u) & !esvo_capped(E.iter) & !(E.t_min > max_dst) &
-                       (E.t_min <= tv_max);
-        if (!d) break;
-        const uint2 slot = S.node_child[E.parent + __popc(E.pmask & ((1u << cidx) - 1u))];
-        esvo_descend(E, stk, S.depth, tc, tc_max, tv_max, slot);
-    }
-}
-
 #ifndef OCTPT_FOLD
-#define OCTPT_FOLD 1  // absent-sibling folds per step (A/B: -DOCTPT_FOLD=0)
+#define OCTPT_FOLD 1  // absent-sibling folds per step of the box instance (the others: their own knobs below)
 #endif
 #ifndef OCTPT_FOLD_SPHERES
 // the sphere instance folds up to 2 (round 5: C3 +0.4 %; the box instance stays at 1: 2 folds there C4 -2.2 %)
@@ -969,20 +946,13 @@ __device__ __forceinline__ void lead_descends(const DevScene &S, Esvo &E, const 
 // C3 -2.4 %, C4 -2.9 %, C2 +-0)
 #define OCTPT_FOLD_MODELS 2
 #endif
-#ifndef OCTPT_DFOLD
 // descend fold in esvo_step, per instance: measured +4 % extend on C5 (block models, depth 11),
-// +-1 % on C3 / C2 / C4 in round 2, so 3 = the block-model instance, plus the block-value and sphere
-// instances by their own knobs below (A/B: -DOCTPT_DFOLD=0 / 1 = all)
-#define OCTPT_DFOLD 3
-#endif
+// +-1 % on C3 / C2 / C4 in round 2, so the block-model instance always has it, the block-value and sphere
+// instances by their own knobs below, and the box instance never
 // the sphere instance's descend fold (round 3, after the lane-mask and spill work: C3 extend -1.4..-2.1 %,
 // C2 -1 %; the box instance stays without it, C4 +0.4..+0.8 %)
 #ifndef OCTPT_DFOLD_SPHERES
 #define OCTPT_DFOLD_SPHERES 1
-#endif
-// descend folds per step where the descend fold is on (A/B knob)
-#ifndef OCTPT_DFOLD_N
-#define OCTPT_DFOLD_N 1
 #endif
 // the block-value instance (C23): absent-sibling folds per step and the descend fold (A/B knobs)
 #ifndef OCTPT_FOLD_BLOCKS
@@ -1186,17 +1156,16 @@ __device__ inline int esvo_step(const DevScene &S, const TraceRay &ray, Esvo &E,
     E.t_min = descend ? E.t_min : tc_max;
     E.idx = descend ? step_mask : (E.idx ^ step_mask);
     bool pop = !descend & ((E.idx & step_mask) != 0u);
-#if OCTPT_DFOLD
     // Descend fold: a descend whose chosen child is again an octant the ray enters is followed, in
     // the reference, by an iteration that only descends (:216-244); 26 % of C3's iterations are such
     // descend-after-descend pairs (tools/esvo_trace.py).  That iteration is run here as an exact
     // replica (its own stop tests, t_corner, push and child choice, counted in E.iter); its slot
     // load depends on this step's, which the other waves of the SIMD hide.
-    constexpr int kDFolds = (OCTPT_DFOLD != 3 || kPrims == kPrimsModels || (kPrims == kPrimsBlocks && OCTPT_DFOLD_BLOCKS) ||
-                             (kPrims == kPrimsSpheres && OCTPT_DFOLD_SPHERES)) ? OCTPT_DFOLD_N : 0;
+    constexpr int kDFolds = (kPrims == kPrimsModels || (kPrims == kPrimsBlocks && OCTPT_DFOLD_BLOCKS) ||
+                             (kPrims == kPrimsSpheres && OCTPT_DFOLD_SPHERES)) ? 1 : 0;
     bool dmore = descend;
 #pragma unroll
-    for (int k = 0; k < kDFolds; ++k) {  // up to kDFolds descend-only iterations after a descend (A/B: OCTPT_DFOLD_N)
+    for (int k = 0; k < kDFolds; ++k) {  // one descend-only iteration after a descend, where the instance folds
     if (dmore) {
         const uint32_t cidx2 = E.idx ^ E.mirror;
         const v3 tc2 = vsub(vmul(E.pos, E.t_coef), E.t_bias);
@@ -1215,8 +1184,6 @@ __device__ inline int esvo_step(const DevScene &S, const TraceRay &ray, Esvo &E,
         dmore = d2;
     }
     }
-#endif
-#if OCTPT_FOLD
     // Absent-sibling fold: when the child this step moved to is absent, the reference's next
     // iteration (:127-141, then :249-299) only advances past it.  That iteration is run here, as an
     // exact replica (same t_corner / tc_max / step_mask operations, counted in E.iter, same stop
@@ -1247,7 +1214,6 @@ __device__ inline int esvo_step(const DevScene &S, const TraceRay &ray, Esvo &E,
         pop = (E.idx & step_mask) != 0u;
     }
     }
-#endif
     bool escaped = false;
 #ifdef OCTPT_PROFILE_LANES
     prof_wave(cnt.p_pop_it, cnt.p_pop_ln, pop);
@@ -1551,7 +1517,7 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
     }
     if (ray.depth + 1u >= R.max_depth) return false;
     ray.depth += 1u;
-    if (!(OCTPT_LEAN_STRICT && kLean) && ray.depth == 1u && ray.branch != 0u) {  // the first reflection splits [C20]
+    if (!kLean && ray.depth == 1u && ray.branch != 0u) {  // the first reflection splits [C20]
         ray.rng = branch_state(ray.rng, ray.branch);
         ray.seg_base = ray.path_segs;
     }
@@ -1563,7 +1529,7 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
         if (do_metal) T = V(T.x * ray.col[0], T.y * ray.col[1], T.z * ray.col[2]);
         specular_reflection(ray, m.roughness);
     } else if (rng_next(ray.rng) < diffuse) {
-        if (!(OCTPT_LEAN_STRICT && kLean) && S.emitters && m.emittance > RAY_EPSILON) {
+        if (!kLean && S.emitters && m.emittance > RAY_EPSILON) {
             const v3 e = V(ray.col[0] * ray.col[0] * m.emittance, ray.col[1] * ray.col[1] * m.emittance,
                            ray.col[2] * ray.col[2] * m.emittance);
             ray.L = V(ray.L.x + T.x * e.x, ray.L.y + T.y * e.y, ray.L.z + T.z * e.z);
@@ -1918,7 +1884,7 @@ __device__ __forceinline__ void store_ray(const WaveBuffers &B, uint32_t q, uint
                                  __uint_as_float(slot | (vdot(ps.d, ps.n) < 0.0f ? 0x80000000u : 0u) |
                                                  (beam ? kRayBeamBit : 0u)));
 }
-// The seed's camera rays when every chunk item has its pixel (direct seeding, OCTPT_CAM_RECORDS): 16 B, ray1
+// The seed's camera rays when every chunk item has its pixel (direct seeding): 16 B, ray1
 // alone as (d, the beam start or 0); the origin is the eye, the last primitive none, and the slot the item, which
 // the position gives (shard_lo(segment) + index in it).  8.5 GB less written by the seed and read by the first
 // extend per C3 frame.  cam_ray turns one into store_ray's two records in registers.
@@ -1944,32 +1910,23 @@ __device__ __forceinline__ void pack_path(const PathState &ps, uint32_t item, fl
     c = make_uint2(ps.cur, ps.depth | (ps.specular ? 1u << 8 : 0u) | (ps.shadow ? 1u << 9 : 0u) | (ps.branch << 10) |
                                (ps.path_segs << 16) | (ps.seg_base << 23));
 }
-// kLean (WaveBuffers::lean): the 24-B path state (T, rng) + (cur, bits).  The radiance L of a
-// path that continues is exactly 0 when the scene has no emitters and no sun sampling (it is added only at the
-// path's end, sky on a miss), and its item equals its slot when the pool holds the chunk (the direct seeding):
-// neither is stored, 16 B less written and read per segment.
-template <bool kLean = false>
 __device__ __forceinline__ void store_path(const WaveBuffers &B, uint32_t slot, const PathState &ps, uint32_t item) {
     float4 a, b;
     uint2 c;
     pack_path(ps, item, a, b, c);
-    if (kLean) {
-        B.pa[slot] = make_float4(a.x, a.y, a.z, b.z);  // (T, rng)
-        B.pc[slot] = c;
-        return;
-    }
     B.pa[slot] = a;
     B.pb[slot] = b;
     B.pc[slot] = c;
 }
 
-// The lean state travels with its ray (OCTPT_LEAN_POS, round 5): shade stores it at the continuing ray's queue
+// The lean state (WaveBuffers::lean): the 24-B path state (T, rng) + (cur, bits).  The radiance L of
+// a path that continues is exactly 0 when the scene has no emitters and no sun sampling (it is added only at the
+// path's end, sky on a miss), and its item equals its slot when the pool holds the chunk (the direct seeding):
+// neither is stored, 16 B less written and read per segment.
+// It travels with its ray (round 5): shade stores it at the continuing ray's queue
 // position (queue q: (T, rng) in pa for q = 0, pb for q = 1 -- pb is free in the lean state -- and (cur, bits) in
 // pc's half q), so the next shade reads it at the position it reads the ray and hit records at, coalesced and
 // without waiting for the ray record's slot word.
-#ifndef OCTPT_LEAN_POS
-#define OCTPT_LEAN_POS 1
-#endif
 __device__ __forceinline__ void store_lean_at(const WaveBuffers &B, uint32_t q, uint32_t pos, const PathState &ps) {
     float4 a, b;
     uint2 c;
@@ -2017,15 +1974,8 @@ __device__ __forceinline__ void unpack_path(float4 a, float4 b, uint2 c, float4 
     ps.path_segs = (c.y >> 16) & 127u;
     ps.seg_base = c.y >> 23;
 }
-template <bool kLean = false>
 __device__ __forceinline__ void load_path(const WaveBuffers &B, uint32_t slot, float4 r0, float4 r1, PathState &ps,
                                           uint32_t &item) {
-    if (kLean) {  // L = +0 as the path started, item = slot (store_path<true>)
-        const float4 a = B.pa[slot];
-        unpack_path(make_float4(a.x, a.y, a.z, 0.0f), make_float4(0.0f, 0.0f, a.w, __uint_as_float(slot)), B.pc[slot],
-                    r0, r1, ps, item);
-        return;
-    }
     unpack_path(B.pa[slot], B.pb[slot], B.pc[slot], r0, r1, ps, item);
 }
 
@@ -2148,22 +2098,16 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         // item is dropped, so shard k's items fill segment k in item order -- position item - lo, the
         // count set by block 0 -- without a queue ticket per wave (8.3 M atomics per C3 frame on 64
         // counters, ~2 ms at their measured rate, tools/atomic_bench.hip)
-#ifndef OCTPT_SEED_TICKET  // (A/B build: every wave takes a queue ticket)
         if (((R.W | R.H) & (kTile - 1u)) == 0u) {
             if (blockIdx.x == 0u && threadIdx.x < kSegs)
                 B.ctrl[ctr_count(0u, threadIdx.x)] = shard_lo(threadIdx.x + 1u, chunk_items) - shard_lo(threadIdx.x, chunk_items);
-#if OCTPT_CAM_RECORDS
             if (ok) store_cam_ray(B, seg * B.seg_cap + (item - lo), ps);
             if (blockIdx.x == 0u && threadIdx.x == 0u) B.ray0[0][0] = B.eye;  // the camera records' origin record
-#else
-            if (ok) store_ray(B, 0u, seg * B.seg_cap + (item - lo), slot, ps);
-#endif
             // every item has its pixel (no tile overhangs the image), so the chunk starts chunk_items paths: one
             // add by block 0 instead of a counter flush per wave (8.3 M per C3 frame)
             if (blockIdx.x == 0u && threadIdx.x == 0u) atomicAdd(&stats[kStatPaths], (unsigned long long)chunk_items);
             return;
         }
-#endif
     } else {
         ItemCursor cur = {seg, true};
         ok = regen<true>(C, R, B, i, i < n_seed, chunk_items, cur, ps, cnt);
@@ -2177,9 +2121,6 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
 // its ray idles until at least `refill` lanes of the wave are idle, then the wave hands the idle
 // lanes the next positions of the chunk it has claimed (Aila & Laine dynamic fetch, with the
 // atomic of the next claim already in flight).
-#ifndef OCTPT_EXTEND_WAVES
-#define OCTPT_EXTEND_WAVES 1
-#endif
 // minimum waves per SIMD a wf_extend_kernel instance is compiled for (register budget)
 // (measured at 64 spp against the unconstrained allocation: the few spilled dwords sit in cold
 // code, the extra waves hide the slot loads' latency)
@@ -2203,9 +2144,6 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
 #define OCTPT_CLAIM 64
 #endif
 constexpr uint32_t kClaim = OCTPT_CLAIM;
-#ifndef OCTPT_XCD_SEGS
-#define OCTPT_XCD_SEGS 0
-#endif
 static_assert(kSegs % 8u == 0u, "eight XCDs share the segments evenly");
 // refill == 0 (adaptive): rays shorter than this many ESVO steps on average refill 32 at a time
 #ifndef OCTPT_THR_LONG
@@ -2227,22 +2165,14 @@ __global__ __launch_bounds__(kBlock, OCTPT_EXTEND_WAVES_OF(kPrims)) void wf_exte
     // refill bit 31 (launch_wf_extend's cam): the queue holds the seed's 16-B camera records (store_cam_ray), whose
     // origin record (eye, kPrimNone) the seed left at ray0[0] (no LDS for it: one more LDS granule per block
     // takes the depth-10 box instance from 7 blocks per CU to 6)
-    const bool cam = OCTPT_CAM_RECORDS && (refill >> 31) != 0u;
+    const bool cam = (refill >> 31) != 0u;
     refill &= 0x7FFFFFFFu;
     if (blockIdx.x == 0 && threadIdx.x < kSegs) {  // the other queue is refilled by this iteration's shade
         B.ctrl[ctr_count(q ^ 1u, threadIdx.x)] = 0u;
         B.ctrl[ctr_head(q ^ 1u, threadIdx.x)] = 0u;
     }
     // the wave starts on its home segment (seg, seg_n rays: wave-uniform)
-#if OCTPT_XCD_SEGS
-    // XCD-aware home segments (A/B knob): blocks are dealt round robin over the 8 XCDs (block b on XCD b % 8), so
-    // XCD x takes the 8 contiguous segments 8x .. 8x + 7 -- one band of the image per XCD, whose geometry its own L2
-    // holds -- instead of the two bands 4x .. 4x + 3 and 4x + 32 .. 4x + 35 the plain modulo gives it
-    uint32_t seg = __builtin_amdgcn_readfirstlane(
-        (blockIdx.x % 8u) * (kSegs / 8u) + ((blockIdx.x / 8u) * (kBlock / 64u) + (threadIdx.x >> 6)) % (kSegs / 8u));
-#else
     uint32_t seg = __builtin_amdgcn_readfirstlane(((blockIdx.x * kBlock + threadIdx.x) >> 6) % kSegs);
-#endif
     uint32_t seg_n = B.ctrl[ctr_count(q, seg)];
     // (the block-model instance holds seg_n in an SGPR: in a VGPR it was spilled, C5 extend -1 %)
     if constexpr (kPrims == kPrimsModels) seg_n = __builtin_amdgcn_readfirstlane(seg_n);
@@ -2306,12 +2236,6 @@ __global__ __launch_bounds__(kBlock, OCTPT_EXTEND_WAVES_OF(kPrims)) void wf_exte
                                         (__float_as_uint(r1.w) >> 31) != 0u);
                     esvo_begin(S, tr, E, stk, bm);
                     cnt.steps -= E.iter;  // a beam start's bound of skipped iterations: executed ones are counted
-#if OCTPT_LEAD_LOOP
-                    // the ray's leading descends (octree_traversal.rs:216-244, exact replicas counted in E.iter) in a
-                    // tight loop of the refilled lanes, while the wave refills anyway, instead of one main-loop step
-                    // per level (A/B knob)
-                    lead_descends(S, E, stk);
-#endif
                 }
             }
             const uint32_t took = min((uint32_t)__popcll(im), avail);
@@ -2380,14 +2304,13 @@ __global__ __launch_bounds__(kBlock, OCTPT_EXTEND_WAVES_OF(kPrims)) void wf_exte
 // it finished (its colour record written).  first (wave-uniform: the chunk's first shade, whose
 // rays the seed started): the path state is rebuilt from the slot's item as the seed computed it,
 // through the same pack / unpack as a stored path, instead of being read.
-// kLean with OCTPT_LEAN_POS: the state is read at (q, pos) and a continuing path's is not stored here: the caller
+// kLean: the state is read at (q, pos) and a continuing path's is not stored here: the caller
 // stores it at the position its next ray takes (store_lean_at).
 template <bool kNee, bool kLean = false, int kSP = kPrimsModels>
 __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C, const DevRender &R,
                                            const WaveBuffers &B, bool first, float4 r0, float4 r1, const uint2 *hit_rec,
                                            const uint4 *hit4_rec, PathState &ps, uint32_t &slot, uint32_t &item,
                                            Counters &cnt, uint32_t q = 0u, uint32_t pos = 0u) {
-    constexpr bool kPos = kLean && OCTPT_LEAN_POS;
     slot = __float_as_uint(r1.w) & (kRayBeamBit - 1u);
     if (first) {
         item = kLean ? slot : B.item0[slot];
@@ -2398,12 +2321,12 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
         uint2 c;
         pack_path(s0, item, a, b, c);
         unpack_path(a, b, c, B.eye, r1, ps, item);  // a camera ray's ray0 is (eye, kPrimNone): not re-read
-    } else if constexpr (kPos) {  // L = +0 as the path started, item = slot (store_lean_at)
+    } else if constexpr (kLean) {  // L = +0 as the path started, item = slot (store_lean_at)
         const float4 a = (q ? B.pb : B.pa)[pos];
         unpack_path(make_float4(a.x, a.y, a.z, 0.0f), make_float4(0.0f, 0.0f, a.w, __uint_as_float(slot)),
                     B.pc[(size_t)q * kSegs * B.seg_cap + pos], r0, r1, ps, item);
     } else {
-        load_path<kLean>(B, slot, r0, r1, ps, item);
+        load_path(B, slot, r0, r1, ps, item);
     }
     // the hit record: 8 B, or in block-value scenes (a uniform branch) 16 B with its (u, v) (C23)
     uint2 hr;
@@ -2420,7 +2343,7 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
         // a beam-started camera ray that reached the reference's step cap (extend's kHitCapped record): the
         // same ray is queued again without its beam start, for the walk from the cube entry.  No segment
         // is counted; the path state is the seed's (stored now when this shade rebuilt it from the item).
-        if (first && !kPos) store_path<kLean>(B, slot, ps, item);
+        if (first && !kLean) store_path(B, slot, ps, item);
         ps.n = V(0.0f, 0.0f, 0.0f);
         ps.beam = 0.0f;
         cnt.redo++;
@@ -2446,7 +2369,7 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
     bool cont = shade_segment<kNee, kLean>(S, R, ps, hit, cnt);
     if (cont) cont = begin_segment(ps);
     if (cont) {
-        if (!kPos) store_path<kLean>(B, slot, ps, item);
+        if (!kLean) store_path(B, slot, ps, item);
         if (kNee && ps.shadow) {  // a shadow segment follows: new sun sample or the next one
             if (!was_shadow) store_nee(B, slot, ps);
             store_att(B, slot, ps);
@@ -2455,7 +2378,7 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
     }
     // segments this item reports (a branch > 0 reports none of the replayed prefix) and whether the
     // first reflection split (C20)
-    const uint32_t segs = ((OCTPT_LEAN_STRICT && kLean) || ps.branch == 0u) ? ps.path_segs
+    const uint32_t segs = (kLean || ps.branch == 0u) ? ps.path_segs
                                                                              : (ps.depth ? ps.path_segs - ps.seg_base : 0u);
     B.color[item] = make_float4(ps.L.x, ps.L.y, ps.L.z, __uint_as_float(segs | (ps.depth ? 0x80000000u : 0u)));
     return false;
@@ -2485,7 +2408,7 @@ constexpr uint32_t kShadeLdsBlocks = OCTPT_SHADE_LDS_BLOCKS;
 // every item); the instance without it is 19 VGPRs leaner (96 instead of 115, 5 waves/SIMD instead of 4).
 // kMode: 0 = the 40-B path state, no regeneration; 1 = with regeneration; 2 = the lean 24-B path state (no
 // regeneration, no sun sampling, kLean above)
-// kNoFirst (OCTPT_SHADE_FIRST_SPLIT): an instance for the chunk's later launches, compiled without the first
+// kNoFirst: an instance for the chunk's later launches, compiled without the first
 // launch's path-state rebuild (first is 0)
 template <bool kNee, bool kLdsMats, int kMode, bool kNoFirst = false, int kSP = kPrimsModels>
 __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT_SHADE_WAVES) void wf_shade_kernel(DevScene Sg, DevCamera C, DevRender R, WaveBuffers B,
@@ -2548,7 +2471,7 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT
         const uint32_t t = wave_ticket(B.ctrl + ctr_count(q ^ 1u, seg), append);
         if (append) {
             store_ray(B, q ^ 1u, seg0 + t, slot, ps);
-            if constexpr (kMode == 2 && OCTPT_LEAN_POS) store_lean_at(B, q ^ 1u, seg0 + t, ps);
+            if constexpr (kMode == 2) store_lean_at(B, q ^ 1u, seg0 + t, ps);
         }
     }
     cnt.ib = 0u;  // issued bytes are extend's only
@@ -2616,7 +2539,7 @@ __global__ __launch_bounds__(kBlock) void wf_drain_kernel(DevScene S, DevRender 
                                        : shade_lane<kNee, false>(S, DevCamera{}, R, B, false, r0, r1, &hr, &h4, ps, slot, item, cnt);
                 if (!cont) break;
                 // the lean state back at this path's queue position, where its next shade_lane reads it
-                if (OCTPT_LEAN_POS && lean) store_lean_at(B, q, p, ps);
+                if (lean) store_lean_at(B, q, p, ps);
                 // the next segment's ray record, as store_ray writes it
                 r0 = make_float4(ps.o.x, ps.o.y, ps.o.z, __uint_as_float(ps.last_prim));
                 r1 = make_float4(ps.d.x, ps.d.y, ps.d.z,
@@ -2757,10 +2680,6 @@ __device__ __forceinline__ float beam_pack(float t, uint32_t nodes) {
     return __uint_as_float(((b - (kBeamIterMask + 1u)) & ~kBeamIterMask) | bound);
 }
 
-#ifndef OCTPT_BEAM_COOP
-#define OCTPT_BEAM_COOP 1
-#endif
-#if OCTPT_BEAM_COOP
 // Round 5: kBeamLanes lanes per beam tile, lane j standing for child j of the octant the
 // walk is in.  Entering an octant tests its eight children's boxes at once (while its node slot is in flight),
 // and each iteration takes the nearest child still nearer than the best leaf so far (a min over the group's
@@ -2891,113 +2810,6 @@ __global__ __launch_bounds__(64) void beam_kernel(DevScene S, DevCamera C, DevRe
     }
     if (lane == 0u) beam[tile] = exhausted ? 0.0f : beam_pack(best * (1.0f - 0x1p-16f), nodes);
 }
-#else
-__global__ __launch_bounds__(64) void beam_kernel(DevScene S, DevCamera C, DevRender R, uint32_t n_tiles,
-                                                  float *__restrict__ beam) {
-    // thread i: beam tile i % kBeamSub of the shard's render tile i / kBeamSub (item_pixel's tile order),
-    // so a rank of N computes only its own tiles' starts
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n_tiles) return;
-    const uint32_t rt = dealt_tile(R.tile_order, R.shard_index + (i / kBeamSub) * R.shard_count), sub = i % kBeamSub;
-    const uint32_t rty = udiv_c(rt, R.div_tiles_x);
-    const uint32_t x0 = (rt - rty * R.tiles_x) * kTile + (sub % (kTile / kBeamTile)) * kBeamTile,
-                   y0 = rty * kTile + (sub / (kTile / kBeamTile)) * kBeamTile;
-    if (x0 >= R.W || y0 >= R.H) return;  // no pixel of the image: never read
-    const uint32_t tile = (y0 / kBeamTile) * R.beam_tx + x0 / kBeamTile;
-    const uint32_t x1 = min(x0 + kBeamTile, R.W), y1 = min(y0 + kBeamTile, R.H);
-    // screen coordinates of the tile's rays (new_path: xn + dx, yn + dy), padded by 2 % + 1e-6
-    float s0 = ((float)(2u * x0) - (float)R.W) / R.dim, s1 = ((float)(2u * x1) - (float)R.W) / R.dim;
-    float t0 = ((float)(2u * (R.H - y1)) - (float)R.H) / R.dim, t1 = ((float)(2u * (R.H - y0)) - (float)R.H) / R.dim;
-    const float ps = 0.02f * (s1 - s0) + 1e-6f, pt = 0.02f * (t1 - t0) + 1e-6f;
-    s0 -= ps; s1 += ps; t0 -= pt; t1 += pt;
-    const v3 F = vscale(V(C.dir[0], C.dir[1], C.dir[2]), C.d_factor);
-    const v3 Rt = V(C.right[0], C.right[1], C.right[2]), Up = V(C.up[0], C.up[1], C.up[2]);
-    const v3 Ek[4] = {vadd(vadd(F, vscale(Rt, s0)), vscale(Up, t0)), vadd(vadd(F, vscale(Rt, s1)), vscale(Up, t0)),
-                      vadd(vadd(F, vscale(Rt, s1)), vscale(Up, t1)), vadd(vadd(F, vscale(Rt, s0)), vscale(Up, t1))};
-    const v3 Ec = vadd(vadd(F, vscale(Rt, 0.5f * (s0 + s1))), vscale(Up, 0.5f * (t0 + t1)));
-    v3 pn[4];
-    for (int k = 0; k < 4; ++k) {
-        v3 n = vcross(Ek[k], Ek[(k + 1) & 3]);
-        if (vdot(n, Ec) < 0.0f) n = vscale(n, -1.0f);
-        pn[k] = n;
-    }
-    // the eye as esvo_begin places a ray origin in octree space
-    const v3 e = vadd(vscale(V(C.eye[0], C.eye[1], C.eye[2]), S.octree_scale), V(1.0f, 1.0f, 1.0f));
-    const uint32_t om = (Ec.x < 0.0f ? 1u : 0u) | (Ec.y < 0.0f ? 2u : 0u) | (Ec.z < 0.0f ? 4u : 0u);
-    // distance from the eye to the box [lo, lo + h], or -1 when the box lies outside the pyramid
-    auto box = [&](v3 lo, float h) -> float {
-        const v3 a = vsub(lo, e), b = vsub(vadd(lo, V(h, h, h)), e);
-        const float ext = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(b.x)), fmaxf(fabsf(a.y), fabsf(b.y))),
-                                fmaxf(fabsf(a.z), fabsf(b.z)));
-        for (int k = 0; k < 4; ++k) {
-            const v3 n = pn[k];
-            const float mx = (fmaxf(n.x * a.x, n.x * b.x) + fmaxf(n.y * a.y, n.y * b.y)) + fmaxf(n.z * a.z, n.z * b.z);
-            const float tol = 1e-5f * ((fabsf(n.x) + fabsf(n.y)) + fabsf(n.z)) * ext;
-            if (mx < -tol) return -1.0f;
-        }
-        const float dx = a.x > 0.0f ? a.x : (b.x < 0.0f ? -b.x : 0.0f);
-        const float dy = a.y > 0.0f ? a.y : (b.y < 0.0f ? -b.y : 0.0f);
-        const float dz = a.z > 0.0f ? a.z : (b.z < 0.0f ? -b.z : 0.0f);
-        return sqrtf((dx * dx + dy * dy) + dz * dz);
-    };
-    // an octant whose cell is at most kBeamLod tile footprints wide at its distance counts as a leaf
-    // (conservative: it holds all its leaves; 0 = walk down to the leaf cells)
-    const float lod = kBeamLod * fmaxf(s1 - s0, t1 - t0) / sqrtf(vdot(F, F));
-    float best = __builtin_inff();
-    // the walk's stack in LDS, [level][thread], for the scene's depth levels (launch_beam sizes it:
-    // 6 x depth x 64 x 4 B, 12 KB at depth 8, so that 10+ blocks share a CU instead of 4 at a fixed 24
-    // levels): octant base, mask, children still to visit (in front-to-back order: bit k = child k ^ om)
-    // and the cell's low corner
-    extern __shared__ uint32_t beam_lds[];
-    const uint32_t t = threadIdx.x, L = beam_levels(S.depth);
-    uint32_t *const st_base = beam_lds, *const st_mask = beam_lds + L * 64u, *const st_rem = beam_lds + 2u * L * 64u;
-    float *const st_lx = reinterpret_cast<float *>(beam_lds + 3u * L * 64u);
-    float *const st_ly = reinterpret_cast<float *>(beam_lds + 4u * L * 64u);
-    float *const st_lz = reinterpret_cast<float *>(beam_lds + 5u * L * 64u);
-    auto order = [&](uint32_t m) {  // present children, permuted so that bit k = child k ^ om
-        uint32_t pm = m & 0xFFu;
-        if (om & 1u) pm = ((pm & 0x55u) << 1) | ((pm >> 1) & 0x55u);
-        if (om & 2u) pm = ((pm & 0x33u) << 2) | ((pm >> 2) & 0x33u);
-        if (om & 4u) pm = ((pm & 0x0Fu) << 4) | ((pm >> 4) & 0x0Fu);
-        return pm;
-    };
-    bool exhausted = S.depth >= (uint32_t)kBeamLevels;
-    uint32_t nodes = 1u;  // octants the walk entered (the root included)
-    if (!exhausted && box(V(1.0f, 1.0f, 1.0f), 1.0f) >= 0.0f) {
-        int lv = 0;
-        st_base[t] = S.root;
-        st_mask[t] = S.root_mask;
-        st_rem[t] = order(S.root_mask);
-        st_lx[t] = st_ly[t] = st_lz[t] = 1.0f;
-        uint32_t visits = 0u;
-        while (lv >= 0) {
-            const uint32_t rem = st_rem[lv * 64 + t];
-            if (rem == 0u) { --lv; continue; }
-            if (++visits > kBeamVisits) { exhausted = true; break; }
-            st_rem[lv * 64 + t] = rem & (rem - 1u);
-            const uint32_t ci = (uint32_t)(__ffs(rem) - 1) ^ om;
-            const uint32_t m = st_mask[lv * 64 + t], kind = (m >> ci) & 0x101u;
-            const float h = __uint_as_float((126u - (uint32_t)lv) << 23);  // 2^-(lv + 1)
-            const v3 lo = V(st_lx[lv * 64 + t] + ((ci & 1u) ? h : 0.0f), st_ly[lv * 64 + t] + ((ci & 2u) ? h : 0.0f),
-                            st_lz[lv * 64 + t] + ((ci & 4u) ? h : 0.0f));
-            const float d = box(lo, h);
-            if (d < 0.0f || d >= best) continue;
-            if (kind == 0x101u || lv + 1 >= (int)L || h <= lod * d) { best = d; continue; }  // leaf / small cell
-            const uint2 slot = S.node_child[st_base[lv * 64 + t] + __popc(m & ((1u << ci) - 1u))];
-            ++lv;
-            ++nodes;
-            st_base[lv * 64 + t] = slot.x;
-            st_mask[lv * 64 + t] = slot.y;
-            st_rem[lv * 64 + t] = order(slot.y);
-            st_lx[lv * 64 + t] = lo.x;
-            st_ly[lv * 64 + t] = lo.y;
-            st_lz[lv * 64 + t] = lo.z;
-        }
-    }
-    beam[tile] = exhausted ? 0.0f : beam_pack(best * (1.0f - 0x1p-16f), nodes);
-}
-
-#endif
 
 __global__ void tonemap_kernel(const float4 *__restrict__ accum, uchar4 *__restrict__ out, uint32_t n,
                                const uint8_t *__restrict__ lut) {
@@ -3119,29 +2931,23 @@ hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q,
     return hipGetLastError();
 }
 
-#ifndef OCTPT_SHADE_FIRST_SPLIT
-#define OCTPT_SHADE_FIRST_SPLIT 1  // round 6: C3 +0.2..0.4 %, C5b +0.2..0.6 %, C4 +0.25 % (profiles/r06/shade_first_split_ab.txt)
-#endif
-// the shade instance a scene and chunk launch (sun sampling, LDS material tables, regeneration, lean state; with
-// OCTPT_SHADE_FIRST_SPLIT the lean state's later launches, first == false, take the instance without the rebuild)
-#ifndef OCTPT_SHADE_COLOUR
-#define OCTPT_SHADE_COLOUR 1  // sphere scenes with colour textures only get an instance without the image path (A/B knob)
-#endif
-#ifndef OCTPT_SHADE_PRIMS
-#define OCTPT_SHADE_PRIMS 1  // round 6: the lean instance per primitive kind (C3 +0.15..0.35 %, profiles/r06/shade_prims_ab.txt)
-#endif
+// the shade instance a scene and chunk launch (sun sampling, LDS material tables, regeneration, lean state).
+// The lean state's later launches, first == false, take the instance without the rebuild (round 6: C3 +0.2..0.4 %,
+// C5b +0.2..0.6 %, C4 +0.25 %, profiles/r06/shade_first_split_ab.txt), and the lean instances are compiled per
+// primitive kind (round 6: C3 +0.15..0.35 %, profiles/r06/shade_prims_ab.txt); sphere scenes with colour textures
+// only get an instance without the image path
 template <bool kLds, int kSP>
 static const void *lean_shade_of(bool first) {
-    return (OCTPT_SHADE_FIRST_SPLIT && !first) ? reinterpret_cast<const void *>(wf_shade_kernel<false, kLds, 2, true, kSP>)
-                                                : reinterpret_cast<const void *>(wf_shade_kernel<false, kLds, 2, false, kSP>);
+    return !first ? reinterpret_cast<const void *>(wf_shade_kernel<false, kLds, 2, true, kSP>)
+                  : reinterpret_cast<const void *>(wf_shade_kernel<false, kLds, 2, false, kSP>);
 }
 template <bool kNee, bool kLds>
 static const void *shade_instance_of(int mode, bool first, int prims) {
-    if (!kNee && mode == 2) {  // the lean instances: per primitive kind (OCTPT_SHADE_PRIMS) and by launch (first)
-        if (OCTPT_SHADE_PRIMS && prims == kShadeSphColour) return lean_shade_of<kLds, kShadeSphColour>(first);
-        if (OCTPT_SHADE_PRIMS && prims == kPrimsSpheres) return lean_shade_of<kLds, kPrimsSpheres>(first);
-        if (OCTPT_SHADE_PRIMS && prims == kPrimsBoxes) return lean_shade_of<kLds, kPrimsBoxes>(first);
-        if (OCTPT_SHADE_PRIMS && prims == kPrimsBlocks) return lean_shade_of<kLds, kPrimsBlocks>(first);
+    if (!kNee && mode == 2) {  // the lean instances: per primitive kind and by launch (first)
+        if (prims == kShadeSphColour) return lean_shade_of<kLds, kShadeSphColour>(first);
+        if (prims == kPrimsSpheres) return lean_shade_of<kLds, kPrimsSpheres>(first);
+        if (prims == kPrimsBoxes) return lean_shade_of<kLds, kPrimsBoxes>(first);
+        if (prims == kPrimsBlocks) return lean_shade_of<kLds, kPrimsBlocks>(first);
         return lean_shade_of<kLds, kPrimsModels>(first);
     }
     return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1>)
@@ -3154,7 +2960,7 @@ static const void *shade_instance(const DevScene &S, int mode, bool first = fals
                       : S.has_models  ? kPrimsModels
                       : S.has_cuboids ? kPrimsBoxes
                       : S.has_images  ? kPrimsSpheres
-                                      : (OCTPT_SHADE_COLOUR ? kShadeSphColour : kPrimsSpheres);
+                                      : kShadeSphColour;
     return S.sun.sun_sampling
                ? (lds ? shade_instance_of<true, true>(mode, first, prims) : shade_instance_of<true, false>(mode, first, prims))
                : (lds ? shade_instance_of<false, true>(mode, first, prims) : shade_instance_of<false, false>(mode, first, prims));
@@ -3229,13 +3035,8 @@ hipError_t launch_intersect(const DevScene &S0, const float *rays, const uint32_
 
 hipError_t launch_beam(const DevScene &S, const DevCamera &C, const DevRender &R, float *beam, hipStream_t stream) {
     const uint32_t n = R.shard_tiles * kBeamSub;  // the shard's render tiles' beam tiles
-#if OCTPT_BEAM_COOP
     const size_t lds = (64u + 5u * (64u / kBeamLanes)) * beam_levels(S.depth) * sizeof(uint32_t);
     const uint32_t per_block = 64u / kBeamLanes;
-#else
-    const size_t lds = 6u * beam_levels(S.depth) * 64u * sizeof(uint32_t);
-    const uint32_t per_block = 64u;
-#endif
     hipLaunchKernelGGL(beam_kernel, dim3((n + per_block - 1u) / per_block), dim3(64), lds, stream, S, C, R, n, beam);
     return hipGetLastError();
 }
