@@ -371,6 +371,58 @@ octpt_status octpt_traversal_data(const octpt_octant *octants, uint32_t octant_c
 octpt_status octpt_get_stats(const octpt_ctx *ctx, octpt_stats *stats);
 octpt_status octpt_reset_stats(octpt_ctx *ctx);
 
+/* --- first-hit guide buffers and the preview denoiser ---------------------- */
+/* Camera::get_ray (camera.rs:77-86) at the pixel centres of a width x height frame: rays[6 * (y * width + x)]
+ * = (origin xyz, unit direction xyz), image order, top row first.  The same f32 expressions in the same
+ * order as octpt_set_camera's basis and the kernels' un-jittered camera ray (preview, guide buffers), so a
+ * ray from here is bit-identical to the ray the device traces for that pixel: what a host needs to turn a
+ * mouse click into an octpt_intersect ray.  Host-only, no context. */
+octpt_status octpt_camera_rays(const octpt_camera *camera, uint32_t width, uint32_t height, float *rays);
+
+/* First-hit guide buffers (AOVs) of the preview's camera ray (C24): one un-jittered ray per pixel, continued
+ * through material-0 and alpha-0 hits exactly as RendererMode::Preview continues it (preview_render,
+ * path_tracer.rs:137-158; next_intersection_preview :447-455); the buffers describe the hit the preview
+ * shades.  Any pointer may be NULL = not wanted.  Layout as octpt_render's accum: width * height pixels in
+ * image order, or the shard's compact tiles with OCTPT_RENDER_SHARD_COMPACT. */
+typedef struct octpt_aov_buffers {
+    float *albedo;      /* 4 floats / pixel: the hit's texture colour (linear rgb, alpha); miss 0,0,0,0 */
+    float *normal;      /* 4 floats / pixel: world normal of the hit, w = 0; miss 0 */
+    float *depth;       /* 1 float / pixel: world distance eye -> first visible hit along the ray; miss +inf */
+    uint32_t *prim;     /* octpt_intersect's encoding (block id / 0x40000000 | quad in block scenes); miss 0xFFFFFFFF */
+    uint32_t *material; /* material index of the hit (never 0, the outer medium); miss 0 */
+} octpt_aov_buffers;
+/* Host arrays.  Of the render parameters only width, height, shard_index, shard_count and
+ * OCTPT_RENDER_SHARD_COMPACT are honoured (a set tile order is followed); spp, depth, seed and the other
+ * flags are ignored.  octpt_stats counts the pass as a preview does (paths, segments, esvo_steps).  On a
+ * multi-device context it runs on devices[0].  All five pointers NULL: OK, nothing is launched. */
+octpt_status octpt_render_aov(octpt_ctx *ctx, const octpt_render_params *p, const octpt_aov_buffers *host);
+/* The same into device buffers, enqueued on `hip_stream` (NULL = default stream); returns once enqueued. */
+octpt_status octpt_render_aov_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_aov_buffers *dev,
+                                     void *hip_stream);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika & Lensch 2010) for low-spp previews (C25):
+ * `iterations` passes of a 5x5 B3-spline kernel, pass i with tap spacing 2^i and colour sigma
+ * sigma_color * 2^-i, each tap weighted by its colour, normal and relative depth distance to the centre.
+ * Guides: normal and depth of octpt_render_aov (full frame), and albedo with OCTPT_DENOISE_DEMODULATE -- the
+ * filter then runs on color.rgb / max(albedo.rgb, 1e-3) and multiplies the albedo back, which keeps texture
+ * detail.  Pixels with depth +inf (misses) are copied through and never contribute; alpha is copied. */
+#define OCTPT_DENOISE_DEMODULATE 0x1u
+typedef struct octpt_denoise_params {
+    uint32_t width, height;
+    uint32_t iterations; /* 1..5 */
+    float sigma_color, sigma_normal, sigma_depth; /* > 0, finite */
+    uint32_t flags;      /* OCTPT_DENOISE_DEMODULATE */
+} octpt_denoise_params;
+/* d_color, d_out: width * height * 4 floats on the device (d_out may alias d_color); d_guides: device
+ * pointers.  One launch per iteration on `hip_stream` between two frames the context owns, no host
+ * synchronisation; returns once enqueued.  The two frames are shared by the context's denoise calls: calls
+ * on different streams must be ordered by the caller.  On a multi-device context it runs on devices[0]. */
+octpt_status octpt_denoise_device(octpt_ctx *ctx, const octpt_denoise_params *p, const float *d_color,
+                                  const octpt_aov_buffers *d_guides, float *d_out, void *hip_stream);
+/* The same over host arrays (out may alias color). */
+octpt_status octpt_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const float *color,
+                           const octpt_aov_buffers *guides, float *out);
+
 /* --- host octree builder (replaces the Rust-side build for primitive scenes) ---
  * Voxelises spheres/cuboids into depth-`depth` leaf cells, Morton-sorts
  * them (new_octree.rs:752-835 code order) and emits octants in pre-order. */

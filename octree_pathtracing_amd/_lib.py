@@ -162,6 +162,23 @@ class RenderParams(C.Structure):
                 ("shard_index", C.c_uint32), ("shard_count", C.c_uint32), ("flags", C.c_uint32)]
 
 
+DENOISE_DEMODULATE = 0x1  # OCTPT_DENOISE_DEMODULATE
+AOV_NAMES = ("albedo", "normal", "depth", "prim", "material")  # octpt_aov_buffers field order
+
+
+class AovBuffers(C.Structure):
+    """octpt_aov_buffers: first-hit guide buffers, NULL = not wanted."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p),
+                ("material", C.c_void_p)]
+
+
+class DenoiseParams(C.Structure):
+    """octpt_denoise_params."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("flags", C.c_uint32)]
+
+
 # octpt_stats::drain order (OCTPT_STAT_*)
 STAT_NAMES = ("paths", "segments", "esvo_steps", "sphere_tests", "cuboid_tests", "shade_events", "texel_reads",
               "block_tests", "issued_bytes")
@@ -218,6 +235,11 @@ SIGNATURES = {
     "octpt_balance_tiles": (_i32, [_u32, _u32, _u32, _vp, _vp]),
     "octpt_intersect": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "octpt_traversal_data": (_i32, [_vp, _u32, _u32, _u32, _vp, _f, _vp, _vp, _vp, _vp]),
+    "octpt_camera_rays": (_i32, [C.POINTER(Camera), _u32, _u32, _vp]),
+    "octpt_render_aov": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers)]),
+    "octpt_render_aov_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers), _vp]),
+    "octpt_denoise_device": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp, _vp]),
+    "octpt_denoise": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp]),
     "octpt_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "octpt_reset_stats": (_i32, [_vp]),
     "octpt_build_octree": (_i32, [_vp, _u32, _vp, _u32, _u32, C.POINTER(_vp)]),

@@ -134,6 +134,9 @@ struct octpt_ctx {
     float4 *m_acc = nullptr;
     uint32_t *m_seg = nullptr;
     size_t m_acc_cap = 0, m_seg_cap = 0;
+    // the denoiser's two ping-pong frames (octpt_denoise_device, C25), allocated on first use, grow-only
+    float4 *dn_frame[2] = {nullptr, nullptr};
+    size_t dn_cap[2] = {0, 0};
     // the tile deal (octpt_set_tile_order): for order_w x order_h frames, dealing position -> frame tile and
     // its inverse, on this context's device; empty = the round-robin deal
     std::vector<uint32_t> h_order;
@@ -1549,6 +1552,8 @@ void octpt_destroy(octpt_ctx *ctx) {
     if (ctx->d_order_pos) (void)hipFree(ctx->d_order_pos);
     if (ctx->m_acc) (void)hipFree(ctx->m_acc);
     if (ctx->m_seg) (void)hipFree(ctx->m_seg);
+    for (float4 *f : ctx->dn_frame)
+        if (f) (void)hipFree(f);
     if (ctx->d_stats) (void)hipFree(ctx->d_stats);
     if (ctx->d_lut_float) (void)hipFree(ctx->d_lut_float);
     if (ctx->d_lut_byte) (void)hipFree(ctx->d_lut_byte);
@@ -2098,6 +2103,215 @@ octpt_status octpt_intersect(octpt_ctx *ctx, const float *rays, const uint32_t *
         if (steps) steps[r] = 0u;
     }
     return OCTPT_OK;
+}
+
+// ---------------- first-hit guide buffers (C24) and the preview denoiser (C25) ----------------
+namespace {
+
+// the render layout of a guide-buffer pass: only the frame size, the shard and the compact flag apply
+octpt_status make_aov_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender &R) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
+    octpt_render_params q{};
+    q.width = p->width;
+    q.height = p->height;
+    q.spp_count = 1u;
+    q.max_depth = 1u;
+    q.branch_count = 1u;
+    q.shard_index = p->shard_index;
+    q.shard_count = p->shard_count;
+    q.flags = p->flags & OCTPT_RENDER_SHARD_COMPACT;
+    const bool ktiming = ctx->ktiming;
+    const octpt_status st = make_render(ctx, &q, R);
+    ctx->ktiming = ktiming;
+    return st;
+}
+
+bool aov_any(const octpt_aov_buffers &b) { return b.albedo || b.normal || b.depth || b.prim || b.material; }
+
+octpt_status enqueue_aov(octpt_ctx *ctx, const DevRender &R, const octpt_aov_buffers &dev, hipStream_t s) {
+    if (R.total_items == 0 || !aov_any(dev)) return OCTPT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    EventPair ev{};
+    HIP_TRY(ctx, hipEventCreate(&ev.start));
+    HIP_TRY(ctx, hipEventCreate(&ev.stop));
+    ctx->pending.push_back(ev);  // destroyed by get_stats / destroy
+    HIP_TRY(ctx, hipEventRecord(ev.start, s));
+    const DevAov out{reinterpret_cast<float4 *>(dev.albedo), reinterpret_cast<float4 *>(dev.normal), dev.depth, dev.prim,
+                     dev.material};
+    const hipError_t e = launch_gbuffer(ctx->S, ctx->C, R, out, ctx->d_stats, s);
+    HIP_TRY(ctx, hipEventRecord(ev.stop, s));
+    if (e != hipSuccess) return hip_fail(ctx, e, "guide buffer launch");
+    ctx->launches++;
+    return OCTPT_OK;
+}
+
+octpt_status check_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const void *color,
+                           const octpt_aov_buffers *g, const void *out) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise params NULL");
+    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: zero frame size");
+    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: bad resolution");
+    if (p->iterations < 1u || p->iterations > 5u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: iterations must be 1..5");
+    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_depth})
+        if (!(s > 0.0f) || !std::isfinite(s))
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: sigma_color, sigma_normal and sigma_depth must be positive and finite");
+    if (p->flags & ~OCTPT_DENOISE_DEMODULATE)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "denoise: unknown flag (full frames only: no shard or compact tile layout; OCTPT_DENOISE_DEMODULATE is the one flag)");
+    if (!color || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: NULL colour or output buffer");
+    if (!g || !g->normal || !g->depth)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: the normal and depth guides are required");
+    if ((p->flags & OCTPT_DENOISE_DEMODULATE) && !g->albedo)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: OCTPT_DENOISE_DEMODULATE needs the albedo guide");
+    return OCTPT_OK;
+}
+
+}  // namespace
+
+octpt_status octpt_render_aov_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_aov_buffers *dev,
+                                     void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
+    if (!dev) return fail(ctx, OCTPT_ERR_INVALID_ARG, "guide buffers NULL");
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {  // on the first entry's replica (the caller's buffers live on its device)
+            const octpt_status st = octpt_render_aov_device(ctx->sub[0], p, dev, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        DevRender R{};
+        const octpt_status st = make_aov_render(ctx, p, R);
+        if (st != OCTPT_OK) return st;
+        return enqueue_aov(ctx, R, *dev, static_cast<hipStream_t>(stream));
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in guide buffer render");
+    }
+}
+
+octpt_status octpt_render_aov(octpt_ctx *ctx, const octpt_render_params *p, const octpt_aov_buffers *host) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
+    if (!host) return fail(ctx, OCTPT_ERR_INVALID_ARG, "guide buffers NULL");
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            const octpt_status st = octpt_render_aov(ctx->sub[0], p, host);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        DevRender R{};
+        octpt_status st = make_aov_render(ctx, p, R);
+        if (st != OCTPT_OK) return st;
+        if (R.total_items == 0 || !aov_any(*host)) return OCTPT_OK;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = accum_pixels(R);
+        // bytes per pixel of the five buffers, in octpt_aov_buffers order
+        void *const h[5] = {host->albedo, host->normal, host->depth, host->prim, host->material};
+        const size_t bpp[5] = {16, 16, 4, 4, 4};
+        void *d[5] = {};
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 5 && e == hipSuccess; ++i) {
+            if (!h[i]) continue;
+            // pixels the pass does not write (a partial shard of a full frame, tile padding) keep the caller's values
+            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) {
+            const octpt_aov_buffers dev{static_cast<float *>(d[0]), static_cast<float *>(d[1]), static_cast<float *>(d[2]),
+                                        static_cast<uint32_t *>(d[3]), static_cast<uint32_t *>(d[4])};
+            st = enqueue_aov(ctx, R, dev, ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+        }
+        for (int i = 0; i < 5 && e == hipSuccess && st == OCTPT_OK; ++i)
+            if (h[i]) e = hipMemcpy(h[i], d[i], n * bpp[i], hipMemcpyDeviceToHost);
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "guide buffer render");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in guide buffer render");
+    }
+}
+
+octpt_status octpt_denoise_device(octpt_ctx *ctx, const octpt_denoise_params *p, const float *d_color,
+                                  const octpt_aov_buffers *g, float *d_out, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_denoise(ctx, p, d_color, g, d_out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_denoise_device(ctx->sub[0], p, d_color, g, d_out, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        // the working signal lives in frame 0 after the prep pass, then ping-pongs; the last iteration writes d_out.
+        // A frame that has to grow may still be read by an earlier call on another stream: drain first
+        const bool two = p->iterations > 1u;
+        if (n > ctx->dn_cap[0] || (two && n > ctx->dn_cap[1])) HIP_TRY(ctx, hipDeviceSynchronize());
+        if ((st = grow_buf(ctx, ctx->dn_frame[0], ctx->dn_cap[0], n)) != OCTPT_OK) return st;
+        if (two && (st = grow_buf(ctx, ctx->dn_frame[1], ctx->dn_cap[1], n)) != OCTPT_OK) return st;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        DevDenoise D{};
+        D.W = p->width;
+        D.H = p->height;
+        D.sigma_color = p->sigma_color;
+        D.sn2 = p->sigma_normal * p->sigma_normal;
+        D.sz2 = p->sigma_depth * p->sigma_depth;
+        D.normal = reinterpret_cast<const float4 *>(g->normal);
+        D.albedo = (p->flags & OCTPT_DENOISE_DEMODULATE) ? reinterpret_cast<const float4 *>(g->albedo) : nullptr;
+        D.depth = g->depth;
+        HIP_TRY(ctx, launch_denoise_prep(D.W, D.H, reinterpret_cast<const float4 *>(d_color), D.albedo, D.depth,
+                                         ctx->dn_frame[0], s));
+        for (uint32_t i = 0; i < p->iterations; ++i) {
+            const bool last = i + 1u == p->iterations;
+            float4 *dst = last ? reinterpret_cast<float4 *>(d_out) : ctx->dn_frame[(i + 1u) & 1u];
+            HIP_TRY(ctx, launch_atrous(D, i, last, ctx->dn_frame[i & 1u], dst, s));
+        }
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise");
+    }
+}
+
+octpt_status octpt_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const float *color,
+                           const octpt_aov_buffers *g, float *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_denoise(ctx, p, color, g, out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_denoise(ctx->sub[0], p, color, g, out);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
+        // colour (filtered in place on the device), normal, depth, albedo
+        const void *h[4] = {color, g->normal, g->depth, demod ? g->albedo : nullptr};
+        const size_t bpp[4] = {16, 16, 4, 16};
+        void *d[4] = {};
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+            if (!h[i]) continue;
+            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) {
+            const octpt_aov_buffers dg{static_cast<float *>(d[3]), static_cast<float *>(d[1]), static_cast<float *>(d[2]),
+                                       nullptr, nullptr};
+            st = octpt_denoise_device(ctx, p, static_cast<float *>(d[0]), &dg, static_cast<float *>(d[0]), ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "denoise");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise");
+    }
 }
 
 octpt_status octpt_get_stats(const octpt_ctx *cctx, octpt_stats *out) {

@@ -1,4 +1,5 @@
-// Host-side queries of the C ABI that need no device: Octree::get_traversal_data.
+// Host-side queries of the C ABI that need no device: Octree::get_traversal_data and, at the end,
+// the camera's pixel-centre rays (octpt_camera_rays).
 //
 // get_traversal_data (octree_traversal.rs:537-714) is the reference's beam-start query: the
 // host walks one ray (GPURenderer::render_frame uses the camera's centre ray,
@@ -130,4 +131,36 @@ extern "C" octpt_status octpt_traversal_data(const octpt_octant *octants, uint32
         }
     }
     return done(scale);
+}
+
+// Camera::get_ray (camera.rs:77-86) at the pixel centres: the camera basis as octpt_set_camera derives it
+// (right = direction x up, d_factor = 1 / tan(fov / 2)) and the un-jittered ray as the preview and
+// guide-buffer kernels form it -- the same f32 operations in the same order, no contraction -- so each ray
+// is the device's ray for its pixel bit for bit.
+extern "C" octpt_status octpt_camera_rays(const octpt_camera *camera, uint32_t width, uint32_t height, float *rays) {
+    if (!camera || !rays || width == 0u || height == 0u) return OCTPT_ERR_INVALID_ARG;
+    if ((uint64_t)width * height >= (1ull << 31)) return OCTPT_ERR_INVALID_ARG;
+    if (!(camera->fov > 0.0f && camera->fov < 3.14159265f)) return OCTPT_ERR_INVALID_ARG;
+    const float *dir = camera->direction, *up = camera->up;
+    const float right[3] = {dir[1] * up[2] - up[1] * dir[2], dir[2] * up[0] - up[2] * dir[0],
+                            dir[0] * up[1] - up[0] * dir[1]};  // camera.rs:80
+    const float d_factor = 1.0f / tanf(camera->fov / 2.0f);    // camera.rs:79
+    const float dim = (float)(width > height ? width : height);
+    for (uint32_t y = 0; y < height; ++y) {
+        const float yn = ((float)(2u * (height - y) - 1u) - (float)height) / dim;
+        for (uint32_t x = 0; x < width; ++x) {
+            const float xn = ((float)(2u * x + 1u) - (float)width) / dim;
+            float nd[3];
+            for (int i = 0; i < 3; ++i) nd[i] = (dir[i] * d_factor + right[i] * xn) + up[i] * yn;
+            const float r = 1.0f / sqrtf((nd[0] * nd[0] + nd[1] * nd[1]) + nd[2] * nd[2]);
+            float *o = rays + 6u * ((size_t)y * width + x);
+            o[0] = camera->eye[0];
+            o[1] = camera->eye[1];
+            o[2] = camera->eye[2];
+            o[3] = nd[0] * r;
+            o[4] = nd[1] * r;
+            o[5] = nd[2] * r;
+        }
+    }
+    return OCTPT_OK;
 }

@@ -166,6 +166,22 @@ struct DevRender {
     const uint32_t *tile_order;
 };
 
+// octpt_aov_buffers as the guide-buffer kernel takes it (device pointers, NULL = not wanted)
+struct DevAov {
+    float4 *albedo, *normal;
+    float *depth;
+    uint32_t *prim, *material;
+};
+
+// one denoise call (octpt_denoise_params + the guides), DESIGN.md C25
+struct DevDenoise {
+    uint32_t W, H;
+    float sigma_color;                  // scaled by 2^-i in iteration i
+    float sn2, sz2;                     // sigma_normal^2, sigma_depth^2
+    const float4 *normal, *albedo;      // albedo: NULL without OCTPT_DENOISE_DEMODULATE
+    const float *depth;
+};
+
 // frame tile at dealing position s (octpt_set_tile_order's permutation, or s itself)
 __host__ __device__ inline uint32_t dealt_tile(const uint32_t *order, uint32_t s) { return order ? order[s] : s; }
 
@@ -303,6 +319,17 @@ hipError_t launch_intersect(const DevScene &S, const float *rays, const uint32_t
                             const float *last_normal, uint32_t n, float *t, uint32_t *prim, float *normal,
                             uint32_t *steps, hipStream_t stream);
 hipError_t launch_beam(const DevScene &S, const DevCamera &C, const DevRender &R, float *beam, hipStream_t stream);
+// first-hit guide buffers: the preview's walk, writing the hit it shades; out holds device
+// pointers, NULL = not written
+hipError_t launch_gbuffer(const DevScene &S, const DevCamera &C, const DevRender &R, const DevAov &out,
+                          unsigned long long *stats, hipStream_t stream);
+// the a-trous denoiser.  prep: color -> sig (the working signal: demodulated by albedo when
+// not NULL, raw on miss pixels; alpha kept).  atrous: one iteration src -> dst with tap spacing 1 << iter;
+// last: dst is the caller's frame and albedo (nullable) is multiplied back
+hipError_t launch_denoise_prep(uint32_t W, uint32_t H, const float4 *color, const float4 *albedo, const float *depth,
+                               float4 *sig, hipStream_t stream);
+hipError_t launch_atrous(const DevDenoise &D, uint32_t iter, bool last, const float4 *src, float4 *dst,
+                         hipStream_t stream);
 hipError_t launch_tonemap(const float4 *accum, uchar4 *out, uint32_t n, const uint8_t *lut_byte,
                           hipStream_t stream);
 hipError_t launch_unshard(uint32_t W, uint32_t H, uint32_t shard_count, const uint32_t *tile_pos, const float4 *shards,

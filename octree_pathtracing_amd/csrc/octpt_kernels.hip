@@ -2852,6 +2852,180 @@ __global__ void multi_stage_kernel(DevRender R, uint32_t n_dev, uint32_t stride,
     }
 }
 
+// ===========================================================================
+// First-hit guide buffers: the preview's camera ray and pass-through chain
+// (preview_kernel above), writing the hit the preview shades instead of shading it -- its texture
+// colour, normal, distance from the eye, primitive and material.  A kernel of its own, so that the
+// preview instances keep their register allocation.  One wave per 8x8 tile, one thread per pixel.
+// ===========================================================================
+#ifndef OCTPT_GBUFFER_BOUNDS
+#define OCTPT_GBUFFER_BOUNDS 1
+#endif
+// the preview's waves per SIMD (OCTPT_PREVIEW_WAVES_OF), one above the natural allocation (79 / 86 / 102 / 95
+// VGPRs for spheres / boxes / models / blocks -> 72 / 80 / 96 / 80): the distance kept across the walk costs
+// 12 / 16 / 12 / 52 B of scratch per lane, and the extra wave still wins (C3 1080p: 0.683 ms against 0.705 at
+// the natural allocation)
+#define OCTPT_GBUFFER_WAVES_OF(k) \
+    (OCTPT_GBUFFER_BOUNDS ? ((k) == kPrimsSpheres ? 7 : ((k) == kPrimsBoxes || (k) == kPrimsBlocks) ? 6 : 5) : 1)
+template <int kPrims>
+__global__ __launch_bounds__(kBlock, OCTPT_GBUFFER_WAVES_OF(kPrims)) void gbuffer_kernel(DevScene S, DevCamera C, DevRender R,
+                                                                                         DevAov out,
+                                                                                         unsigned long long *__restrict__ stats) {
+    extern __shared__ uint2 lds_stack[];
+    const Stack stk = stack_of(lds_stack, S.depth);
+    Counters cnt = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    const uint32_t item = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t x = 0u, y = 0u;
+    if (item < R.total_items) item_pixel(R, item, x, y);
+    if (item < R.total_items && x < R.W && y < R.H) {
+        PathState ps;
+        // Camera::get_ray at the pixel centre (camera.rs:77-86), no jitter: preview_kernel's ray
+        const float xn = ((float)(2u * x + 1u) - (float)R.W) / R.dim;
+        const float yn = ((float)(2u * (R.H - y) - 1u) - (float)R.H) / R.dim;
+        const v3 nd = vadd(vadd(vscale(V(C.dir[0], C.dir[1], C.dir[2]), C.d_factor),
+                                vscale(V(C.right[0], C.right[1], C.right[2]), xn)),
+                           vscale(V(C.up[0], C.up[1], C.up[2]), yn));
+        ps.o = V(C.eye[0], C.eye[1], C.eye[2]);
+        ps.d = vnorm(nd);
+        ps.n = V(0.0f, 0.0f, 0.0f);
+        ps.col[0] = ps.col[1] = ps.col[2] = ps.col[3] = 0.0f;
+        ps.T = V(1.0f, 1.0f, 1.0f);
+        ps.L = V(0.0f, 0.0f, 0.0f);
+        ps.cur = ps.prev = ps.depth = 0u;
+        ps.rng = 0u;
+        ps.last_prim = kPrimNone;
+        ps.path_segs = 0u;
+        ps.specular = true;
+        cnt.paths++;
+        // the distance from the eye: the segments' t in order, plus one RAY_OFFSET per continuation
+        float dist = 0.0f;
+        uint32_t prim = kPrimNone;  // of the visible hit; kPrimNone = none (a hit never encodes to it)
+        const uint32_t ai = R.compact ? item : y * R.W + x;
+        while (begin_segment(ps)) {  // [C15] bounds the pass-through chain
+            cnt.segs++;
+            const TraceRay tr = trace_ray_of(S, ps);
+            Esvo E;
+            esvo_begin(S, tr, E, stk);
+            prim = kPrimNone;
+            PrimHit h;
+            int rs;
+            do {
+                rs = esvo_step<kPrims>(S, tr, E, stk, cnt, prim, h);
+            } while (rs == kStepContinue);
+            cnt.steps += E.iter;
+            if (rs != kStepHit) {  // a miss after pass-through hits is a miss
+                prim = kPrimNone;
+                break;
+            }
+            commit_hit(S, ps, prim, h, cnt);
+            dist += h.t;
+            if (ps.cur != 0u && ps.col[3] > 0.0f) break;
+            prim = kPrimNone;  // passed through; ending on the segment cap is a miss too
+            ps.o = vadd(ps.o, vscale(ps.d, RAY_OFFSET));
+            dist += RAY_OFFSET;
+        }
+        const bool visible = prim != kPrimNone;
+        // octpt_intersect's encoding: block-value scenes (C23) report the block id or kQuadKey | quad
+        const uint32_t hit_prim = (kPrims != kPrimsBlocks || !visible) ? prim
+                                  : (prim & kPrimCuboidBit)            ? kQuadKey | (prim & kPrimIndexMask)
+                                                                       : prim & kPrimIndexMask;
+        if (out.albedo)
+            out.albedo[ai] = visible ? make_float4(ps.col[0], ps.col[1], ps.col[2], ps.col[3])
+                                     : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (out.normal)
+            out.normal[ai] = visible ? make_float4(ps.n.x, ps.n.y, ps.n.z, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (out.depth) out.depth[ai] = visible ? dist : __int_as_float(0x7f800000);
+        if (out.prim) out.prim[ai] = hit_prim;
+        if (out.material) out.material[ai] = visible ? ps.cur : 0u;
+    }
+    cnt.ib = 0u;  // issued bytes are extend's only
+    flush_counters(cnt, stats);
+}
+
+// ===========================================================================
+// Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010).  The arithmetic below is the
+// contract's, operation for operation (f32, no contraction, expf), so that a host restatement is comparable.
+// ===========================================================================
+constexpr uint32_t kDnX = 32, kDnY = 8;  // a 256-thread block filters 32 x 8 pixels (rows of 512 B of float4)
+constexpr float kDnAlbedoFloor = 1e-3f;
+
+// the working signal: color.rgb / max(albedo.rgb, 1e-3) when demodulating (albedo != NULL), the colour itself
+// otherwise and on miss pixels (which pass through every iteration untouched); alpha kept
+__global__ __launch_bounds__(256) void denoise_prep_kernel(uint32_t n, const float4 *__restrict__ color,
+                                                           const float4 *__restrict__ albedo,
+                                                           const float *__restrict__ depth, float4 *__restrict__ sig) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float4 c = color[i];
+    if (albedo && depth[i] != __builtin_inff()) {
+        const float4 a = albedo[i];
+        c.x = c.x / fmaxf(a.x, kDnAlbedoFloor);
+        c.y = c.y / fmaxf(a.y, kDnAlbedoFloor);
+        c.z = c.z / fmaxf(a.z, kDnAlbedoFloor);
+    }
+    sig[i] = c;
+}
+
+// One iteration: src -> dst with taps `1 << iter` apart, every tap a global load (float4 signal and normal, one
+// dword of depth).  kLast: dst is the caller's frame, the albedo (when demodulating) is multiplied back.
+// The kernel is bound by its arithmetic -- three expf and four IEEE divisions per tap -- not by its loads:
+// staging the tile and halo of spacings 1 and 2 in LDS measured the same (tools/rejected/denoise_lds_halo.patch).
+template <bool kLast>
+__global__ __launch_bounds__(256) void atrous_kernel(DevDenoise D, uint32_t iter, const float4 *__restrict__ src,
+                                                     float4 *__restrict__ dst) {
+    const int step = 1 << iter;
+    const int x = (int)(blockIdx.x * kDnX + threadIdx.x % kDnX), y = (int)(blockIdx.y * kDnY + threadIdx.x / kDnX);
+    const int W = (int)D.W, H = (int)D.H;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * D.W + (size_t)x;
+    const float4 sp = src[p];
+    const float zp = D.depth[p];
+    if (zp == __builtin_inff()) {  // a miss pixel: copied through (its signal is the input colour, prep)
+        dst[p] = sp;
+        return;
+    }
+    const float4 np = D.normal[p];
+    const float sc = D.sigma_color * __uint_as_float((127u - iter) << 23);  // sigma_color * 2^-iter
+    const float sc2 = sc * sc;
+    const float kH[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, ws = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {  // row-major tap order
+            const int qx = x + dx * step, qy = y + dy * step;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const size_t q = (size_t)qy * D.W + (size_t)qx;
+            const float zq = D.depth[q];
+            if (zq == __builtin_inff()) continue;
+            const float4 sq = src[q];
+            float w = kH[dx + 2] * kH[dy + 2];
+            if (dx != 0 || dy != 0) {  // the centre tap's three edge weights are 1
+                const float4 nq = D.normal[q];
+                const float cx = sp.x - sq.x, cy = sp.y - sq.y, cz = sp.z - sq.z;
+                const float wc = expf(-(((cx * cx + cy * cy) + cz * cz) / sc2));
+                const float nx = np.x - nq.x, ny = np.y - nq.y, nz = np.z - nq.z;
+                const float wn = expf(-(((nx * nx + ny * ny) + nz * nz) / D.sn2));
+                const float dz = (zp - zq) / zp;
+                const float wz = expf(-((dz * dz) / D.sz2));
+                w = ((w * wc) * wn) * wz;
+            }
+            sx = sx + w * sq.x;
+            sy = sy + w * sq.y;
+            sz = sz + w * sq.z;
+            ws = ws + w;
+        }
+    }
+    float4 o = make_float4(sx / ws, sy / ws, sz / ws, sp.w);
+    if (kLast && D.albedo) {
+        const float4 a = D.albedo[p];
+        o.x = o.x * fmaxf(a.x, kDnAlbedoFloor);
+        o.y = o.y * fmaxf(a.y, kDnAlbedoFloor);
+        o.z = o.z * fmaxf(a.z, kDnAlbedoFloor);
+    }
+    dst[p] = o;
+}
+
 }  // namespace
 
 // ESVO stack levels 1..depth-1 (level 0 is never used, see esvo_step)
@@ -2895,6 +3069,35 @@ hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRende
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args,
                                          render_lds_bytes(S.depth), stream);
     if (e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_gbuffer(const DevScene &S, const DevCamera &C, const DevRender &R, const DevAov &out,
+                          unsigned long long *stats, hipStream_t stream) {
+    const uint32_t grid = (R.total_items + kBlock - 1u) / kBlock;
+    // the primitive kinds of the scene pick the instance, as for preview_kernel
+    const void *fn = S.has_blocks   ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBlocks>)
+                     : S.has_models ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsModels>)
+                     : S.has_cuboids ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBoxes>)
+                                     : reinterpret_cast<const void *>(gbuffer_kernel<kPrimsSpheres>);
+    void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
+                    const_cast<DevAov *>(&out), &stats};
+    const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, render_lds_bytes(S.depth), stream);
+    if (e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_prep(uint32_t W, uint32_t H, const float4 *color, const float4 *albedo, const float *depth,
+                               float4 *sig, hipStream_t stream) {
+    const uint32_t n = W * H;
+    hipLaunchKernelGGL(denoise_prep_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, n, color, albedo, depth, sig);
+    return hipGetLastError();
+}
+
+hipError_t launch_atrous(const DevDenoise &D, uint32_t iter, bool last, const float4 *src, float4 *dst,
+                         hipStream_t stream) {
+    const dim3 grid((D.W + kDnX - 1u) / kDnX, (D.H + kDnY - 1u) / kDnY);
+    hipLaunchKernelGGL(last ? atrous_kernel<true> : atrous_kernel<false>, grid, dim3(256), 0, stream, D, iter, src, dst);
     return hipGetLastError();
 }
 

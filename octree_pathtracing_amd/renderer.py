@@ -293,6 +293,73 @@ class HipRenderer:
         self._check(self._lib.octpt_intersect(self._ctx, P(rays), P(lp), P(ln), n, P(t), P(prim), P(nrm), P(steps)))
         return t, prim, nrm, steps
 
+    # ------------------------------------------------------------ guide buffers and denoise (C24, C25)
+    def camera_rays(self, W: int, H: int) -> np.ndarray:
+        """octpt_camera_rays of the current camera: [H, W, 6] (origin, unit direction), the rays the device
+        traces for the pixel centres, bit for bit."""
+        return camera_rays(self._camera, W, H)
+
+    def render_aov(self, settings: RenderSettings, which=_lib.AOV_NAMES, shard=(0, 1), compact: bool = False,
+                   out: dict | None = None) -> dict:
+        """First-hit guide buffers (octpt_render_aov) -> {name: array} for the names in `which`: albedo and
+        normal [.., 4] f32, depth f32, prim and material u32; shaped [H, W] for a full frame, or flat over the
+        shard's tile-major pixels with compact.  shard = (index, count).  `out` supplies the arrays to fill
+        (a partial shard of a full frame leaves the other pixels as they are)."""
+        W, H = settings.width, settings.height
+        n = shard_pixels(W, H, *shard) if compact else W * H
+        shape = (n,) if compact else (H, W)
+        res, b = {}, _lib.AovBuffers()
+        for name in which:
+            if name not in _lib.AOV_NAMES:
+                raise ValueError(f"unknown guide buffer {name!r}; known: {_lib.AOV_NAMES}")
+            dt, tail = (np.float32, (4,)) if name in ("albedo", "normal") else \
+                (np.float32, ()) if name == "depth" else (np.uint32, ())
+            a = out[name] if out is not None else np.zeros(shape + tail, dt)
+            if a.dtype != dt or a.size != n * (4 if tail else 1) or not a.flags.c_contiguous:
+                raise ValueError(f"{name}: expected a contiguous {np.dtype(dt).name} array of {shape + tail}")
+            res[name] = a
+            setattr(b, name, a.ctypes.data)
+        p = self.params(W, H, 0, 0, shard_index=shard[0], shard_count=shard[1], compact=compact)
+        self._check(self._lib.octpt_render_aov(self._ctx, C.byref(p), C.byref(b)))
+        return res
+
+    def render_aov_device(self, params: "_lib.RenderParams", buffers: dict, stream: int | None = None) -> None:
+        """Enqueue the guide-buffer pass into device buffers: {name: raw device pointer} (e.g. torch
+        tensor.data_ptr()) for the wanted names of _lib.AOV_NAMES."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in buffers.items() if v})
+        self._check(self._lib.octpt_render_aov_device(self._ctx, C.byref(params), C.byref(b),
+                                                      C.c_void_p(stream) if stream else None))
+
+    def denoise(self, color: np.ndarray, aov: dict, iterations: int = 5, sigma_color: float = 0.6,
+                sigma_normal: float = 0.3, sigma_depth: float = 0.1, demodulate: bool = True) -> np.ndarray:
+        """Edge-avoiding a-trous filter (octpt_denoise) of a [H, W, 4] frame guided by render_aov's normal and
+        depth (and albedo with demodulate); returns the filtered frame."""
+        color = np.ascontiguousarray(color, np.float32)
+        H, W = color.shape[:2]
+        b = _lib.AovBuffers()
+        keep = []
+        for name in ("normal", "depth") + (("albedo",) if demodulate else ()):
+            if aov.get(name) is None:
+                continue  # the library reports the missing guide
+            a = np.ascontiguousarray(aov[name], np.float32)
+            if a.size != W * H * (1 if name == "depth" else 4):
+                raise ValueError(f"{name} guide does not match the {W} x {H} frame")
+            keep.append(a)
+            setattr(b, name, a.ctypes.data)
+        p = _lib.DenoiseParams(W, H, iterations, sigma_color, sigma_normal, sigma_depth,
+                               _lib.DENOISE_DEMODULATE if demodulate else 0)
+        out = np.empty_like(color)
+        self._check(self._lib.octpt_denoise(self._ctx, C.byref(p), color.ctypes.data_as(C.c_void_p), C.byref(b),
+                                            out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoise_device(self, params: "_lib.DenoiseParams", d_color: int, guides: dict, d_out: int,
+                       stream: int | None = None) -> None:
+        """Enqueue octpt_denoise_device on raw device pointers (d_out may equal d_color)."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in guides.items() if v})
+        self._check(self._lib.octpt_denoise_device(self._ctx, C.byref(params), C.c_void_p(d_color), C.byref(b),
+                                                   C.c_void_p(d_out), C.c_void_p(stream) if stream else None))
+
     def stats(self) -> dict:
         s = _lib.Stats()
         self._check(self._lib.octpt_get_stats(self._ctx, C.byref(s)))
@@ -317,6 +384,17 @@ def branch_pass_end(spp_start: int, spp_count: int, scene_branch_count: int) -> 
     while spp < spp_start + spp_count:
         spp += current_branch_count(spp, scene_branch_count)
     return spp
+
+
+def camera_rays(camera: Camera, W: int, H: int) -> np.ndarray:
+    """octpt_camera_rays: Camera::get_ray at the pixel centres, [H, W, 6] f32 (host-only, no context)."""
+    c = _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction), (C.c_float * 3)(*camera.up),
+                    camera.fov, 0.0, 0.0)
+    rays = np.zeros((H, W, 6), np.float32)
+    st = _lib.load().octpt_camera_rays(C.byref(c), W, H, rays.ctypes.data_as(C.c_void_p))
+    if st != 0:
+        raise _lib.OctptError(st, "octpt_camera_rays")
+    return rays
 
 
 def shard_pixels(W: int, H: int, shard_index: int, shard_count: int) -> int:
