@@ -466,6 +466,26 @@ octpt_status octpt_build_octree_device_ex(octpt_ctx *ctx, const octpt_sphere *sp
  * away.  Two cells at one position, or a block id >= 2^27, are INVALID_ARG. */
 octpt_status octpt_build_block_octree(const uint32_t *cells, uint32_t cell_count, uint32_t depth, uint32_t flags,
                                       octpt_octree **out);
+/* The block-value builder on the context's device: one thread per cell emits (Morton code,
+ * block), a radix sort on the code, then the octants, the merge passes of OCTPT_BUILD_COMPACT and the
+ * pre-order numbering as octpt_build_octree_device makes them.  The result equals octpt_build_block_octree's
+ * array for array, and the same cells are INVALID_ARG.  At most 2^31 cells (else OOM).
+ * OCTPT_BUILD_CELLS_ON_DEVICE (these two entries only; octpt_build_block_octree refuses it): `cells` is a
+ * device pointer on the context's device and is read where it is, with no upload.  The cells must be complete
+ * before the call: the library reads them on a stream of its own and does not synchronise with the stream
+ * that wrote them.  UNSUPPORTED on a multi-device context (the cells live on one device). */
+#define OCTPT_BUILD_CELLS_ON_DEVICE 0x2u
+octpt_status octpt_build_block_octree_device(octpt_ctx *ctx, const uint32_t *cells, uint32_t cell_count,
+                                             uint32_t depth, uint32_t flags, octpt_octree **out);
+/* set_scene for a block-value scene (C23) with the octree built on the device and kept there: the block
+ * counterpart of octpt_scene_build_device.  `scene` carries the block table (blocks must be set), materials,
+ * textures, models and the build depth, and no octree and no primitives; the cells are voxelised by the
+ * device block builder and its octants packed into the device node slots in place.  The resulting device
+ * scene is the one octpt_scene_upload makes from octpt_build_block_octree's octree.  Besides the builder's
+ * errors, a cell whose block id is >= block_count is INVALID_ARG.  flags: OCTPT_BUILD_COMPACT,
+ * OCTPT_BUILD_CELLS_ON_DEVICE (as above).  On a multi-device context every entry builds its own replica. */
+octpt_status octpt_scene_build_blocks_device(octpt_ctx *ctx, const octpt_scene_desc *scene, const uint32_t *cells,
+                                             uint32_t cell_count, uint32_t flags);
 octpt_status octpt_octree_get_view(const octpt_octree *tree, octpt_octree_view *view);
 void octpt_octree_free(octpt_octree *tree);
 

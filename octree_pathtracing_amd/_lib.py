@@ -31,6 +31,7 @@ RENDER_MEGAKERNEL = 0x2
 RENDER_KERNEL_TIMING = 0x4
 RENDER_PREVIEW = 0x8
 BUILD_COMPACT = 0x1  # OCTPT_BUILD_COMPACT
+BUILD_CELLS_ON_DEVICE = 0x2  # OCTPT_BUILD_CELLS_ON_DEVICE (the device block builds)
 PRIM_NONE = 0xFFFFFFFF
 PRIM_CUBOID_BIT = 0x80000000
 
@@ -247,6 +248,8 @@ SIGNATURES = {
     "octpt_build_octree_ex": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "octpt_build_octree_device_ex": (_i32, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "octpt_build_block_octree": (_i32, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "octpt_build_block_octree_device": (_i32, [_vp, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "octpt_scene_build_blocks_device": (_i32, [_vp, C.POINTER(SceneDesc), _vp, _u32, _u32]),
     "octpt_scene_from_reference": (_i32, [C.POINTER(ReferenceScene), _vp, _vp, _vp, C.POINTER(SceneDesc)]),
     "octpt_octree_get_view": (_i32, [_vp, C.POINTER(OctreeView)]),
     "octpt_octree_free": (None, [_vp]),

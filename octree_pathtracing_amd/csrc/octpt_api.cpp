@@ -337,7 +337,8 @@ DevQuad make_dev_quad(const octpt_quad &x) {
 octpt_status validate_tables(octpt_ctx *ctx, const octpt_scene_desc *d);
 
 // the checks that precede the octree's: version, depth, non-empty tables, primitive pointers.
-// with_octree = false (octpt_scene_build_device): the octree fields must be NULL / 0
+// with_octree = false (octpt_scene_build_device, octpt_scene_build_blocks_device): the octree fields must be
+// NULL / 0; which of the two a block table belongs to is the entries' own check
 octpt_status validate_head(octpt_ctx *ctx, const octpt_scene_desc *d, bool with_octree) {
     if (!d) return fail(ctx, OCTPT_ERR_INVALID_ARG, "scene is NULL");
     if (d->abi_version != OCTPT_ABI_VERSION) return fail(ctx, OCTPT_ERR_INVALID_ARG, "scene abi_version mismatch");
@@ -359,7 +360,6 @@ octpt_status validate_head(octpt_ctx *ctx, const octpt_scene_desc *d, bool with_
     if (d->sphere_count && !d->spheres) return fail(ctx, OCTPT_ERR_INVALID_ARG, "spheres is NULL");
     if (d->cuboid_count && !d->cuboids) return fail(ctx, OCTPT_ERR_INVALID_ARG, "cuboids is NULL");
     if (d->blocks) {  // block-value leaves (C23): the payloads are block ids, there are no primitives
-        if (!with_octree) return fail(ctx, OCTPT_ERR_INVALID_ARG, "a block-value scene is uploaded with its octree");
         if (d->block_count == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "block table is empty");
         if (d->block_count > kPrimIndexMask + 1u) return fail(ctx, OCTPT_ERR_UNSUPPORTED, "more than 2^27 blocks");
         if (d->leaf_first || d->leaf_count || d->leaf_table_size || d->leaf_prims || d->leaf_prim_count ||
@@ -1401,6 +1401,27 @@ uint64_t pair_bound(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid
     return bound;
 }
 
+// what build_block_octree_gpu's error word says (kCellErr*): the cells octpt_build_block_octree refuses,
+// and for a scene a block id beyond its block table
+octpt_status cell_error(octpt_ctx *ctx, uint32_t errors) {
+    if (errors & kCellErrRange) return fail(ctx, OCTPT_ERR_INVALID_ARG, "a cell coordinate is >= 2^depth");
+    if (errors & kCellErrBlockId) return fail(ctx, OCTPT_ERR_INVALID_ARG, "a cell's block id is >= 2^27");
+    if (errors & kCellErrBlockTable)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "a cell's block id is out of range of the block table");
+    return fail(ctx, OCTPT_ERR_INVALID_ARG, "two cells at one position");
+}
+
+// the argument checks the two device block builds share (after the NULL-context check and join_inflight)
+octpt_status check_block_build_args(octpt_ctx *ctx, const uint32_t *cells, uint32_t cell_count, uint32_t flags) {
+    if (flags & ~(OCTPT_BUILD_COMPACT | OCTPT_BUILD_CELLS_ON_DEVICE))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "unknown build flags");
+    if (cell_count && !cells) return fail(ctx, OCTPT_ERR_INVALID_ARG, "cells is NULL");
+    if (cell_count > kMaxBuildPairs) return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 cells");
+    if ((flags & OCTPT_BUILD_CELLS_ON_DEVICE) && is_multi(ctx))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "device cells live on one device: not on a multi-device context");
+    return OCTPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1731,6 +1752,89 @@ octpt_status octpt_scene_build_device(octpt_ctx *ctx, const octpt_scene_desc *d,
     } catch (...) {
         free_scene(ctx);
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device scene build");
+    }
+}
+
+octpt_status octpt_scene_build_blocks_device(octpt_ctx *ctx, const octpt_scene_desc *d, const uint32_t *cells,
+                                             uint32_t cell_count, uint32_t flags) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    join_inflight(ctx);
+    octpt_status st = check_block_build_args(ctx, cells, cell_count, flags);
+    if (st != OCTPT_OK) return st;
+    try {
+        if (is_multi(ctx)) {  // every device entry builds its own replica
+            ctx->has_scene = false;
+            st = for_each_sub(ctx, [&](size_t i) {
+                return octpt_scene_build_blocks_device(ctx->sub[i], d, cells, cell_count, flags);
+            });
+            ctx->has_scene = st == OCTPT_OK;
+            return st;
+        }
+        st = validate_head(ctx, d, false);
+        if (st != OCTPT_OK) return st;
+        if (!d->blocks)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "the block build needs the scene's block table (blocks is NULL)");
+        st = validate_tables(ctx, d);
+        if (st != OCTPT_OK) return st;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        free_scene(ctx);
+        // the GPU block builder (§4) with its octants left in the build scratch
+        BuiltOctree unused;
+        DeviceOctree t;
+        uint32_t errors = 0u;
+        float ms = 0.0f;
+        const hipError_t e = build_block_octree_gpu(ctx->stream, ctx->build_scratch, cells, cell_count,
+                                                    (flags & OCTPT_BUILD_CELLS_ON_DEVICE) != 0, d->depth,
+                                                    (flags & OCTPT_BUILD_COMPACT) != 0, d->block_count, unused, errors,
+                                                    &ms, &t);
+        if (e != hipSuccess) return hip_fail(ctx, e, "block octree build");
+        if (errors) return cell_error(ctx, errors);
+        ctx->build_ms = ms;
+        if ((uint64_t)t.n_octants * 8u >= 0xFFFFFFF0ull)  // the u32 slot scan cannot wrap
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "octree too large for the device build (>= 2^29 octants)");
+        uint32_t *d_base = nullptr, n_slots = 0;
+        HIP_TRY(ctx, slot_bases_gpu(ctx->stream, ctx->build_scratch, t, &d_base, n_slots));
+        const std::vector<uint32_t> bflags = block_slot_flags(d);
+        DevScene S{};
+        uint2 *d_child;
+        HIP_TRY(ctx, upload<uint2>(ctx, nullptr, (size_t)n_slots + 8, &d_child));  // zeroed: + 8 tail slots
+        HIP_TRY(ctx, fill_block_scene_gpu(ctx->stream, ctx->build_scratch, t, d_base, bflags.data(), d->block_count,
+                                          d_child));
+        uint16_t root_mask = 0;  // the root is octant 0 (pre-order), base 0
+        HIP_TRY(ctx, hipMemcpy(&root_mask, &t.octants[0].child_mask, sizeof root_mask, hipMemcpyDeviceToHost));
+        // the empty primitive tables a block-value scene has after octpt_scene_upload (one zeroed element each)
+        uint32_t *d_prims, *d_sph_mat, *d_cmat;
+        float4 *d_sph, *d_cmin;
+        float2 *d_cmax;
+        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_prims));
+        HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_sph));
+        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_sph_mat));
+        HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_cmin));
+        HIP_TRY(ctx, upload<float2>(ctx, nullptr, 0, &d_cmax));
+        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_cmat));
+        S.node_child = d_child;
+        S.leaf_prims = d_prims;
+        S.spheres = d_sph;
+        S.sphere_mat = d_sph_mat;
+        S.cub_a = d_cmin;
+        S.cub_b = d_cmax;
+        S.cub_mat = d_cmat;
+        S.root = 0u;
+        S.root_mask = root_mask;
+        S.n_octants = t.n_octants;
+        st = upload_tables(ctx, d, false, S);
+        if (st != OCTPT_OK) return st;
+        ctx->S = S;
+        ctx->has_scene = true;
+        ++ctx->scene_gen;
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        free_scene(ctx);
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
+    } catch (...) {
+        free_scene(ctx);
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device block scene build");
     }
 }
 
@@ -2603,6 +2707,35 @@ octpt_status octpt_build_block_octree(const uint32_t *cells, uint32_t n, uint32_
         return OCTPT_ERR_OOM;
     } catch (...) {
         return OCTPT_ERR_INTERNAL;
+    }
+}
+
+octpt_status octpt_build_block_octree_device(octpt_ctx *ctx, const uint32_t *cells, uint32_t n, uint32_t depth,
+                                             uint32_t flags, octpt_octree **out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    join_inflight(ctx);
+    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "out NULL");
+    *out = nullptr;
+    if (depth < 1 || depth > kMaxDepth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "depth must be in [1, 21]");
+    const octpt_status st = check_block_build_args(ctx, cells, n, flags);
+    if (st != OCTPT_OK) return st;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::unique_ptr<octpt_octree> t(new octpt_octree());
+        uint32_t errors = 0u;
+        float ms = 0.0f;
+        const hipError_t e = build_block_octree_gpu(ctx->stream, ctx->build_scratch, cells, n,
+                                                    (flags & OCTPT_BUILD_CELLS_ON_DEVICE) != 0, depth,
+                                                    (flags & OCTPT_BUILD_COMPACT) != 0, 0u, *t, errors, &ms);
+        if (e != hipSuccess) return hip_fail(ctx, e, "block octree build");
+        if (errors) return cell_error(ctx, errors);
+        ctx->build_ms = ms;
+        *out = t.release();
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "block octree build: host out of memory");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in block octree build");
     }
 }
 

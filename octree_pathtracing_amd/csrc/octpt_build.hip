@@ -17,6 +17,10 @@
 //            numbers them consecutively, so ids = exclusive scan of that count.  Each new octant
 //            links itself into its parent (found by binary search over the leaf codes when the
 //            parent was opened by an earlier leaf), each leaf into its level depth-1 octant.
+//
+// Block-value octrees (octpt_build_block_octree, C23) take the same path from the sort on
+// (build_block_octree_gpu): one thread per cell emits (Morton code, block), every cell is its own
+// leaf (no head flags, no leaf tables), and a leaf's payload is its block value.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -131,6 +135,32 @@ __global__ __launch_bounds__(kBuildBlock) void emit_pairs_kernel(const octpt_sph
             }
 }
 
+// block-value cells (C23): one thread per cell (x, y, z, block) writes (Morton code, block) and ORs what the
+// host builder refuses into *err (kCellErr*; a coordinate out of range is masked by morton(), so nothing
+// is written out of bounds before the host reads the word).  aligned: `cells` is 16-byte aligned
+__global__ __launch_bounds__(kBuildBlock) void emit_cells_kernel(const uint32_t *__restrict__ cells, uint32_t n,
+                                                                 uint32_t depth, uint32_t block_count, bool aligned,
+                                                                 uint64_t *__restrict__ codes,
+                                                                 uint32_t *__restrict__ blks,
+                                                                 uint32_t *__restrict__ err) {
+    const uint32_t k = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (k >= n) return;
+    uint4 c;
+    if (aligned) {
+        c = reinterpret_cast<const uint4 *>(cells)[k];
+    } else {
+        const uint32_t *p = cells + 4u * (size_t)k;
+        c = make_uint4(p[0], p[1], p[2], p[3]);
+    }
+    uint32_t e = 0u;
+    if ((c.x | c.y | c.z) >> depth) e |= kCellErrRange;
+    if (c.w > kPrimIndexMask) e |= kCellErrBlockId;
+    if (block_count && c.w >= block_count) e |= kCellErrBlockTable;
+    if (e) atomicOr(err, e);
+    codes[k] = morton(c.x, c.y, c.z);
+    blks[k] = c.w;
+}
+
 __global__ __launch_bounds__(kBuildBlock) void leaf_heads_kernel(const uint64_t *__restrict__ codes, uint32_t n,
                                                                  uint32_t *__restrict__ head) {
     const uint32_t k = blockIdx.x * kBuildBlock + threadIdx.x;
@@ -151,19 +181,28 @@ __global__ __launch_bounds__(kBuildBlock) void leaf_tables_kernel(const uint64_t
     leaf_code[l] = codes[k];
 }
 
-// leaf_count and the number of octants leaf j opens (pre-order ids follow by an exclusive scan)
+// leaf_count and the number of octants leaf j opens (pre-order ids follow by an exclusive scan).
+// kCells (block-value build): every cell is a leaf, leaf_code = the sorted cell codes and there are no
+// leaf tables; two equal neighbours are two blocks in one cell (kCellErrDuplicate, opens nothing)
+template <bool kCells>
 __global__ __launch_bounds__(kBuildBlock) void leaf_count_kernel(const uint32_t *__restrict__ leaf_first,
                                                                  const uint64_t *__restrict__ leaf_code, uint32_t L,
                                                                  uint32_t n_pairs, uint32_t depth,
                                                                  uint32_t *__restrict__ leaf_count,
-                                                                 uint32_t *__restrict__ opens) {
+                                                                 uint32_t *__restrict__ opens,
+                                                                 uint32_t *__restrict__ err) {
     const uint32_t j = blockIdx.x * kBuildBlock + threadIdx.x;
     if (j >= L) return;
-    leaf_count[j] = (j + 1u < L ? leaf_first[j + 1u] : n_pairs) - leaf_first[j];
+    if (!kCells) leaf_count[j] = (j + 1u < L ? leaf_first[j + 1u] : n_pairs) - leaf_first[j];
     if (j == 0u) {
         opens[j] = depth;
     } else {
         const uint64_t d = leaf_code[j] ^ leaf_code[j - 1u];  // != 0: codes are unique
+        if (kCells && d == 0ull) {
+            atomicOr(err, kCellErrDuplicate);
+            opens[j] = 0u;
+            return;
+        }
         opens[j] = (63u - (uint32_t)__clzll((long long)d)) / 3u;
     }
 }
@@ -183,10 +222,13 @@ __device__ inline uint32_t octant_at(const uint64_t *__restrict__ leaf_code, con
     return base[lo] + (level - (depth - opens[lo]));
 }
 
+// kBlockValues: leaf j's payload is value[j] (its block), else its leaf table index j
+template <bool kBlockValues>
 __global__ __launch_bounds__(kBuildBlock) void link_kernel(const uint64_t *__restrict__ leaf_code,
                                                            const uint32_t *__restrict__ base,
                                                            const uint32_t *__restrict__ opens, uint32_t L,
-                                                           uint32_t depth, uint32_t *__restrict__ child,
+                                                           uint32_t depth, const uint32_t *__restrict__ value,
+                                                           uint32_t *__restrict__ child,
                                                            uint32_t *__restrict__ mask, uint32_t *__restrict__ up,
                                                            uint8_t *__restrict__ lvl) {
     const uint32_t j = blockIdx.x * kBuildBlock + threadIdx.x;
@@ -207,7 +249,7 @@ __global__ __launch_bounds__(kBuildBlock) void link_kernel(const uint64_t *__res
     }
     const uint32_t p = nj ? base[j] + nj - 1u : octant_at(leaf_code, base, opens, L, depth, depth - 1u, code);
     const uint32_t c = (uint32_t)code & 7u;
-    child[8u * p + c] = j;  // leaf payload = leaf table index
+    child[8u * p + c] = kBlockValues ? value[j] : j;  // leaf payload = block value / leaf table index
     atomicOr(&mask[p], (1u << c) | (1u << (c + 8u)));
 }
 
@@ -216,6 +258,9 @@ __global__ __launch_bounds__(kBuildBlock) void link_kernel(const uint64_t *__res
 // 0's payload (Octant::is_compactable, new_octree.rs:227-233; RegionOctreeBuilder::recursive_build
 // :679-690).  Parents are one level up, handled by the next launch; siblings touch distinct slots.
 // up[o] = the parent slot (8 * parent + child index), lvl[o] its level; the root (level 0) stays.
+// kBlockValues (C23): leaf payloads are block values and "the same" is value equality; the mask alone
+// says what a leaf is (block 0 is a value like any other, and the child array is zero-filled).
+template <bool kBlockValues>
 __global__ __launch_bounds__(kBuildBlock) void compact_level_kernel(const uint32_t *__restrict__ up,
                                                                     const uint8_t *__restrict__ lvl, uint32_t n_oct,
                                                                     uint32_t level, const uint32_t *__restrict__ leaf_first,
@@ -228,13 +273,18 @@ __global__ __launch_bounds__(kBuildBlock) void compact_level_kernel(const uint32
     if (o == 0u || o >= n_oct) return;  // octant 0 is the root
     if (lvl[o] != level || mask[o] != 0xFFFFu) return;
     const uint32_t c0 = child[8u * o];
-    const uint32_t f0 = leaf_first[c0], n0 = leaf_count[c0];
-    for (int k = 1; k < 8; ++k) {
-        const uint32_t ck = child[8u * o + k];
-        if (leaf_count[ck] != n0) return;
-        const uint32_t fk = leaf_first[ck];
-        for (uint32_t e = 0; e < n0; ++e)
-            if (prims[fk + e] != prims[f0 + e]) return;
+    if (kBlockValues) {
+        for (int k = 1; k < 8; ++k)
+            if (child[8u * o + k] != c0) return;
+    } else {
+        const uint32_t f0 = leaf_first[c0], n0 = leaf_count[c0];
+        for (int k = 1; k < 8; ++k) {
+            const uint32_t ck = child[8u * o + k];
+            if (leaf_count[ck] != n0) return;
+            const uint32_t fk = leaf_first[ck];
+            for (uint32_t e = 0; e < n0; ++e)
+                if (prims[fk + e] != prims[f0 + e]) return;
+        }
     }
     keep[o] = 0u;
     const uint32_t slot = up[o];
@@ -284,7 +334,7 @@ inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + kBuildBlock - 1) / k
 // slots of the context's grow-only scratch, taken in a fixed order per build
 struct ScratchCursor {
     BuildScratch &s;
-    int next = 0;  // the build takes at most slots 0..25 in a fixed order, slot_bases_gpu 27..29
+    int next = 0;  // a build takes at most slots 0..25 in a fixed order, slot_bases_gpu 27..29, the block flags 30
     template <class T>
     hipError_t get(T **ptr, size_t n) {
         const int k = next++;
@@ -321,6 +371,66 @@ void BuildScratch::release() {
         cap[k] = 0;
     }
 }
+
+namespace {
+
+// The octants of L Morton-sorted leaves (codes d_lcode; d_opens / d_base = the octants each leaf opens and
+// their exclusive scan, n_oct = its total): link, with `compact` one merge pass per level bottom-up and the
+// pre-order renumbering, and the packed octpt_octant array *d_oct; n_oct becomes the surviving count.
+// kBlockValues: leaf j's payload is d_value[j] and leaves merge by value (C23); else the payload is j and
+// leaves merge by primitive list (d_first / d_count / d_prims).
+template <bool kBlockValues>
+hipError_t octants_gpu(hipStream_t stream, ScratchCursor &pool, const uint64_t *d_lcode, const uint32_t *d_base,
+                       const uint32_t *d_opens, uint32_t L, uint32_t depth, bool compact, const uint32_t *d_value,
+                       const uint32_t *d_first, const uint32_t *d_count, const uint32_t *d_prims, uint32_t &n_oct,
+                       octpt_octant **d_oct_out) {
+    uint32_t *d_child, *d_mask, *d_up = nullptr, *d_keep = nullptr, *d_newid = nullptr;
+    uint8_t *d_lvl = nullptr;
+    octpt_octant *d_oct;
+    BTRY(pool.get(&d_child, (size_t)n_oct * 8));
+    BTRY(pool.get(&d_mask, n_oct));
+    BTRY(pool.get(&d_oct, n_oct));
+    if (compact) {
+        BTRY(pool.get(&d_up, n_oct));
+        BTRY(pool.get(&d_lvl, n_oct));
+        BTRY(pool.get(&d_keep, n_oct + 1));  // entry n_oct = 0: the exclusive scan's last input
+        BTRY(pool.get(&d_newid, n_oct + 1));
+    }
+    BTRY(hipMemsetAsync(d_child, 0, (size_t)n_oct * 8 * sizeof(uint32_t), stream));
+    BTRY(hipMemsetAsync(d_mask, 0, (size_t)n_oct * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(link_kernel<kBlockValues>, dim3(blocks(L)), dim3(kBuildBlock), 0, stream, d_lcode, d_base, d_opens,
+                       L, depth, d_value, d_child, d_mask, d_up, d_lvl);
+    BTRY(hipGetLastError());
+    if (compact) {
+        // keep = 1 per octant, then one pass per level, bottom-up
+        hipLaunchKernelGGL(fill_u32_kernel, dim3(blocks(n_oct + 1)), dim3(kBuildBlock), 0, stream, d_keep, n_oct + 1,
+                           n_oct);
+        BTRY(hipGetLastError());
+        for (uint32_t level = depth - 1; level >= 1; --level) {
+            hipLaunchKernelGGL(compact_level_kernel<kBlockValues>, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, d_up,
+                               d_lvl, n_oct, level, d_first, d_count, d_prims, d_child, d_mask, d_keep);
+            BTRY(hipGetLastError());
+        }
+        size_t id_bytes = 0;
+        BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, id_bytes, d_keep, d_newid, n_oct + 1, stream));
+        char *d_tmp3;
+        BTRY(pool.get(&d_tmp3, id_bytes));
+        BTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp3, id_bytes, d_keep, d_newid, n_oct + 1, stream));
+        hipLaunchKernelGGL(pack_compacted_kernel, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, d_child, d_mask,
+                           d_keep, d_newid, n_oct, d_oct);
+        BTRY(hipGetLastError());
+        BTRY(hipMemcpyAsync(&n_oct, d_newid + n_oct, sizeof n_oct, hipMemcpyDeviceToHost, stream));
+        BTRY(hipStreamSynchronize(stream));
+    } else {
+        hipLaunchKernelGGL(pack_octants_kernel, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, d_child, d_mask,
+                           n_oct, d_oct);
+        BTRY(hipGetLastError());
+    }
+    *d_oct_out = d_oct;
+    return hipSuccess;
+}
+
+}  // namespace
 
 hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const octpt_sphere *spheres, uint32_t ns,
                             const octpt_cuboid *cuboids, uint32_t nc, uint32_t depth, bool compact,
@@ -429,8 +539,8 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     hipLaunchKernelGGL(leaf_tables_kernel, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, d_code_s, d_head, d_incl, n,
                        d_first, d_lcode);
     BTRY(hipGetLastError());
-    hipLaunchKernelGGL(leaf_count_kernel, dim3(blocks(L)), dim3(kBuildBlock), 0, stream, d_first, d_lcode, L, n, depth,
-                       d_count, d_opens);
+    hipLaunchKernelGGL(leaf_count_kernel<false>, dim3(blocks(L)), dim3(kBuildBlock), 0, stream, d_first, d_lcode, L, n,
+                       depth, d_count, d_opens, (uint32_t *)nullptr);
     BTRY(hipGetLastError());
     size_t base_bytes = 0;
     BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, base_bytes, d_opens, d_base, L + 1, stream));
@@ -441,48 +551,9 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     uint32_t n_oct = 0;
     BTRY(hipMemcpyAsync(&n_oct, d_base + L, sizeof n_oct, hipMemcpyDeviceToHost, stream));
     BTRY(hipStreamSynchronize(stream));
-    uint32_t *d_child, *d_mask, *d_up = nullptr, *d_keep = nullptr, *d_newid = nullptr;
-    uint8_t *d_lvl = nullptr;
     octpt_octant *d_oct;
-    BTRY(pool.get(&d_child, (size_t)n_oct * 8));
-    BTRY(pool.get(&d_mask, n_oct));
-    BTRY(pool.get(&d_oct, n_oct));
-    if (compact) {
-        BTRY(pool.get(&d_up, n_oct));
-        BTRY(pool.get(&d_lvl, n_oct));
-        BTRY(pool.get(&d_keep, n_oct + 1));  // entry n_oct = 0: the exclusive scan's last input
-        BTRY(pool.get(&d_newid, n_oct + 1));
-    }
-    BTRY(hipMemsetAsync(d_child, 0, (size_t)n_oct * 8 * sizeof(uint32_t), stream));
-    BTRY(hipMemsetAsync(d_mask, 0, (size_t)n_oct * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(link_kernel, dim3(blocks(L)), dim3(kBuildBlock), 0, stream, d_lcode, d_base, d_opens, L, depth,
-                       d_child, d_mask, d_up, d_lvl);
-    BTRY(hipGetLastError());
-    if (compact) {
-        // keep = 1 per octant, then one pass per level, bottom-up
-        hipLaunchKernelGGL(fill_u32_kernel, dim3(blocks(n_oct + 1)), dim3(kBuildBlock), 0, stream, d_keep, n_oct + 1,
-                           n_oct);
-        BTRY(hipGetLastError());
-        for (uint32_t level = depth - 1; level >= 1; --level) {
-            hipLaunchKernelGGL(compact_level_kernel, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, d_up, d_lvl, n_oct,
-                               level, d_first, d_count, d_prim_s, d_child, d_mask, d_keep);
-            BTRY(hipGetLastError());
-        }
-        size_t id_bytes = 0;
-        BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, id_bytes, d_keep, d_newid, n_oct + 1, stream));
-        char *d_tmp3;
-        BTRY(pool.get(&d_tmp3, id_bytes));
-        BTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp3, id_bytes, d_keep, d_newid, n_oct + 1, stream));
-        hipLaunchKernelGGL(pack_compacted_kernel, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, d_child, d_mask,
-                           d_keep, d_newid, n_oct, d_oct);
-        BTRY(hipGetLastError());
-        BTRY(hipMemcpyAsync(&n_oct, d_newid + n_oct, sizeof n_oct, hipMemcpyDeviceToHost, stream));
-        BTRY(hipStreamSynchronize(stream));
-    } else {
-        hipLaunchKernelGGL(pack_octants_kernel, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, d_child, d_mask,
-                           n_oct, d_oct);
-        BTRY(hipGetLastError());
-    }
+    BTRY(octants_gpu<false>(stream, pool, d_lcode, d_base, d_opens, L, depth, compact, nullptr, d_first, d_count,
+                            d_prim_s, n_oct, &d_oct));
     BTRY(hipEventRecord(e1, stream));
     if (dev) {  // device-resident: the arrays stay in the scratch
         dev->octants = d_oct;
@@ -505,6 +576,106 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     BTRY(hipMemcpyAsync(out.leaf_first.data(), d_first, (size_t)L * 4, hipMemcpyDeviceToHost, stream));
     BTRY(hipMemcpyAsync(out.leaf_count.data(), d_count, (size_t)L * 4, hipMemcpyDeviceToHost, stream));
     BTRY(hipMemcpyAsync(out.leaf_prims.data(), d_prim_s, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    BTRY(hipStreamSynchronize(stream));
+    if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
+    return hipSuccess;
+}
+
+// The block-value builder (octpt_internal.h).  Scratch slots in a fixed order like build_octree_gpu's, at
+// most 0..17.  One readback (the error word with the octant count) precedes the octant arrays.
+hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, const uint32_t *cells, uint32_t n,
+                                  bool cells_on_device, uint32_t depth, bool compact, uint32_t block_count,
+                                  BuiltOctree &out, uint32_t &errors, float *ms, DeviceOctree *dev) {
+    errors = 0u;
+    ScratchCursor pool{scratch};
+    hipEvent_t e0, e1;
+    BTRY(hipEventCreate(&e0));
+    BTRY(hipEventCreate(&e1));
+    struct EvGuard {
+        hipEvent_t a, b;
+        ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    } evg{e0, e1};
+    uint32_t *d_cells, *d_err;
+    BTRY(pool.get(&d_cells, cells_on_device ? 0u : (size_t)n * 4));
+    BTRY(pool.get(&d_err, 2));  // the error word, and beside it the octant count (one readback)
+    const uint32_t *d_in = cells;
+    if (!cells_on_device) {
+        if (n) BTRY(hipMemcpyAsync(d_cells, cells, (size_t)n * 16, hipMemcpyHostToDevice, stream));
+        d_in = d_cells;
+    }
+    BTRY(hipEventRecord(e0, stream));
+    out.depth = depth;
+    out.root = 0u;
+    out.leaf_first.clear();
+    out.leaf_count.clear();
+    out.leaf_prims.clear();
+    if (dev) {
+        *dev = DeviceOctree{};
+        dev->depth = depth;
+    }
+    if (n == 0u) {  // empty world: a childless root, as the host builder emits
+        if (ms) *ms = 0.0f;
+        if (dev) {
+            octpt_octant *d_root;
+            BTRY(pool.get(&d_root, 1));
+            BTRY(hipMemsetAsync(d_root, 0, sizeof(octpt_octant), stream));
+            BTRY(hipStreamSynchronize(stream));
+            dev->octants = d_root;
+            dev->n_octants = 1u;
+            return hipSuccess;
+        }
+        out.octants.assign(1, octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
+        return hipSuccess;
+    }
+    uint64_t *d_code, *d_code_s;
+    uint32_t *d_blk, *d_blk_s, *d_opens, *d_base;
+    BTRY(pool.get(&d_code, n));
+    BTRY(pool.get(&d_code_s, n));
+    BTRY(pool.get(&d_blk, n));
+    BTRY(pool.get(&d_blk_s, n));
+    BTRY(pool.get(&d_opens, (size_t)n + 1));  // entry n = 0: the exclusive scan's last input
+    BTRY(pool.get(&d_base, (size_t)n + 1));
+    BTRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(emit_cells_kernel, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, d_in, n, depth, block_count,
+                       (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0u, d_code, d_blk, d_err);
+    BTRY(hipGetLastError());
+    size_t sort_bytes = 0, base_bytes = 0;
+    BTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
+                                            (int)(3u * depth), stream));
+    BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, base_bytes, d_opens, d_base, n + 1, stream));
+    char *d_tmp;
+    BTRY(pool.get(&d_tmp, std::max(sort_bytes, base_bytes)));
+    BTRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
+                                            (int)(3u * depth), stream));
+    // every cell is a leaf: the octants it opens, and equal neighbours (two blocks in one cell)
+    BTRY(hipMemsetAsync(d_opens + n, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(leaf_count_kernel<true>, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, (const uint32_t *)nullptr,
+                       d_code_s, n, n, depth, (uint32_t *)nullptr, d_opens, d_err);
+    BTRY(hipGetLastError());
+    BTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, base_bytes, d_opens, d_base, n + 1, stream));
+    BTRY(hipMemcpyAsync(d_err + 1, d_base + n, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    uint32_t head[2] = {0u, 0u};
+    BTRY(hipMemcpyAsync(head, d_err, sizeof head, hipMemcpyDeviceToHost, stream));
+    BTRY(hipStreamSynchronize(stream));
+    if (head[0]) {
+        errors = head[0];
+        return hipSuccess;
+    }
+    uint32_t n_oct = head[1];
+    octpt_octant *d_oct;
+    BTRY(octants_gpu<true>(stream, pool, d_code_s, d_base, d_opens, n, depth, compact, d_blk_s, nullptr, nullptr, nullptr,
+                           n_oct, &d_oct));
+    BTRY(hipEventRecord(e1, stream));
+    if (dev) {  // device-resident: the octants stay in the scratch
+        dev->octants = d_oct;
+        dev->n_octants = n_oct;
+        BTRY(hipStreamSynchronize(stream));
+        if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
+        return hipSuccess;
+    }
+    out.octants.resize(n_oct);
+    BTRY(hipMemcpyAsync(out.octants.data(), d_oct, (size_t)n_oct * sizeof(octpt_octant), hipMemcpyDeviceToHost,
+                        stream));
     BTRY(hipStreamSynchronize(stream));
     if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
     return hipSuccess;
@@ -555,6 +726,24 @@ __global__ __launch_bounds__(kBuildBlock) void slot_fill_kernel(const octpt_octa
             child[k] = make_uint2(first[c], count[c]);
         }
         ++k;
+    }
+}
+
+// the slots of a block-value octree (C23): octant child = (its base, its mask), leaf child = (block value,
+// the block's slot flags); a leaf value is < the block count (emit_cells_kernel's check)
+__global__ __launch_bounds__(kBuildBlock) void block_slot_fill_kernel(const octpt_octant *__restrict__ oct, uint32_t n,
+                                                                      const uint32_t *__restrict__ base,
+                                                                      const uint32_t *__restrict__ bflags,
+                                                                      uint2 *__restrict__ child) {
+    const uint32_t o = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (o >= n) return;
+    const octpt_octant v = oct[o];
+    const uint32_t m = v.child_mask;
+    uint32_t k = base[o];
+    for (int i = 0; i < 8; ++i) {
+        if (!((m >> i) & 1u)) continue;
+        const uint32_t c = v.children[i];
+        child[k++] = ((m >> (i + 8)) & 1u) ? make_uint2(c, bflags[c]) : make_uint2(base[c], oct[c].child_mask);
     }
 }
 
@@ -613,6 +802,18 @@ hipError_t fill_scene_gpu(hipStream_t stream, const DeviceOctree &t, const uint3
                            out.cub_mat);
         BTRY(hipGetLastError());
     }
+    return hipStreamSynchronize(stream);
+}
+
+hipError_t fill_block_scene_gpu(hipStream_t stream, BuildScratch &scratch, const DeviceOctree &t,
+                                const uint32_t *d_base, const uint32_t *bflags, uint32_t n_blocks, uint2 *node_child) {
+    ScratchCursor pool{scratch, 30};  // after slot_bases_gpu's slots (27..29)
+    uint32_t *d_bflags;
+    BTRY(pool.get(&d_bflags, n_blocks));
+    BTRY(hipMemcpyAsync(d_bflags, bflags, (size_t)n_blocks * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(block_slot_fill_kernel, dim3(blocks(t.n_octants)), dim3(kBuildBlock), 0, stream, t.octants,
+                       t.n_octants, d_base, d_bflags, node_child);
+    BTRY(hipGetLastError());
     return hipStreamSynchronize(stream);
 }
 

@@ -397,6 +397,20 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
                             uint64_t max_pairs, BuiltOctree &out, bool &too_many, float *ms,
                             DeviceOctree *dev = nullptr);
 
+// The block-value builder on the device (octpt_build_block_octree, C23): cells[4k .. 4k+3] = (x, y, z, block),
+// a host array uploaded once into the scratch, or with cells_on_device read where it is (on `stream`).
+// The result equals the host builder's array for array and is returned as build_octree_gpu returns its own
+// (no leaf tables: the leaf payloads are the block values).  `errors` receives the kCellErr* bits the cells
+// raised; when it is not 0 nothing is built.  block_count (the scene entry; 0 = not checked): a block id
+// >= block_count raises kCellErrBlockTable.
+constexpr uint32_t kCellErrRange = 1u;       // x, y or z >= 2^depth
+constexpr uint32_t kCellErrBlockId = 2u;     // block > kPrimIndexMask
+constexpr uint32_t kCellErrBlockTable = 4u;  // block >= block_count
+constexpr uint32_t kCellErrDuplicate = 8u;   // two cells at one position
+hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, const uint32_t *cells, uint32_t n,
+                                  bool cells_on_device, uint32_t depth, bool compact, uint32_t block_count,
+                                  BuiltOctree &out, uint32_t &errors, float *ms, DeviceOctree *dev = nullptr);
+
 // Device-resident scene packing (octpt_scene_build_device): the sparse child-slot bases of a
 // DeviceOctree (exclusive scan of the present-child counts; *d_base in the scratch, n_octants + 1
 // entries, the last = slot count), then the slots, the single-sphere leaf table and the primitive
@@ -415,5 +429,10 @@ struct ScenePrimTables {
 };
 hipError_t fill_scene_gpu(hipStream_t stream, const DeviceOctree &t, const uint32_t *d_base,
                           const ScenePrimTables &out);
+// The slots of a block-value octree (octpt_scene_build_blocks_device): octant child = (its base, its mask),
+// leaf child = (block, bflags[block]); bflags = the host's block_slot_flags, one word per block, uploaded
+// into the scratch.  node_child: n_slots + 8 (the tail zeroed by the caller).
+hipError_t fill_block_scene_gpu(hipStream_t stream, BuildScratch &scratch, const DeviceOctree &t,
+                                const uint32_t *d_base, const uint32_t *bflags, uint32_t n_blocks, uint2 *node_child);
 
 }  // namespace octpt

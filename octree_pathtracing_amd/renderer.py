@@ -178,9 +178,32 @@ class HipRenderer:
     def set_scene_built(self, scene: Scene, depth: int, compact: bool = False) -> None:
         """set_scene with the octree built on this GPU and kept there (octpt_scene_build_device): the
         device scene equals set_scene(scene) after scene.build_octree(depth, compact=compact), without
-        the host round trip.  scene.octree is left untouched."""
+        the host round trip.  scene.octree is left untouched.  A block-value scene (scene.blocks set) builds
+        from scene.cells with octpt_scene_build_blocks_device."""
+        if scene.blocks is not None:
+            cells = scene.cells_array()
+            self._set_scene_built_blocks(scene, depth, cells.ctypes.data if len(cells) else None, len(cells),
+                                         _lib.BUILD_COMPACT if compact else 0)
+            return
         desc, keep = scene.to_desc(octree=False, depth=depth)
         self._check(self._lib.octpt_scene_build_device(self._ctx, C.byref(desc), _lib.BUILD_COMPACT if compact else 0))
+        self._scene_keep = keep
+        self.reset_render()
+
+    def set_scene_built_cells(self, scene: Scene, depth: int, cells_ptr: int, cell_count: int,
+                              compact: bool = False) -> None:
+        """set_scene_built for a block-value scene whose cells are already on this GPU: cells_ptr is a device
+        pointer to cell_count rows of (x, y, z, block) uint32, e.g. a torch int32 tensor's data_ptr()
+        (OCTPT_BUILD_CELLS_ON_DEVICE).  The cells must be complete before the call (synchronise the stream
+        that wrote them): the library reads them on its own stream.  scene.cells is not read."""
+        if scene.blocks is None:
+            raise ValueError("set_scene_built_cells: a block-value scene (scene.blocks) is needed")
+        self._set_scene_built_blocks(scene, depth, int(cells_ptr), int(cell_count),
+                                     _lib.BUILD_CELLS_ON_DEVICE | (_lib.BUILD_COMPACT if compact else 0))
+
+    def _set_scene_built_blocks(self, scene: Scene, depth: int, cells_ptr, cell_count: int, flags: int) -> None:
+        desc, keep = scene.to_desc(octree=False, depth=depth)
+        self._check(self._lib.octpt_scene_build_blocks_device(self._ctx, C.byref(desc), cells_ptr, cell_count, flags))
         self._scene_keep = keep
         self.reset_render()
 

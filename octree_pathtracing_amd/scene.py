@@ -217,15 +217,20 @@ class Scene:
     cells: np.ndarray | None = None
 
     # ---------------------------------------------------------------- octree
-    def build_octree(self, depth: int, renderer=None, compact: bool = False) -> Octree:
+    def build_octree(self, depth: int, renderer=None, compact: bool = False, device_cells=None) -> Octree:
         """Voxelise the primitives with the product builder: octpt_build_octree (host), or with a
         HipRenderer given, octpt_build_octree_device on its GPU (the same arrays).  compact: merge
         eight sibling leaves holding the same primitive list, bottom-up (OCTPT_BUILD_COMPACT,
         Octant::is_compactable, new_octree.rs:227-233).  A block-value scene (C23) builds from its
-        cells with octpt_build_block_octree (compact: eight equal block values merge)."""
+        cells with octpt_build_block_octree (compact: eight equal block values merge), or with a
+        renderer given, octpt_build_block_octree_device; device_cells = (device pointer, cell count)
+        then reads the cells from that renderer's GPU (OCTPT_BUILD_CELLS_ON_DEVICE; they must be
+        complete, e.g. after torch.cuda.synchronize()) instead of self.cells."""
         lib = _lib.load()
+        if device_cells is not None and (self.blocks is None or renderer is None):
+            raise ValueError("device_cells: a block-value scene and a renderer are needed")
         if self.blocks is not None:
-            return self._build_block_octree(lib, depth, compact)
+            return self._build_block_octree(lib, depth, compact, renderer, device_cells)
         sph = self.sphere_structs()
         cub = self.cuboid_structs()
         handle = C.c_void_p()
@@ -256,12 +261,24 @@ class Scene:
             lib.octpt_octree_free(handle)
         return self.octree
 
-    def _build_block_octree(self, lib, depth: int, compact: bool) -> Octree:
-        cells = np.ascontiguousarray(self.cells, np.uint32).reshape(-1, 4)
+    def cells_array(self) -> np.ndarray:
+        """`cells` as the contiguous uint32 (n, 4) array the block builders take."""
+        return np.ascontiguousarray(self.cells, np.uint32).reshape(-1, 4)
+
+    def _build_block_octree(self, lib, depth: int, compact: bool, renderer=None, device_cells=None) -> Octree:
+        flags = _lib.BUILD_COMPACT if compact else 0
         handle = C.c_void_p()
-        _lib.check(lib, None, lib.octpt_build_block_octree(cells.ctypes.data_as(C.c_void_p) if len(cells) else None,
-                                                           len(cells), depth, _lib.BUILD_COMPACT if compact else 0,
-                                                           C.byref(handle)))
+        if device_cells is not None:
+            ptr, n = C.c_void_p(int(device_cells[0])), int(device_cells[1])
+            flags |= _lib.BUILD_CELLS_ON_DEVICE
+        else:
+            cells = self.cells_array()
+            ptr, n = (cells.ctypes.data_as(C.c_void_p) if len(cells) else None), len(cells)
+        if renderer is None:
+            _lib.check(lib, None, lib.octpt_build_block_octree(ptr, n, depth, flags, C.byref(handle)))
+        else:
+            _lib.check(lib, renderer._ctx,
+                       lib.octpt_build_block_octree_device(renderer._ctx, ptr, n, depth, flags, C.byref(handle)))
         try:
             v = _lib.OctreeView()
             _lib.check(lib, None, lib.octpt_octree_get_view(handle, C.byref(v)))

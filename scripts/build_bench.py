@@ -1,6 +1,11 @@
 """Octree build time: host builder (octpt_build_octree) vs the GPU builder
 (octpt_build_octree_device).  Prints the library call's wall time (the device call includes the
-primitive upload and the result download) and the GPU time of the build kernels."""
+primitive upload and the result download) and the GPU time of the build kernels.
+
+Block-value configs (C5b, C5s) run the block legs instead: octpt_build_block_octree against
+octpt_build_block_octree_device (end to end: cell upload, build, octant download), the build kernels alone,
+and scene set-up through octpt_scene_build_blocks_device against the host build + octpt_scene_upload.  C5s is
+built compacted (as it is rendered), C5b not (nothing merges there)."""
 import ctypes as C
 import sys
 import time
@@ -30,9 +35,61 @@ def call(sc, depth, ctx=None, reps=3):
     return best
 
 
-for name in sys.argv[1:] or ["C3", "C4", "C5"]:
+def best_of(fn, reps):
+    best = 1e9
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        best = min(best, time.perf_counter() - t)
+    return best
+
+
+def block_leg(name, sc, depth):
+    compact = name.startswith("C5s")
+    flags = _lib.BUILD_COMPACT if compact else 0
+    cells = sc.cells_array()
+    p, n = cells.ctypes.data_as(C.c_void_p), len(cells)
+    reps = 3 if n < 10_000_000 else 1  # the host builder sorts C5s's 110 M cells on one core
+    octants = [0]
+
+    def build(ctx):
+        h = C.c_void_p()
+        st = lib.octpt_build_block_octree(p, n, depth, flags, C.byref(h)) if ctx is None else \
+            lib.octpt_build_block_octree_device(ctx, p, n, depth, flags, C.byref(h))
+        _lib.check(lib, ctx, st)
+        v = _lib.OctreeView()
+        lib.octpt_octree_get_view(h, C.byref(v))
+        octants[0] = v.octant_count
+        lib.octpt_octree_free(h)
+
+    print(f"{name}: {n} cells, depth {depth}, compact={compact}", flush=True)
+    th = best_of(lambda: build(None), reps)
+    print(f"{name}: host builder {th * 1e3:.1f} ms ({octants[0]} octants)", flush=True)
+    build(r._ctx)  # warm: scratch and code objects
+    tg = best_of(lambda: build(r._ctx), 3)
+    kms = r.stats()["build_ms"]
+    print(f"{name}: GPU builder {tg * 1e3:.1f} ms end to end ({th / tg:.1f}x), build kernels {kms:.2f} ms "
+          f"({th * 1e3 / kms:.0f}x)", flush=True)
+
+    def setup_host():
+        sc.build_octree(depth, compact=compact)
+        r.set_scene(sc)
+
+    r.set_scene_built(sc, depth, compact=compact)  # warm
+    td = best_of(lambda: r.set_scene_built(sc, depth, compact=compact), 3)
+    kms2 = r.stats()["build_ms"]
+    tu = best_of(setup_host, reps)
+    print(f"{name}: scene set-up on the device {td * 1e3:.1f} ms (build kernels {kms2:.2f} ms) against host build + "
+          f"octpt_scene_upload {tu * 1e3:.1f} ms ({tu / td:.1f}x)", flush=True)
+
+
+for name in sys.argv[1:] or ["C3", "C4", "C5", "C5b", "C5s"]:
+    print(f"{name}: generating the scene", flush=True)
     sc, _, _ = S.make_config(name, build=False)
     d = sc._depth
+    if sc.blocks is not None:
+        block_leg(name, sc, d)
+        continue
     th = call(sc, d)
     tg = call(sc, d, r._ctx)
     kms = r.stats()["build_ms"]
