@@ -486,6 +486,59 @@ octpt_status octpt_build_block_octree_device(octpt_ctx *ctx, const uint32_t *cel
  * OCTPT_BUILD_CELLS_ON_DEVICE (as above).  On a multi-device context every entry builds its own replica. */
 octpt_status octpt_scene_build_blocks_device(octpt_ctx *ctx, const octpt_scene_desc *scene, const uint32_t *cells,
                                              uint32_t cell_count, uint32_t flags);
+/* Block-value worlds as 16^3 palette sections: the form the reference ingests a world in
+ * (section_to_compacted_octree / RegionOctreeBuilder, new_octree.rs:446-750).  A section is 4096 palette
+ * indices in the order of section_index_to_block_coordinates (new_octree.rs:838-850) plus a slice of a palette
+ * of block values.  A palette value of 0 is air (the reference's NonZeroU32) and produces no cell; any other
+ * value v is block id v, the leaf payload, exactly as in the cell form -- so block 0 of the block table cannot
+ * be placed through sections.  Sections may share palette slices and index blocks. */
+#define OCTPT_SECTION_UNIFORM 0xFFFFFFFFu
+typedef struct octpt_section {       /* 24 bytes */
+    uint32_t x, y, z;                /* section coordinates: cells [16x, 16x+16) etc.; 16*(x+1) <= 2^depth */
+    uint32_t palette_first, palette_count;  /* block values palette[palette_first .. +palette_count), 1..4096 entries */
+    uint32_t index_first;            /* indices[index_first .. +4096), a multiple of 4096; entry i = y<<8 | z<<4 | x
+                                        (section_index_to_block_coordinates, new_octree.rs:838-850) is a palette index.
+                                        OCTPT_SECTION_UNIFORM: no indices, every cell is palette[palette_first]
+                                        (palette_count must be 1): the reference's one-entry-palette case, :716-732 */
+} octpt_section;
+typedef struct octpt_section_world {
+    const octpt_section *sections; uint32_t section_count;
+    const uint32_t *palette;       uint32_t palette_size;
+    const uint16_t *indices;       uint32_t index_count;   /* multiple of 4096 */
+} octpt_section_world;
+/* The cells of a section world, as the rows (x, y, z, block) octpt_build_block_octree takes: sections in
+ * ascending Morton code of their section coordinates, each section's non-air cells in ascending local Morton
+ * code -- ascending Morton order of the world.  This is the definition of what the section builds below build.
+ * Host-only, no context.  *count always receives the number of cells; cells == NULL only counts; cells != NULL
+ * with capacity (in rows) < *count writes nothing and is INVALID_ARG.  INVALID_ARG also: depth < 4 or > 21; a
+ * section outside the world; two sections at one position; palette_first + palette_count > palette_size;
+ * palette_count 0 or > 4096; index_first not a multiple of 4096 or index_first + 4096 > index_count;
+ * OCTPT_SECTION_UNIFORM with palette_count != 1; an index >= palette_count; a value >= 2^27 in a section's
+ * palette slice (used by an index or not).  More than 2^31 cells is OOM. */
+octpt_status octpt_sections_to_cells(const octpt_section_world *world, uint32_t depth, uint32_t *cells,
+                                     uint32_t capacity, uint32_t *count);
+/* The block-value builder on the context's device, from sections: one block of threads per section
+ * counts its non-air cells, the (section Morton code, section) pairs are sorted, and one block per sorted section
+ * writes its (Morton code, block) pairs in local Morton order -- already sorted, so the octants follow with no
+ * sort of the cells.  The result equals octpt_build_block_octree of octpt_sections_to_cells' cells array for array,
+ * with and without OCTPT_BUILD_COMPACT, and the same worlds are INVALID_ARG / OOM.  A world whose cells are all
+ * air builds the childless root.
+ * OCTPT_BUILD_SECTIONS_ON_DEVICE (the two section entries only): world->sections, palette and indices are device
+ * pointers on the context's device and are read where they are (the struct itself is host memory); indices may be
+ * only 2-byte aligned.  They must be complete before the call, as for OCTPT_BUILD_CELLS_ON_DEVICE.  UNSUPPORTED on
+ * a multi-device context.  OCTPT_BUILD_CELLS_ON_DEVICE is INVALID_ARG here, as OCTPT_BUILD_SECTIONS_ON_DEVICE is on
+ * the cell entries. */
+#define OCTPT_BUILD_SECTIONS_ON_DEVICE 0x4u
+octpt_status octpt_build_block_octree_sections_device(octpt_ctx *ctx, const octpt_section_world *world, uint32_t depth,
+                                                      uint32_t flags, octpt_octree **out);
+/* The section counterpart of octpt_scene_build_blocks_device, with the same scene rules (blocks set, no octree,
+ * no primitives; the build depth in scene->depth): the octree is built on the device from the sections and packed
+ * into the node slots in place; the device scene is the one octpt_scene_upload makes from the host builder's octree
+ * of octpt_sections_to_cells' cells.  Besides the builder's errors, a value >= block_count in a section's palette
+ * slice is INVALID_ARG.  flags: OCTPT_BUILD_COMPACT, OCTPT_BUILD_SECTIONS_ON_DEVICE.  On a multi-device context
+ * every entry builds its own replica. */
+octpt_status octpt_scene_build_sections_device(octpt_ctx *ctx, const octpt_scene_desc *scene,
+                                               const octpt_section_world *world, uint32_t flags);
 octpt_status octpt_octree_get_view(const octpt_octree *tree, octpt_octree_view *view);
 void octpt_octree_free(octpt_octree *tree);
 

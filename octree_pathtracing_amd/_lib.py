@@ -32,6 +32,8 @@ RENDER_KERNEL_TIMING = 0x4
 RENDER_PREVIEW = 0x8
 BUILD_COMPACT = 0x1  # OCTPT_BUILD_COMPACT
 BUILD_CELLS_ON_DEVICE = 0x2  # OCTPT_BUILD_CELLS_ON_DEVICE (the device block builds)
+BUILD_SECTIONS_ON_DEVICE = 0x4  # OCTPT_BUILD_SECTIONS_ON_DEVICE (the device section builds)
+SECTION_UNIFORM = 0xFFFFFFFF  # OCTPT_SECTION_UNIFORM
 PRIM_NONE = 0xFFFFFFFF
 PRIM_CUBOID_BIT = 0x80000000
 
@@ -87,6 +89,23 @@ MODEL_NONE = 0xFFFFFFFF
 class Block(C.Structure):
     """octpt_block: a block value's six face materials or its block model."""
     _fields_ = [("face_material", C.c_uint32 * 6), ("model", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Section(C.Structure):
+    """octpt_section: a 16^3 section's position, palette slice and index block."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("z", C.c_uint32), ("palette_first", C.c_uint32),
+                ("palette_count", C.c_uint32), ("index_first", C.c_uint32)]
+
+
+class SectionWorld(C.Structure):
+    """octpt_section_world: the three arrays of a world of sections."""
+    _fields_ = [("sections", C.c_void_p), ("section_count", C.c_uint32), ("palette", C.c_void_p),
+                ("palette_size", C.c_uint32), ("indices", C.c_void_p), ("index_count", C.c_uint32)]
+
+
+# numpy view of octpt_section rows (scene.SectionWorld.sections)
+SECTION_DTYPE = [("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("palette_first", "<u4"), ("palette_count", "<u4"),
+                 ("index_first", "<u4")]
 # numpy view of octpt_quad rows (Scene.quads)
 QUAD_DTYPE = [("origin", "<f4", (3,)), ("material", "<u4"), ("u", "<f4", (3,)), ("v", "<f4", (3,)),
               ("texture_u_range", "<f4", (2,)), ("texture_v_range", "<f4", (2,)), ("reserved", "<u4", (2,))]
@@ -250,6 +269,9 @@ SIGNATURES = {
     "octpt_build_block_octree": (_i32, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "octpt_build_block_octree_device": (_i32, [_vp, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "octpt_scene_build_blocks_device": (_i32, [_vp, C.POINTER(SceneDesc), _vp, _u32, _u32]),
+    "octpt_sections_to_cells": (_i32, [C.POINTER(SectionWorld), _u32, _vp, _u32, C.POINTER(_u32)]),
+    "octpt_build_block_octree_sections_device": (_i32, [_vp, C.POINTER(SectionWorld), _u32, _u32, C.POINTER(_vp)]),
+    "octpt_scene_build_sections_device": (_i32, [_vp, C.POINTER(SceneDesc), C.POINTER(SectionWorld), _u32]),
     "octpt_scene_from_reference": (_i32, [C.POINTER(ReferenceScene), _vp, _vp, _vp, C.POINTER(SceneDesc)]),
     "octpt_octree_get_view": (_i32, [_vp, C.POINTER(OctreeView)]),
     "octpt_octree_free": (None, [_vp]),

@@ -1408,7 +1408,38 @@ octpt_status cell_error(octpt_ctx *ctx, uint32_t errors) {
     if (errors & kCellErrBlockId) return fail(ctx, OCTPT_ERR_INVALID_ARG, "a cell's block id is >= 2^27");
     if (errors & kCellErrBlockTable)
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "a cell's block id is out of range of the block table");
+    if (errors & kCellErrPalette)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "a section's palette slice is empty, > 4096 entries or leaves the palette");
+    if (errors & kCellErrIndexBlock)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "a section's index_first is not a multiple of 4096 or is past index_count");
+    if (errors & kCellErrUniform)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "a uniform section needs palette_count == 1");
+    if (errors & kCellErrPaletteIndex)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "a section index is >= its palette_count");
     return fail(ctx, OCTPT_ERR_INVALID_ARG, "two cells at one position");
+}
+
+// the section world's own refusals before any array is read: 0, or the status (the three entries share it)
+octpt_status section_world_status(const octpt_section_world *w, uint32_t depth) {
+    if (!w || depth < 4 || depth > kMaxDepth) return OCTPT_ERR_INVALID_ARG;
+    if ((w->section_count && !w->sections) || (w->palette_size && !w->palette) || (w->index_count && !w->indices))
+        return OCTPT_ERR_INVALID_ARG;
+    if (w->index_count % 4096u) return OCTPT_ERR_INVALID_ARG;
+    if (w->section_count >= kMaxBuildPairs) return OCTPT_ERR_OOM;  // one block of threads per section
+    return OCTPT_OK;
+}
+
+// the argument checks the two device section builds share (after the NULL-context check and join_inflight)
+octpt_status check_section_build_args(octpt_ctx *ctx, const octpt_section_world *w, uint32_t depth, uint32_t flags) {
+    if (flags & ~(OCTPT_BUILD_COMPACT | OCTPT_BUILD_SECTIONS_ON_DEVICE))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "unknown build flags");
+    const octpt_status st = section_world_status(w, depth);
+    if (st == OCTPT_ERR_OOM) return fail(ctx, st, "more than 2^31 sections");
+    if (st != OCTPT_OK)
+        return fail(ctx, st, "section world: NULL, depth outside [4, 21], a NULL array or index_count not a multiple of 4096");
+    if ((flags & OCTPT_BUILD_SECTIONS_ON_DEVICE) && is_multi(ctx))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "device sections live on one device: not on a multi-device context");
+    return OCTPT_OK;
 }
 
 // the argument checks the two device block builds share (after the NULL-context check and join_inflight)
@@ -1419,6 +1450,50 @@ octpt_status check_block_build_args(octpt_ctx *ctx, const uint32_t *cells, uint3
     if (cell_count > kMaxBuildPairs) return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 cells");
     if ((flags & OCTPT_BUILD_CELLS_ON_DEVICE) && is_multi(ctx))
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "device cells live on one device: not on a multi-device context");
+    return OCTPT_OK;
+}
+
+// the device scene of a block-value octree the builder left in the scratch (the two device block scene builds):
+// its octants packed into the node slots in place, the tables uploaded, as octpt_scene_upload makes it
+octpt_status pack_block_scene(octpt_ctx *ctx, const octpt_scene_desc *d, const DeviceOctree &t) {
+    octpt_status st = OCTPT_OK;
+    if ((uint64_t)t.n_octants * 8u >= 0xFFFFFFF0ull)  // the u32 slot scan cannot wrap
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "octree too large for the device build (>= 2^29 octants)");
+    uint32_t *d_base = nullptr, n_slots = 0;
+    HIP_TRY(ctx, slot_bases_gpu(ctx->stream, ctx->build_scratch, t, &d_base, n_slots));
+    const std::vector<uint32_t> bflags = block_slot_flags(d);
+    DevScene S{};
+    uint2 *d_child;
+    HIP_TRY(ctx, upload<uint2>(ctx, nullptr, (size_t)n_slots + 8, &d_child));  // zeroed: + 8 tail slots
+    HIP_TRY(ctx, fill_block_scene_gpu(ctx->stream, ctx->build_scratch, t, d_base, bflags.data(), d->block_count,
+                                      d_child));
+    uint16_t root_mask = 0;  // the root is octant 0 (pre-order), base 0
+    HIP_TRY(ctx, hipMemcpy(&root_mask, &t.octants[0].child_mask, sizeof root_mask, hipMemcpyDeviceToHost));
+    // the empty primitive tables a block-value scene has after octpt_scene_upload (one zeroed element each)
+    uint32_t *d_prims, *d_sph_mat, *d_cmat;
+    float4 *d_sph, *d_cmin;
+    float2 *d_cmax;
+    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_prims));
+    HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_sph));
+    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_sph_mat));
+    HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_cmin));
+    HIP_TRY(ctx, upload<float2>(ctx, nullptr, 0, &d_cmax));
+    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_cmat));
+    S.node_child = d_child;
+    S.leaf_prims = d_prims;
+    S.spheres = d_sph;
+    S.sphere_mat = d_sph_mat;
+    S.cub_a = d_cmin;
+    S.cub_b = d_cmax;
+    S.cub_mat = d_cmat;
+    S.root = 0u;
+    S.root_mask = root_mask;
+    S.n_octants = t.n_octants;
+    st = upload_tables(ctx, d, false, S);
+    if (st != OCTPT_OK) return st;
+    ctx->S = S;
+    ctx->has_scene = true;
+    ++ctx->scene_gen;
     return OCTPT_OK;
 }
 
@@ -1791,50 +1866,62 @@ octpt_status octpt_scene_build_blocks_device(octpt_ctx *ctx, const octpt_scene_d
         if (e != hipSuccess) return hip_fail(ctx, e, "block octree build");
         if (errors) return cell_error(ctx, errors);
         ctx->build_ms = ms;
-        if ((uint64_t)t.n_octants * 8u >= 0xFFFFFFF0ull)  // the u32 slot scan cannot wrap
-            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "octree too large for the device build (>= 2^29 octants)");
-        uint32_t *d_base = nullptr, n_slots = 0;
-        HIP_TRY(ctx, slot_bases_gpu(ctx->stream, ctx->build_scratch, t, &d_base, n_slots));
-        const std::vector<uint32_t> bflags = block_slot_flags(d);
-        DevScene S{};
-        uint2 *d_child;
-        HIP_TRY(ctx, upload<uint2>(ctx, nullptr, (size_t)n_slots + 8, &d_child));  // zeroed: + 8 tail slots
-        HIP_TRY(ctx, fill_block_scene_gpu(ctx->stream, ctx->build_scratch, t, d_base, bflags.data(), d->block_count,
-                                          d_child));
-        uint16_t root_mask = 0;  // the root is octant 0 (pre-order), base 0
-        HIP_TRY(ctx, hipMemcpy(&root_mask, &t.octants[0].child_mask, sizeof root_mask, hipMemcpyDeviceToHost));
-        // the empty primitive tables a block-value scene has after octpt_scene_upload (one zeroed element each)
-        uint32_t *d_prims, *d_sph_mat, *d_cmat;
-        float4 *d_sph, *d_cmin;
-        float2 *d_cmax;
-        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_prims));
-        HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_sph));
-        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_sph_mat));
-        HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_cmin));
-        HIP_TRY(ctx, upload<float2>(ctx, nullptr, 0, &d_cmax));
-        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_cmat));
-        S.node_child = d_child;
-        S.leaf_prims = d_prims;
-        S.spheres = d_sph;
-        S.sphere_mat = d_sph_mat;
-        S.cub_a = d_cmin;
-        S.cub_b = d_cmax;
-        S.cub_mat = d_cmat;
-        S.root = 0u;
-        S.root_mask = root_mask;
-        S.n_octants = t.n_octants;
-        st = upload_tables(ctx, d, false, S);
-        if (st != OCTPT_OK) return st;
-        ctx->S = S;
-        ctx->has_scene = true;
-        ++ctx->scene_gen;
-        return OCTPT_OK;
+        return pack_block_scene(ctx, d, t);
     } catch (const std::bad_alloc &) {
         free_scene(ctx);
         return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
     } catch (...) {
         free_scene(ctx);
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device block scene build");
+    }
+}
+
+octpt_status octpt_scene_build_sections_device(octpt_ctx *ctx, const octpt_scene_desc *d,
+                                               const octpt_section_world *world, uint32_t flags) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    join_inflight(ctx);
+    if (!d) return fail(ctx, OCTPT_ERR_INVALID_ARG, "scene NULL");
+    octpt_status st = check_section_build_args(ctx, world, d->depth, flags);
+    if (st != OCTPT_OK) return st;
+    try {
+        if (is_multi(ctx)) {  // every device entry builds its own replica
+            ctx->has_scene = false;
+            st = for_each_sub(ctx, [&](size_t i) {
+                return octpt_scene_build_sections_device(ctx->sub[i], d, world, flags);
+            });
+            ctx->has_scene = st == OCTPT_OK;
+            return st;
+        }
+        st = validate_head(ctx, d, false);
+        if (st != OCTPT_OK) return st;
+        if (!d->blocks)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "the block build needs the scene's block table (blocks is NULL)");
+        st = validate_tables(ctx, d);
+        if (st != OCTPT_OK) return st;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        free_scene(ctx);
+        // the GPU section builder (§4) with its octants left in the build scratch
+        BuiltOctree unused;
+        DeviceOctree t;
+        uint32_t errors = 0u;
+        bool too_many = false;
+        float ms = 0.0f;
+        const hipError_t e = build_section_octree_gpu(ctx->stream, ctx->build_scratch, *world,
+                                                      (flags & OCTPT_BUILD_SECTIONS_ON_DEVICE) != 0, d->depth,
+                                                      (flags & OCTPT_BUILD_COMPACT) != 0, d->block_count, kMaxBuildPairs,
+                                                      unused, errors, too_many, &ms, &t);
+        if (e != hipSuccess) return hip_fail(ctx, e, "section octree build");
+        if (errors) return cell_error(ctx, errors);
+        if (too_many) return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 cells");
+        ctx->build_ms = ms;
+        return pack_block_scene(ctx, d, t);
+    } catch (const std::bad_alloc &) {
+        free_scene(ctx);
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
+    } catch (...) {
+        free_scene(ctx);
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device section scene build");
     }
 }
 
@@ -2736,6 +2823,107 @@ octpt_status octpt_build_block_octree_device(octpt_ctx *ctx, const uint32_t *cel
         return fail(ctx, OCTPT_ERR_OOM, "block octree build: host out of memory");
     } catch (...) {
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in block octree build");
+    }
+}
+
+octpt_status octpt_sections_to_cells(const octpt_section_world *w, uint32_t depth, uint32_t *cells, uint32_t capacity,
+                                     uint32_t *count) {
+    if (!count) return OCTPT_ERR_INVALID_ARG;
+    *count = 0u;
+    const octpt_status st = section_world_status(w, depth);
+    if (st != OCTPT_OK) return st;
+    try {
+        // validate and count: sections in ascending Morton code of their coordinates
+        std::vector<std::pair<uint64_t, uint32_t>> order(w->section_count);
+        uint64_t total = 0;
+        for (uint32_t s = 0; s < w->section_count; ++s) {
+            const octpt_section &sec = w->sections[s];
+            if ((sec.x | sec.y | sec.z) >> (depth - 4u)) return OCTPT_ERR_INVALID_ARG;
+            if (sec.palette_count == 0u || sec.palette_count > 4096u ||
+                (uint64_t)sec.palette_first + sec.palette_count > w->palette_size)
+                return OCTPT_ERR_INVALID_ARG;
+            const uint32_t *pal = w->palette + sec.palette_first;
+            for (uint32_t i = 0; i < sec.palette_count; ++i)
+                if (pal[i] > kPrimIndexMask) return OCTPT_ERR_INVALID_ARG;
+            if (sec.index_first == OCTPT_SECTION_UNIFORM) {
+                if (sec.palette_count != 1u) return OCTPT_ERR_INVALID_ARG;
+                total += pal[0] ? 4096u : 0u;
+            } else {
+                if ((sec.index_first & 4095u) || (uint64_t)sec.index_first + 4096u > w->index_count)
+                    return OCTPT_ERR_INVALID_ARG;
+                const uint16_t *idx = w->indices + sec.index_first;
+                for (uint32_t i = 0; i < 4096u; ++i) {
+                    if (idx[i] >= sec.palette_count) return OCTPT_ERR_INVALID_ARG;
+                    total += pal[idx[i]] ? 1u : 0u;
+                }
+            }
+            order[s] = {morton(sec.x, sec.y, sec.z), s};
+        }
+        std::sort(order.begin(), order.end());
+        for (size_t k = 1; k < order.size(); ++k)
+            if (order[k].first == order[k - 1].first) return OCTPT_ERR_INVALID_ARG;  // two sections at one position
+        if (total > kMaxBuildPairs) return OCTPT_ERR_OOM;
+        *count = (uint32_t)total;
+        if (!cells) return OCTPT_OK;
+        if (capacity < total) return OCTPT_ERR_INVALID_ARG;
+        uint32_t *out = cells;
+        for (const auto &ks : order) {
+            const octpt_section &sec = w->sections[ks.second];
+            const uint32_t *pal = w->palette + sec.palette_first;
+            const bool uniform = sec.index_first == OCTPT_SECTION_UNIFORM;
+            const uint16_t *idx = uniform ? nullptr : w->indices + sec.index_first;
+            for (uint32_t m = 0; m < 4096u; ++m) {  // local Morton order: x bit 0, y bit 1, z bit 2 per level
+                uint32_t x = 0, y = 0, z = 0;
+                for (uint32_t b = 0; b < 4u; ++b) {
+                    x |= ((m >> (3u * b)) & 1u) << b;
+                    y |= ((m >> (3u * b + 1u)) & 1u) << b;
+                    z |= ((m >> (3u * b + 2u)) & 1u) << b;
+                }
+                const uint32_t v = uniform ? pal[0] : pal[idx[y << 8 | z << 4 | x]];
+                if (!v) continue;
+                out[0] = 16u * sec.x + x;
+                out[1] = 16u * sec.y + y;
+                out[2] = 16u * sec.z + z;
+                out[3] = v;
+                out += 4;
+            }
+        }
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return OCTPT_ERR_OOM;
+    } catch (...) {
+        return OCTPT_ERR_INTERNAL;
+    }
+}
+
+octpt_status octpt_build_block_octree_sections_device(octpt_ctx *ctx, const octpt_section_world *world, uint32_t depth,
+                                                      uint32_t flags, octpt_octree **out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    join_inflight(ctx);
+    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "out NULL");
+    *out = nullptr;
+    const octpt_status st = check_section_build_args(ctx, world, depth, flags);
+    if (st != OCTPT_OK) return st;
+    try {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::unique_ptr<octpt_octree> t(new octpt_octree());
+        uint32_t errors = 0u;
+        bool too_many = false;
+        float ms = 0.0f;
+        const hipError_t e = build_section_octree_gpu(ctx->stream, ctx->build_scratch, *world,
+                                                      (flags & OCTPT_BUILD_SECTIONS_ON_DEVICE) != 0, depth,
+                                                      (flags & OCTPT_BUILD_COMPACT) != 0, 0u, kMaxBuildPairs, *t, errors,
+                                                      too_many, &ms);
+        if (e != hipSuccess) return hip_fail(ctx, e, "section octree build");
+        if (errors) return cell_error(ctx, errors);
+        if (too_many) return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 cells");
+        ctx->build_ms = ms;
+        *out = t.release();
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "section octree build: host out of memory");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in section octree build");
     }
 }
 

@@ -161,6 +161,191 @@ __global__ __launch_bounds__(kBuildBlock) void emit_cells_kernel(const uint32_t 
     blks[k] = c.w;
 }
 
+// ---------------------------------------------------------------------------
+// 16^3 palette sections (octpt_build_block_octree_sections_device): the front end that writes the cell builder's
+// (Morton code, block) streams already sorted.  One 256-thread block per section stages the section's palette
+// slice (<= 16 KB) and its 4096 16-bit palette indices (8 KB) in LDS.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSectionCells = 4096;
+// LDS position of index i = y<<8 | z<<4 | x: 4 pad entries (2 dwords) per y-plane, so the 4x4x4 cube a wave reads
+// per emit step (x: 2 dwords, z: stride 8 dwords, y: stride 128 + 2 dwords) covers 32 distinct banks
+__device__ __forceinline__ uint32_t index_slot(uint32_t i) { return i + ((i >> 8) << 2); }
+constexpr uint32_t kSectionIndexSlots = kSectionCells + 16 * 4;
+
+// the struct-level refusals (octpt_sections_to_cells): 0 = the palette slice and the index block may be read
+__device__ inline uint32_t section_errors(const octpt_section &s, uint32_t depth, uint32_t palette_size,
+                                          uint32_t index_count) {
+    uint32_t e = 0u;
+    if ((s.x | s.y | s.z) >> (depth - 4u)) e |= kCellErrRange;
+    if (s.palette_count == 0u || s.palette_count > kSectionCells ||
+        (uint64_t)s.palette_first + s.palette_count > palette_size)
+        e |= kCellErrPalette;
+    if (s.index_first == OCTPT_SECTION_UNIFORM) {
+        if (s.palette_count != 1u) e |= kCellErrUniform;
+    } else if ((s.index_first & (kSectionCells - 1u)) || (uint64_t)s.index_first + kSectionCells > index_count) {
+        e |= kCellErrIndexBlock;
+    }
+    return e;
+}
+
+// what a block value raises (the cell builder's checks)
+__device__ __forceinline__ uint32_t value_errors(uint32_t v, uint32_t block_count) {
+    uint32_t e = 0u;
+    if (v > kPrimIndexMask) e |= kCellErrBlockId;
+    if (block_count && v >= block_count) e |= kCellErrBlockTable;
+    return e;
+}
+
+// the section's 4096 indices into LDS (index_slot positions); aligned: 16-byte loads, else 2-byte loads
+__device__ inline void stage_indices(const uint16_t *__restrict__ g, bool aligned, uint16_t *s_idx) {
+    if (aligned) {
+        const uint4 *g4 = reinterpret_cast<const uint4 *>(g);
+        for (uint32_t q = threadIdx.x; q < kSectionCells / 8u; q += kBuildBlock) {
+            const uint4 v = g4[q];
+            uint2 *d = reinterpret_cast<uint2 *>(s_idx + index_slot(8u * q));  // 8-byte aligned: 16 q + 8 (q >> 5)
+            d[0] = make_uint2(v.x, v.y);
+            d[1] = make_uint2(v.z, v.w);
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < kSectionCells; i += kBuildBlock) s_idx[index_slot(i)] = g[i];
+    }
+}
+
+// bits 0, 3, 6, 9 of v gathered into bits 0..3 (a coordinate of a 12-bit local Morton code)
+__device__ __forceinline__ uint32_t compact_4(uint32_t v) {
+    v &= 0x249u;
+    v = (v | v >> 2) & 0x0C3u;
+    v = (v | v >> 4) & 0x00Fu;
+    return v;
+}
+
+// Count: block s validates section s and writes its Morton key, its id and its number of non-air cells (0 when
+// the section is refused; every refusal is ORed into *err and nothing out of bounds is read)
+__global__ __launch_bounds__(kBuildBlock) void section_count_kernel(
+    const octpt_section *__restrict__ secs, const uint32_t *__restrict__ palette, uint32_t palette_size,
+    const uint16_t *__restrict__ indices, uint32_t index_count, bool aligned, uint32_t depth, uint32_t block_count,
+    uint64_t *__restrict__ keys, uint32_t *__restrict__ ids, uint32_t *__restrict__ counts,
+    uint32_t *__restrict__ err) {
+    __shared__ uint32_t s_pal[kSectionCells];
+    __shared__ __attribute__((aligned(16))) uint16_t s_idx[kSectionIndexSlots];
+    __shared__ uint32_t s_wave[kBuildBlock / 64];
+    const uint32_t s = blockIdx.x, tid = threadIdx.x;
+    const octpt_section sec = secs[s];
+    if (tid == 0u) {
+        keys[s] = morton(sec.x, sec.y, sec.z);
+        ids[s] = s;
+    }
+    uint32_t e = section_errors(sec, depth, palette_size, index_count);
+    if (e) {  // uniform over the block
+        if (tid == 0u) {
+            atomicOr(err, e);
+            counts[s] = 0u;
+        }
+        return;
+    }
+    if (sec.index_first == OCTPT_SECTION_UNIFORM) {  // 0 or 4096 cells, no index read
+        if (tid == 0u) {
+            const uint32_t v = palette[sec.palette_first];
+            e = value_errors(v, block_count);
+            if (e) atomicOr(err, e);
+            counts[s] = v ? kSectionCells : 0u;
+        }
+        return;
+    }
+    for (uint32_t i = tid; i < sec.palette_count; i += kBuildBlock) {
+        const uint32_t v = palette[sec.palette_first + i];
+        e |= value_errors(v, block_count);
+        s_pal[i] = v;
+    }
+    stage_indices(indices + sec.index_first, aligned, s_idx);
+    __syncthreads();
+    uint32_t n = 0u;  // the wave's non-air cells (the same in every lane)
+#pragma unroll
+    for (uint32_t k = 0; k < kSectionCells / kBuildBlock; ++k) {
+        const uint32_t idx = s_idx[index_slot(k * kBuildBlock + tid)];
+        const bool ok = idx < sec.palette_count;
+        if (!ok) e |= kCellErrPaletteIndex;
+        const bool solid = ok && s_pal[ok ? idx : 0u] != 0u;
+        n += (uint32_t)__popcll(__ballot(solid));
+    }
+    if (e) atomicOr(err, e);
+    if ((tid & 63u) == 0u) s_wave[tid >> 6] = n;
+    __syncthreads();
+    if (tid == 0u) counts[s] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// Order: the counts in sorted section order (entry n_sec = 0: the exclusive scan's last input); two equal
+// neighbours among the sorted keys are two sections at one position
+__global__ __launch_bounds__(kBuildBlock) void section_order_kernel(const uint64_t *__restrict__ keys_s,
+                                                                    const uint32_t *__restrict__ ids_s,
+                                                                    const uint32_t *__restrict__ counts,
+                                                                    uint32_t n_sec,
+                                                                    unsigned long long *__restrict__ cnt_s,
+                                                                    uint32_t *__restrict__ err) {
+    const uint32_t j = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (j > n_sec) return;
+    cnt_s[j] = j < n_sec ? counts[ids_s[j]] : 0u;
+    if (j > 0u && j < n_sec && keys_s[j] == keys_s[j - 1u]) atomicOr(err, kCellErrDuplicate);
+}
+
+// Emit: block j writes the cells of the j-th section in Morton order from offs[j]: code = key << 12 | m for the
+// local Morton codes m in ascending order, the block value beside it.  Wave w takes m in [1024 w, 1024 w + 1024),
+// 64 consecutive codes per step; a cell's rank is the wave's running count + the ballot's prefix count, and the
+// waves' bases come from their totals through LDS -- no atomics.  Runs only after the count raised no error.
+__global__ __launch_bounds__(kBuildBlock) void section_emit_kernel(
+    const octpt_section *__restrict__ secs, const uint32_t *__restrict__ palette,
+    const uint16_t *__restrict__ indices, bool aligned, const uint64_t *__restrict__ keys_s,
+    const uint32_t *__restrict__ ids_s, const unsigned long long *__restrict__ offs, uint32_t n_cells,
+    uint64_t *__restrict__ codes, uint32_t *__restrict__ blks) {
+    __shared__ uint32_t s_pal[kSectionCells];
+    __shared__ __attribute__((aligned(16))) uint16_t s_idx[kSectionIndexSlots];
+    __shared__ uint32_t s_wave[kBuildBlock / 64];
+    const uint32_t j = blockIdx.x, tid = threadIdx.x;
+    const unsigned long long base = offs[j];
+    if (offs[j + 1u] == base) return;  // all air
+    const octpt_section sec = secs[ids_s[j]];
+    const uint64_t hi = keys_s[j] << 12;
+    if (sec.index_first == OCTPT_SECTION_UNIFORM) {
+        const uint32_t v = palette[sec.palette_first];
+        for (uint32_t m = tid; m < kSectionCells; m += kBuildBlock) {
+            const unsigned long long o = base + m;
+            if (o < n_cells) {
+                codes[o] = hi | m;
+                blks[o] = v;
+            }
+        }
+        return;
+    }
+    for (uint32_t i = tid; i < sec.palette_count; i += kBuildBlock) s_pal[i] = palette[sec.palette_first + i];
+    stage_indices(indices + sec.index_first, aligned, s_idx);
+    __syncthreads();
+    constexpr uint32_t kSteps = kSectionCells / kBuildBlock;  // 16 steps of 64 codes per wave
+    const uint32_t wave = tid >> 6, lane = tid & 63u, m0 = wave * (kSectionCells / 4u) + lane;
+    uint32_t val[kSteps], rank[kSteps], run = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kSteps; ++k) {
+        const uint32_t m = m0 + k * 64u;
+        const uint32_t i = compact_4(m >> 1) << 8 | compact_4(m >> 2) << 4 | compact_4(m);  // y<<8 | z<<4 | x
+        const uint32_t idx = s_idx[index_slot(i)];
+        val[k] = idx < sec.palette_count ? s_pal[idx] : 0u;
+        const unsigned long long b = __ballot(val[k] != 0u);
+        rank[k] = run + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        run += (uint32_t)__popcll(b);
+    }
+    if (lane == 0u) s_wave[wave] = run;
+    __syncthreads();
+    unsigned long long o0 = base;
+    for (uint32_t w = 0; w < wave; ++w) o0 += s_wave[w];
+#pragma unroll
+    for (uint32_t k = 0; k < kSteps; ++k) {
+        const unsigned long long o = o0 + rank[k];
+        if (val[k] != 0u && o < n_cells) {
+            codes[o] = hi | (m0 + k * 64u);
+            blks[o] = val[k];
+        }
+    }
+}
+
 __global__ __launch_bounds__(kBuildBlock) void leaf_heads_kernel(const uint64_t *__restrict__ codes, uint32_t n,
                                                                  uint32_t *__restrict__ head) {
     const uint32_t k = blockIdx.x * kBuildBlock + threadIdx.x;
@@ -334,7 +519,8 @@ inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + kBuildBlock - 1) / k
 // slots of the context's grow-only scratch, taken in a fixed order per build
 struct ScratchCursor {
     BuildScratch &s;
-    int next = 0;  // a build takes at most slots 0..25 in a fixed order, slot_bases_gpu 27..29, the block flags 30
+    int next = 0;  // a build takes at most slots 0..25 in a fixed order (the section build's per-section arrays
+                   // 17..24), slot_bases_gpu 27..29, the block flags 30
     template <class T>
     hipError_t get(T **ptr, size_t n) {
         const int k = next++;
@@ -581,29 +767,23 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     return hipSuccess;
 }
 
-// The block-value builder (octpt_internal.h).  Scratch slots in a fixed order like build_octree_gpu's, at
-// most 0..17.  One readback (the error word with the octant count) precedes the octant arrays.
-hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, const uint32_t *cells, uint32_t n,
-                                  bool cells_on_device, uint32_t depth, bool compact, uint32_t block_count,
-                                  BuiltOctree &out, uint32_t &errors, float *ms, DeviceOctree *dev) {
-    errors = 0u;
-    ScratchCursor pool{scratch};
-    hipEvent_t e0, e1;
-    BTRY(hipEventCreate(&e0));
-    BTRY(hipEventCreate(&e1));
-    struct EvGuard {
-        hipEvent_t a, b;
-        ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    } evg{e0, e1};
-    uint32_t *d_cells, *d_err;
-    BTRY(pool.get(&d_cells, cells_on_device ? 0u : (size_t)n * 4));
-    BTRY(pool.get(&d_err, 2));  // the error word, and beside it the octant count (one readback)
-    const uint32_t *d_in = cells;
-    if (!cells_on_device) {
-        if (n) BTRY(hipMemcpyAsync(d_cells, cells, (size_t)n * 16, hipMemcpyHostToDevice, stream));
-        d_in = d_cells;
+namespace {
+
+// the two events a build's kernel time is taken between
+struct BuildEvents {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t create() {
+        const hipError_t e = hipEventCreate(&e0);
+        return e != hipSuccess ? e : hipEventCreate(&e1);
     }
-    BTRY(hipEventRecord(e0, stream));
+    ~BuildEvents() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// a block-value build's result fields before the octants exist
+void block_result_init(BuiltOctree &out, DeviceOctree *dev, uint32_t depth) {
     out.depth = depth;
     out.root = 0u;
     out.leaf_first.clear();
@@ -613,20 +793,87 @@ hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, con
         *dev = DeviceOctree{};
         dev->depth = depth;
     }
-    if (n == 0u) {  // empty world: a childless root, as the host builder emits
-        if (ms) *ms = 0.0f;
-        if (dev) {
-            octpt_octant *d_root;
-            BTRY(pool.get(&d_root, 1));
-            BTRY(hipMemsetAsync(d_root, 0, sizeof(octpt_octant), stream));
-            BTRY(hipStreamSynchronize(stream));
-            dev->octants = d_root;
-            dev->n_octants = 1u;
-            return hipSuccess;
-        }
-        out.octants.assign(1, octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
+}
+
+// no cells: a childless root, as the host builder emits
+hipError_t block_empty_root(hipStream_t stream, ScratchCursor &pool, BuiltOctree &out, float *ms, DeviceOctree *dev) {
+    if (ms) *ms = 0.0f;
+    if (dev) {
+        octpt_octant *d_root;
+        BTRY(pool.get(&d_root, 1));
+        BTRY(hipMemsetAsync(d_root, 0, sizeof(octpt_octant), stream));
+        BTRY(hipStreamSynchronize(stream));
+        dev->octants = d_root;
+        dev->n_octants = 1u;
         return hipSuccess;
     }
+    out.octants.assign(1, octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
+    return hipSuccess;
+}
+
+// The tail of the block-value builds, from n >= 1 Morton-sorted (code, block) pairs: every cell is a leaf -- the
+// octants it opens and equal neighbours (two blocks in one cell) -- the scan, one readback (the error word d_err[0]
+// with the octant count beside it), then the octants.  d_opens / d_base: n + 1 entries; d_tmp: base_bytes, the
+// scan's temporary storage.
+hipError_t block_tail_gpu(hipStream_t stream, ScratchCursor &pool, const BuildEvents &ev, const uint64_t *d_code_s,
+                          const uint32_t *d_blk_s, uint32_t n, uint32_t depth, bool compact, uint32_t *d_err,
+                          uint32_t *d_opens, uint32_t *d_base, char *d_tmp, size_t base_bytes, BuiltOctree &out,
+                          uint32_t &errors, float *ms, DeviceOctree *dev) {
+    BTRY(hipMemsetAsync(d_opens + n, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(leaf_count_kernel<true>, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, (const uint32_t *)nullptr,
+                       d_code_s, n, n, depth, (uint32_t *)nullptr, d_opens, d_err);
+    BTRY(hipGetLastError());
+    BTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, base_bytes, d_opens, d_base, n + 1, stream));
+    BTRY(hipMemcpyAsync(d_err + 1, d_base + n, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    uint32_t head[2] = {0u, 0u};
+    BTRY(hipMemcpyAsync(head, d_err, sizeof head, hipMemcpyDeviceToHost, stream));
+    BTRY(hipStreamSynchronize(stream));
+    if (head[0]) {
+        errors = head[0];
+        return hipSuccess;
+    }
+    uint32_t n_oct = head[1];
+    octpt_octant *d_oct;
+    BTRY(octants_gpu<true>(stream, pool, d_code_s, d_base, d_opens, n, depth, compact, d_blk_s, nullptr, nullptr, nullptr,
+                           n_oct, &d_oct));
+    BTRY(hipEventRecord(ev.e1, stream));
+    if (dev) {  // device-resident: the octants stay in the scratch
+        dev->octants = d_oct;
+        dev->n_octants = n_oct;
+        BTRY(hipStreamSynchronize(stream));
+        if (ms) BTRY(hipEventElapsedTime(ms, ev.e0, ev.e1));
+        return hipSuccess;
+    }
+    out.octants.resize(n_oct);
+    BTRY(hipMemcpyAsync(out.octants.data(), d_oct, (size_t)n_oct * sizeof(octpt_octant), hipMemcpyDeviceToHost,
+                        stream));
+    BTRY(hipStreamSynchronize(stream));
+    if (ms) BTRY(hipEventElapsedTime(ms, ev.e0, ev.e1));
+    return hipSuccess;
+}
+
+}  // namespace
+
+// The block-value builder (octpt_internal.h): the cell front end -- emit and radix sort -- and block_tail_gpu.
+// Scratch slots in a fixed order like build_octree_gpu's, at most 0..16.
+hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, const uint32_t *cells, uint32_t n,
+                                  bool cells_on_device, uint32_t depth, bool compact, uint32_t block_count,
+                                  BuiltOctree &out, uint32_t &errors, float *ms, DeviceOctree *dev) {
+    errors = 0u;
+    ScratchCursor pool{scratch};
+    BuildEvents ev;
+    BTRY(ev.create());
+    uint32_t *d_cells, *d_err;
+    BTRY(pool.get(&d_cells, cells_on_device ? 0u : (size_t)n * 4));
+    BTRY(pool.get(&d_err, 2));  // the error word, and beside it the octant count (one readback)
+    const uint32_t *d_in = cells;
+    if (!cells_on_device) {
+        if (n) BTRY(hipMemcpyAsync(d_cells, cells, (size_t)n * 16, hipMemcpyHostToDevice, stream));
+        d_in = d_cells;
+    }
+    BTRY(hipEventRecord(ev.e0, stream));
+    block_result_init(out, dev, depth);
+    if (n == 0u) return block_empty_root(stream, pool, out, ms, dev);
     uint64_t *d_code, *d_code_s;
     uint32_t *d_blk, *d_blk_s, *d_opens, *d_base;
     BTRY(pool.get(&d_code, n));
@@ -647,38 +894,123 @@ hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, con
     BTRY(pool.get(&d_tmp, std::max(sort_bytes, base_bytes)));
     BTRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
                                             (int)(3u * depth), stream));
-    // every cell is a leaf: the octants it opens, and equal neighbours (two blocks in one cell)
-    BTRY(hipMemsetAsync(d_opens + n, 0, sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(leaf_count_kernel<true>, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, (const uint32_t *)nullptr,
-                       d_code_s, n, n, depth, (uint32_t *)nullptr, d_opens, d_err);
+    return block_tail_gpu(stream, pool, ev, d_code_s, d_blk_s, n, depth, compact, d_err, d_opens, d_base, d_tmp,
+                          base_bytes, out, errors, ms, dev);
+}
+
+// The section front end (octpt_internal.h) and block_tail_gpu.  The large streams take the cell build's slots
+// (2 codes, 4 blocks, 6..8 the tail's scan, 9..16 the octants; 3 and 5 only with OCTPT_SECTION_SORT), so a context
+// that builds both ways does not hold them twice; the per-section arrays take slots 17..24.
+hipError_t build_section_octree_gpu(hipStream_t stream, BuildScratch &scratch, const octpt_section_world &world,
+                                    bool on_device, uint32_t depth, bool compact, uint32_t block_count,
+                                    uint64_t max_cells, BuiltOctree &out, uint32_t &errors, bool &too_many, float *ms,
+                                    DeviceOctree *dev) {
+    errors = 0u;
+    too_many = false;
+    ScratchCursor pool{scratch}, small{scratch, 17};
+    BuildEvents ev;
+    BTRY(ev.create());
+    const uint32_t n_sec = world.section_count;
+    // host arrays: one upload each into slot 0, at 16-byte aligned offsets
+    const size_t sec_bytes = (size_t)n_sec * sizeof(octpt_section), pal_bytes = (size_t)world.palette_size * 4,
+                 idx_bytes = (size_t)world.index_count * 2;
+    const size_t pal_at = (sec_bytes + 15) & ~(size_t)15, idx_at = (pal_at + pal_bytes + 15) & ~(size_t)15;
+    char *d_in;
+    uint32_t *d_err;
+    BTRY(pool.get(&d_in, on_device ? 0u : idx_at + idx_bytes));
+    BTRY(pool.get(&d_err, 4));  // the error word, the octant count, and the 64-bit cell count (8-byte aligned)
+    const octpt_section *d_secs = world.sections;
+    const uint32_t *d_pal = world.palette;
+    const uint16_t *d_idx = world.indices;
+    if (!on_device) {
+        if (sec_bytes) BTRY(hipMemcpyAsync(d_in, world.sections, sec_bytes, hipMemcpyHostToDevice, stream));
+        if (pal_bytes) BTRY(hipMemcpyAsync(d_in + pal_at, world.palette, pal_bytes, hipMemcpyHostToDevice, stream));
+        if (idx_bytes) BTRY(hipMemcpyAsync(d_in + idx_at, world.indices, idx_bytes, hipMemcpyHostToDevice, stream));
+        d_secs = reinterpret_cast<const octpt_section *>(d_in);
+        d_pal = reinterpret_cast<const uint32_t *>(d_in + pal_at);
+        d_idx = reinterpret_cast<const uint16_t *>(d_in + idx_at);
+    }
+    BTRY(hipEventRecord(ev.e0, stream));
+    block_result_init(out, dev, depth);
+    if (n_sec == 0u) return block_empty_root(stream, pool, out, ms, dev);
+    // count, order
+    uint64_t *d_key, *d_key_s;
+    uint32_t *d_id, *d_id_s, *d_cnt;
+    unsigned long long *d_cnt_s, *d_off;
+    BTRY(small.get(&d_key, n_sec));
+    BTRY(small.get(&d_id, n_sec));
+    BTRY(small.get(&d_key_s, n_sec));
+    BTRY(small.get(&d_id_s, n_sec));
+    BTRY(small.get(&d_cnt, n_sec));
+    BTRY(small.get(&d_cnt_s, (size_t)n_sec + 1));  // entry n_sec = 0: the exclusive scan's last input
+    BTRY(small.get(&d_off, (size_t)n_sec + 1));
+    const bool aligned = (reinterpret_cast<uintptr_t>(d_idx) & 15u) == 0u;
+    const int key_bits = std::max(1, (int)(3u * (depth - 4u)));
+    BTRY(hipMemsetAsync(d_err, 0, 4 * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(section_count_kernel, dim3(n_sec), dim3(kBuildBlock), 0, stream, d_secs, d_pal,
+                       world.palette_size, d_idx, world.index_count, aligned, depth, block_count, d_key, d_id, d_cnt,
+                       d_err);
     BTRY(hipGetLastError());
-    BTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, base_bytes, d_opens, d_base, n + 1, stream));
-    BTRY(hipMemcpyAsync(d_err + 1, d_base + n, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-    uint32_t head[2] = {0u, 0u};
+    size_t key_sort_bytes = 0, off_bytes = 0;
+    BTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, key_sort_bytes, d_key, d_key_s, d_id, d_id_s, n_sec, 0, key_bits,
+                                            stream));
+    BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, off_bytes, d_cnt_s, d_off, n_sec + 1, stream));
+    char *d_tmp_s;
+    BTRY(small.get(&d_tmp_s, std::max(key_sort_bytes, off_bytes)));
+    BTRY(hipcub::DeviceRadixSort::SortPairs(d_tmp_s, key_sort_bytes, d_key, d_key_s, d_id, d_id_s, n_sec, 0, key_bits,
+                                            stream));
+    hipLaunchKernelGGL(section_order_kernel, dim3(blocks((uint64_t)n_sec + 1)), dim3(kBuildBlock), 0, stream, d_key_s,
+                       d_id_s, d_cnt, n_sec, d_cnt_s, d_err);
+    BTRY(hipGetLastError());
+    BTRY(hipcub::DeviceScan::ExclusiveSum(d_tmp_s, off_bytes, d_cnt_s, d_off, n_sec + 1, stream));
+    BTRY(hipMemcpyAsync(d_err + 2, d_off + n_sec, sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+    uint32_t head[4] = {0u, 0u, 0u, 0u};
     BTRY(hipMemcpyAsync(head, d_err, sizeof head, hipMemcpyDeviceToHost, stream));
     BTRY(hipStreamSynchronize(stream));
-    if (head[0]) {
+    if (head[0]) {  // nothing is emitted from a refused world
         errors = head[0];
         return hipSuccess;
     }
-    uint32_t n_oct = head[1];
-    octpt_octant *d_oct;
-    BTRY(octants_gpu<true>(stream, pool, d_code_s, d_base, d_opens, n, depth, compact, d_blk_s, nullptr, nullptr, nullptr,
-                           n_oct, &d_oct));
-    BTRY(hipEventRecord(e1, stream));
-    if (dev) {  // device-resident: the octants stay in the scratch
-        dev->octants = d_oct;
-        dev->n_octants = n_oct;
-        BTRY(hipStreamSynchronize(stream));
-        if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
+    const uint64_t total = (uint64_t)head[2] | (uint64_t)head[3] << 32;
+    if (total > max_cells) {
+        too_many = true;
         return hipSuccess;
     }
-    out.octants.resize(n_oct);
-    BTRY(hipMemcpyAsync(out.octants.data(), d_oct, (size_t)n_oct * sizeof(octpt_octant), hipMemcpyDeviceToHost,
-                        stream));
-    BTRY(hipStreamSynchronize(stream));
-    if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
-    return hipSuccess;
+    const uint32_t n = (uint32_t)total;
+    if (n == 0u) return block_empty_root(stream, pool, out, ms, dev);  // every cell is air
+    // emit: the streams come out sorted
+    uint64_t *d_code, *d_code_s;
+    uint32_t *d_blk, *d_blk_s, *d_opens, *d_base;
+#ifdef OCTPT_SECTION_SORT
+    const size_t n_sorted = n;  // A/B: the cell build's radix sort over the emitted streams
+#else
+    const size_t n_sorted = 0;
+#endif
+    BTRY(pool.get(&d_code, n));
+    BTRY(pool.get(&d_code_s, n_sorted));
+    BTRY(pool.get(&d_blk, n));
+    BTRY(pool.get(&d_blk_s, n_sorted));
+    BTRY(pool.get(&d_opens, (size_t)n + 1));  // entry n = 0: the exclusive scan's last input
+    BTRY(pool.get(&d_base, (size_t)n + 1));
+    hipLaunchKernelGGL(section_emit_kernel, dim3(n_sec), dim3(kBuildBlock), 0, stream, d_secs, d_pal, d_idx, aligned,
+                       d_key_s, d_id_s, d_off, n, d_code, d_blk);
+    BTRY(hipGetLastError());
+    size_t sort_bytes = 0, base_bytes = 0;
+    BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, base_bytes, d_opens, d_base, n + 1, stream));
+#ifdef OCTPT_SECTION_SORT
+    BTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
+                                            (int)(3u * depth), stream));
+#endif
+    char *d_tmp;
+    BTRY(pool.get(&d_tmp, std::max(sort_bytes, base_bytes)));
+#ifdef OCTPT_SECTION_SORT
+    BTRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
+                                            (int)(3u * depth), stream));
+    std::swap(d_code, d_code_s);
+    std::swap(d_blk, d_blk_s);
+#endif
+    return block_tail_gpu(stream, pool, ev, d_code, d_blk, n, depth, compact, d_err, d_opens, d_base, d_tmp, base_bytes,
+                          out, errors, ms, dev);
 }
 
 // ---------------------------------------------------------------------------

@@ -411,6 +411,22 @@ hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, con
                                   bool cells_on_device, uint32_t depth, bool compact, uint32_t block_count,
                                   BuiltOctree &out, uint32_t &errors, float *ms, DeviceOctree *dev = nullptr);
 
+// The block-value builder from 16^3 palette sections (octpt_build_block_octree_sections_device): a front end
+// that writes the (Morton code, block) streams of octpt_sections_to_cells' cells already sorted -- count per
+// section, sort of the section keys, emit per sorted section in local Morton order -- and the cell builder's
+// tail.  The world's three arrays are host arrays uploaded once into the scratch, or with on_device read where
+// they are.  `errors`: the kCellErr* bits above (range = a section outside the world, duplicate = two sections
+// at one position; block id / block table = a value of a section's palette slice) and the section bits below;
+// when it is not 0 nothing is built.  too_many: more than max_cells cells (nothing is built).
+constexpr uint32_t kCellErrPalette = 16u;       // palette_count 0 or > 4096, or the slice leaves the palette
+constexpr uint32_t kCellErrIndexBlock = 32u;    // index_first not a multiple of 4096 or past index_count
+constexpr uint32_t kCellErrUniform = 64u;       // OCTPT_SECTION_UNIFORM with palette_count != 1
+constexpr uint32_t kCellErrPaletteIndex = 128u; // an index >= palette_count
+hipError_t build_section_octree_gpu(hipStream_t stream, BuildScratch &scratch, const octpt_section_world &world,
+                                    bool on_device, uint32_t depth, bool compact, uint32_t block_count,
+                                    uint64_t max_cells, BuiltOctree &out, uint32_t &errors, bool &too_many, float *ms,
+                                    DeviceOctree *dev = nullptr);
+
 // Device-resident scene packing (octpt_scene_build_device): the sparse child-slot bases of a
 // DeviceOctree (exclusive scan of the present-child counts; *d_base in the scratch, n_octants + 1
 // entries, the last = slot count), then the slots, the single-sphere leaf table and the primitive

@@ -201,6 +201,21 @@ class HipRenderer:
         self._set_scene_built_blocks(scene, depth, int(cells_ptr), int(cell_count),
                                      _lib.BUILD_CELLS_ON_DEVICE | (_lib.BUILD_COMPACT if compact else 0))
 
+    def set_scene_built_sections(self, scene: Scene, depth: int, world, compact: bool = False,
+                                 on_device=False) -> None:
+        """set_scene_built for a block-value scene from a scene.SectionWorld (octpt_scene_build_sections_device):
+        the device scene equals set_scene after a host build of world.to_cells().  on_device: the (sections,
+        palette, indices) device addresses of copies of the world's arrays on this GPU, complete before the call
+        (OCTPT_BUILD_SECTIONS_ON_DEVICE); False: the host arrays are uploaded.  scene.cells is not read."""
+        if scene.blocks is None:
+            raise ValueError("set_scene_built_sections: a block-value scene (scene.blocks) is needed")
+        flags = (_lib.BUILD_COMPACT if compact else 0) | (_lib.BUILD_SECTIONS_ON_DEVICE if on_device else 0)
+        desc, keep = scene.to_desc(octree=False, depth=depth)
+        w = world.struct(on_device if on_device else None)
+        self._check(self._lib.octpt_scene_build_sections_device(self._ctx, C.byref(desc), C.byref(w), flags))
+        self._scene_keep = keep
+        self.reset_render()
+
     def _set_scene_built_blocks(self, scene: Scene, depth: int, cells_ptr, cell_count: int, flags: int) -> None:
         desc, keep = scene.to_desc(octree=False, depth=depth)
         self._check(self._lib.octpt_scene_build_blocks_device(self._ctx, C.byref(desc), cells_ptr, cell_count, flags))

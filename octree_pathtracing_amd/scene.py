@@ -8,7 +8,7 @@ C++ builder (``liboctpt.so: octpt_build_octree``).
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace as dataclasses_replace
 from pathlib import Path
 
 import numpy as np
@@ -191,6 +191,84 @@ class Octree:
 
 
 @dataclass
+class SectionWorld:
+    """octpt_section_world: a block-value world as 16^3 palette sections, the form the reference
+    ingests (section_to_compacted_octree, new_octree.rs:712-750).  sections: _lib.SECTION_DTYPE rows; palette:
+    uint32 block values, 0 = air; indices: uint16, 4096 per index block, entry y<<8 | z<<4 | x."""
+    sections: np.ndarray
+    palette: np.ndarray
+    indices: np.ndarray
+    depth: int
+
+    def __post_init__(self):
+        self.sections = np.ascontiguousarray(self.sections, _lib.SECTION_DTYPE).reshape(-1)
+        self.palette = np.ascontiguousarray(self.palette, np.uint32).reshape(-1)
+        self.indices = np.ascontiguousarray(self.indices, np.uint16).reshape(-1)
+
+    @property
+    def nbytes(self) -> int:
+        """bytes of the three arrays (what a build from host arrays uploads)"""
+        return self.sections.nbytes + self.palette.nbytes + self.indices.nbytes
+
+    def struct(self, pointers=None) -> "_lib.SectionWorld":
+        """octpt_section_world over the numpy arrays (keep `self` alive), or over `pointers` = (sections,
+        palette, indices) device addresses of copies of them (OCTPT_BUILD_SECTIONS_ON_DEVICE)."""
+        ptr = pointers if pointers is not None else [a.ctypes.data if len(a) else None
+                                                     for a in (self.sections, self.palette, self.indices)]
+        return _lib.SectionWorld(ptr[0], len(self.sections), ptr[1], len(self.palette), ptr[2], len(self.indices))
+
+    @staticmethod
+    def from_cells(cells, depth: int, uniform: bool = True) -> "SectionWorld":
+        """Pack (n, 4) cells (x, y, z, block != 0) into sections: one palette slice per section (its sorted
+        distinct values, a leading 0 where the section has air) and one index block, or with `uniform`
+        OCTPT_SECTION_UNIFORM for a full section of a single value."""
+        c = np.ascontiguousarray(cells, np.uint32).reshape(-1, 4)
+        if len(c) and int(c[:, 3].min()) == 0:
+            raise ValueError("block 0 is air in a section world")
+        sx, sy, sz = (c[:, a].astype(np.uint64) >> np.uint64(4) for a in range(3))
+        key = (sx << np.uint64(40)) | (sy << np.uint64(20)) | sz
+        order = np.argsort(key, kind="stable")
+        c, key = c[order], key[order]
+        ukey, start = np.unique(key, return_index=True)
+        bounds = np.append(start, len(c))
+        sections = np.zeros(len(ukey), _lib.SECTION_DTYPE)
+        sections["x"] = ukey >> np.uint64(40)
+        sections["y"] = (ukey >> np.uint64(20)) & np.uint64(0xFFFFF)
+        sections["z"] = ukey & np.uint64(0xFFFFF)
+        palette, index_blocks = [], []
+        n_pal = 0
+        for s in range(len(ukey)):
+            rows = c[bounds[s]:bounds[s + 1]]
+            full = len(rows) == 4096
+            vals = rows[:1, 3] if full and rows[:, 3].min() == rows[:, 3].max() else np.unique(rows[:, 3])
+            pal = vals if full else np.concatenate([np.zeros(1, np.uint32), vals])
+            sections["palette_first"][s], sections["palette_count"][s] = n_pal, len(pal)
+            palette.append(pal)
+            n_pal += len(pal)
+            if uniform and full and len(vals) == 1:
+                sections["index_first"][s] = _lib.SECTION_UNIFORM
+                continue
+            block = np.zeros(4096, np.uint16)
+            local = rows[:, :3] & 15
+            block[(local[:, 1] << 8) | (local[:, 2] << 4) | local[:, 0]] = np.searchsorted(pal, rows[:, 3])
+            sections["index_first"][s] = 4096 * len(index_blocks)
+            index_blocks.append(block)
+        return SectionWorld(sections, np.concatenate(palette) if palette else np.zeros(0, np.uint32),
+                            np.concatenate(index_blocks) if index_blocks else np.zeros(0, np.uint16), depth)
+
+    def to_cells(self) -> np.ndarray:
+        """octpt_sections_to_cells: the (n, 4) cells of the world in Morton order."""
+        lib = _lib.load()
+        w, n = self.struct(), C.c_uint32()
+        _lib.check(lib, None, lib.octpt_sections_to_cells(C.byref(w), self.depth, None, 0, C.byref(n)))
+        cells = np.zeros((n.value, 4), np.uint32)
+        if n.value:
+            _lib.check(lib, None, lib.octpt_sections_to_cells(C.byref(w), self.depth, cells.ctypes.data_as(C.c_void_p),
+                                                              n.value, C.byref(n)))
+        return cells
+
+
+@dataclass
 class Scene:
     """scene::Scene (scene/mod.rs:146-156): spheres and cuboids, plus block models (DESIGN.md C19):
     a cuboid whose cuboid_model entry is not MODEL_NONE is a block-model instance whose surface is
@@ -217,7 +295,8 @@ class Scene:
     cells: np.ndarray | None = None
 
     # ---------------------------------------------------------------- octree
-    def build_octree(self, depth: int, renderer=None, compact: bool = False, device_cells=None) -> Octree:
+    def build_octree(self, depth: int, renderer=None, compact: bool = False, device_cells=None,
+                     sections: "SectionWorld | None" = None, device_sections=None) -> Octree:
         """Voxelise the primitives with the product builder: octpt_build_octree (host), or with a
         HipRenderer given, octpt_build_octree_device on its GPU (the same arrays).  compact: merge
         eight sibling leaves holding the same primitive list, bottom-up (OCTPT_BUILD_COMPACT,
@@ -225,8 +304,13 @@ class Scene:
         cells with octpt_build_block_octree (compact: eight equal block values merge), or with a
         renderer given, octpt_build_block_octree_device; device_cells = (device pointer, cell count)
         then reads the cells from that renderer's GPU (OCTPT_BUILD_CELLS_ON_DEVICE; they must be
-        complete, e.g. after torch.cuda.synchronize()) instead of self.cells."""
+        complete, e.g. after torch.cuda.synchronize()) instead of self.cells.  sections: build from that
+        SectionWorld instead (octpt_build_block_octree_sections_device with a renderer, else the host builder
+        over its to_cells()); device_sections = (sections, palette, indices) device addresses of copies of
+        its arrays on the renderer's GPU (OCTPT_BUILD_SECTIONS_ON_DEVICE)."""
         lib = _lib.load()
+        if sections is not None:
+            return self._build_section_octree(lib, depth, compact, renderer, sections, device_sections)
         if device_cells is not None and (self.blocks is None or renderer is None):
             raise ValueError("device_cells: a block-value scene and a renderer are needed")
         if self.blocks is not None:
@@ -279,6 +363,10 @@ class Scene:
         else:
             _lib.check(lib, renderer._ctx,
                        lib.octpt_build_block_octree_device(renderer._ctx, ptr, n, depth, flags, C.byref(handle)))
+        return self._take_block_octree(lib, handle)
+
+    def _take_block_octree(self, lib, handle) -> Octree:
+        """self.octree = a copy of a block-value octree handle's octants; frees the handle."""
         try:
             v = _lib.OctreeView()
             _lib.check(lib, None, lib.octpt_octree_get_view(handle, C.byref(v)))
@@ -290,6 +378,36 @@ class Scene:
         finally:
             lib.octpt_octree_free(handle)
         return self.octree
+
+    def _build_section_octree(self, lib, depth: int, compact: bool, renderer, world, device_sections) -> Octree:
+        if self.blocks is None:
+            raise ValueError("sections: a block-value scene (scene.blocks) is needed")
+        if renderer is None:
+            if device_sections is not None:
+                raise ValueError("device_sections: a renderer is needed")
+            host = dataclasses_replace(self, cells=world.to_cells(), octree=None)
+            self.octree = host.build_octree(depth, compact=compact)
+            return self.octree
+        flags = (_lib.BUILD_COMPACT if compact else 0) | (_lib.BUILD_SECTIONS_ON_DEVICE if device_sections else 0)
+        w, handle = world.struct(device_sections), C.c_void_p()
+        _lib.check(lib, renderer._ctx, lib.octpt_build_block_octree_sections_device(renderer._ctx, C.byref(w), depth,
+                                                                                    flags, C.byref(handle)))
+        return self._take_block_octree(lib, handle)
+
+    def with_air_block(self) -> "Scene":
+        """A copy in the form a SectionWorld can carry: palette value 0 is air there, so the block table gains an
+        unused block 0 and every cell's block id is raised by one (block b becomes value b + 1)."""
+        blocks = np.asarray(self.blocks, np.uint32).reshape(-1, 6)
+        model = (np.asarray(self.block_model, np.uint32) if self.block_model is not None
+                 else np.full(len(blocks), _lib.MODEL_NONE, np.uint32))
+        cells = self.cells_array().copy()
+        cells[:, 3] += 1
+        out = dataclasses_replace(self, blocks=np.concatenate([np.zeros((1, 6), np.uint32), blocks]),
+                                  block_model=np.concatenate([np.full(1, _lib.MODEL_NONE, np.uint32), model]),
+                                  cells=cells, octree=None)
+        if hasattr(self, "_depth"):
+            out._depth = self._depth
+        return out
 
     def block_structs(self):
         """octpt_block rows of `blocks` / `block_model` (C23)."""

@@ -5,7 +5,12 @@ primitive upload and the result download) and the GPU time of the build kernels.
 Block-value configs (C5b, C5s) run the block legs instead: octpt_build_block_octree against
 octpt_build_block_octree_device (end to end: cell upload, build, octant download), the build kernels alone,
 and scene set-up through octpt_scene_build_blocks_device against the host build + octpt_scene_upload.  C5s is
-built compacted (as it is rendered), C5b not (nothing merges there)."""
+built compacted (as it is rendered), C5b not (nothing merges there).
+
+`--sections` runs the sections leg for them instead: the world packed once into a SectionWorld
+(outside the timed region), scene set-up through octpt_scene_build_sections_device from host arrays and from
+arrays on the device, against the cell path in the same run, the bytes each path uploads, and the build kernels'
+time -- with OCTPT_SECTION_LIB naming a -DOCTPT_SECTION_SORT build, also with the radix sort kept."""
 import ctypes as C
 import sys
 import time
@@ -83,12 +88,62 @@ def block_leg(name, sc, depth):
           f"octpt_scene_upload {tu * 1e3:.1f} ms ({tu / td:.1f}x)", flush=True)
 
 
-for name in sys.argv[1:] or ["C3", "C4", "C5", "C5b", "C5s"]:
+def section_leg(name, sc, depth):
+    import os
+
+    import numpy as np
+    import torch
+
+    compact = name.startswith("C5s")
+    sc = sc.with_air_block()  # palette value 0 is air: block b becomes value b + 1
+    cells = sc.cells_array()
+    t = time.perf_counter()
+    w = S.SectionWorld.from_cells(cells, depth)
+    uniform = int((w.sections["index_first"] == _lib.SECTION_UNIFORM).sum())
+    print(f"{name}: {len(cells)} cells in {len(w.sections)} sections ({uniform} uniform), {len(w.palette)} palette "
+          f"entries, packed in {time.perf_counter() - t:.1f} s (not timed below); uploads: cells {cells.nbytes / 1e6:.1f} MB, "
+          f"sections {w.nbytes / 1e6:.1f} MB ({cells.nbytes / w.nbytes:.1f}x fewer)", flush=True)
+    keep = [torch.as_tensor(a.view(np.uint8).copy(), device="cuda") for a in (w.sections, w.palette, w.indices)]
+    d_cells = torch.as_tensor(cells.view(np.int32), device="cuda")
+    torch.cuda.synchronize()
+    ptrs = tuple(k.data_ptr() for k in keep)
+    legs = {"cells, host array": lambda rr: rr.set_scene_built(sc, depth, compact=compact),
+            "cells, device array": lambda rr: rr.set_scene_built_cells(sc, depth, d_cells.data_ptr(), len(cells),
+                                                                       compact=compact),
+            "sections, host arrays": lambda rr: rr.set_scene_built_sections(sc, depth, w, compact=compact),
+            "sections, device arrays": lambda rr: rr.set_scene_built_sections(sc, depth, w, compact=compact,
+                                                                              on_device=ptrs)}
+    times = {}
+    for tag, fn in legs.items():
+        fn(r)  # warm: scratch and code objects
+        times[tag] = best_of(lambda: fn(r), 5)
+        kms = r.stats()["build_ms"]
+        times[tag + " kernels"] = kms
+        print(f"{name}: scene set-up from {tag}: {times[tag] * 1e3:.2f} ms (build kernels {kms:.2f} ms)", flush=True)
+    print(f"{name}: set-up from host arrays, sections against cells: {times['cells, host array'] / times['sections, host arrays']:.2f}x "
+          f"({(times['cells, host array'] - times['sections, host arrays']) * 1e3:.2f} ms less); from device arrays "
+          f"{times['cells, device array'] / times['sections, device arrays']:.2f}x; build kernels "
+          f"{times['cells, device array kernels'] / times['sections, device arrays kernels']:.2f}x", flush=True)
+    alt = os.environ.get("OCTPT_SECTION_LIB")
+    if alt:  # the A/B: the same front end followed by the cell build's radix sort
+        r2 = HipRenderer(0, lib_path=alt)
+        fn = legs["sections, device arrays"]
+        fn(r2)
+        t2 = best_of(lambda: fn(r2), 5)
+        print(f"{name}: sections, device arrays, with the radix sort kept (-DOCTPT_SECTION_SORT): {t2 * 1e3:.2f} ms "
+              f"(build kernels {r2.stats()['build_ms']:.2f} ms against {times['sections, device arrays kernels']:.2f} ms "
+              f"without)", flush=True)
+        r2.close()
+
+
+args = [a for a in sys.argv[1:] if a != "--sections"]
+sections = "--sections" in sys.argv[1:]
+for name in args or ["C3", "C4", "C5", "C5b", "C5s"]:
     print(f"{name}: generating the scene", flush=True)
     sc, _, _ = S.make_config(name, build=False)
     d = sc._depth
     if sc.blocks is not None:
-        block_leg(name, sc, d)
+        (section_leg if sections else block_leg)(name, sc, d)
         continue
     th = call(sc, d)
     tg = call(sc, d, r._ctx)

@@ -1,12 +1,16 @@
 #!/bin/bash
-# Registers, scratch and occupancy of the wavefront, preview, guide-buffer and denoise kernels as the compiler reports them (kernel-resource-usage
-# remarks): tools/resource_usage.sh [-DFLAG ...].  CPU only (a device-only compile of octpt_kernels.hip).
+# Registers, scratch, LDS and occupancy of the wavefront, preview, guide-buffer and denoise kernels (octpt_kernels.hip) and of the
+# section builder's count and emit kernels (octpt_build.hip) as the compiler reports them (kernel-resource-usage
+# remarks): tools/resource_usage.sh [-DFLAG ...].  CPU only (device-only compiles).
 cd "$(dirname "$0")/.."
 FLAGS=$(python3 -c "import __graft_entry__ as g; print(' '.join(f for f in g.HIPCC_FLAGS if f not in ('-shared', '-fPIC')))")
-/opt/rocm/bin/hipcc $FLAGS "$@" -c octree_pathtracing_amd/csrc/octpt_kernels.hip -o /tmp/octpt_res.o --offload-device-only \
+for SRC in octpt_kernels.hip octpt_build.hip; do
+/opt/rocm/bin/hipcc $FLAGS "$@" -c octree_pathtracing_amd/csrc/$SRC -o /tmp/octpt_res.o --offload-device-only \
     -Rpass-analysis=kernel-resource-usage 2>&1 | sed 's/ \[-Rpass-analysis=kernel-resource-usage\]//' | awk '
   /Function Name:/ {n = $NF}
   /remark:     VGPRs:/ {v = $NF}
   /remark:     TotalSGPRs: / {sg = $NF}
   /ScratchSize/ {sc = $NF}
-  /Occupancy/ {if (n ~ /extend|shade|seed|drain|beam|preview|gbuffer|atrous|denoise/) printf "%-70s VGPR %3s SGPR %3s scratch %3s occ %s\n", substr(n, 1, 70), v, sg, sc, $NF}'
+  /Occupancy/ {occ = $NF}
+  /LDS Size/ {if (n ~ /extend|shade|seed|drain|beam|preview|gbuffer|atrous|denoise|section_count|section_emit/) printf "%-70s VGPR %3s SGPR %3s scratch %3s LDS %5s occ %s\n", substr(n, 1, 70), v, sg, sc, $NF, occ}'
+done
