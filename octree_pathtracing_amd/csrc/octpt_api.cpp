@@ -3,7 +3,8 @@
 // Replaces the reference's wgpu backend (src/renderer/gpu_renderer.rs:151-702): scene
 // validation + upload (set_scene / create_pipeline), camera uniform construction
 // (render_frame :590-599), progressive render submission, FrameInFlight polling, and the
-// host octree builder for primitive scenes.  No CPU rendering path exists here.
+// device octree and scene build entries.  The host builders are in octpt_build_host.cpp.
+// No CPU rendering path exists here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,7 +39,6 @@ constexpr uint32_t kLookahead = OCTPT_LOOKAHEAD;    // host steering: iterations
 constexpr uint32_t kDefaultPool = 512u << 20;        // path slots in flight (124 B each: queues + path state)
 constexpr uint32_t kMaxPool = 1u << 30;              // the sun-sampling planes index 4 * pool slots in uint32
 constexpr uint32_t kMinPool = 1u << 20;              // floor of the out-of-memory fallback (halving)
-constexpr uint64_t kMaxBuildPairs = 1ull << 31;      // octree builder: (cell, primitive) pair cap
 constexpr uint32_t kDefaultRefill = 0;               // extend: idle lanes before a wave refills (0: adaptive)
 constexpr uint32_t kDefaultDrainRays = 4096;         // drain the chunk in one launch below this many queued rays
 
@@ -177,8 +177,6 @@ struct octpt_frame {
     uint8_t *h_rgba = nullptr;  // pinned
     bool delivered = false;
 };
-
-struct octpt_octree : octpt::BuiltOctree {};
 
 namespace {
 
@@ -1252,155 +1250,6 @@ void deliver(octpt_frame *f) {
     f->delivered = true;
 }
 
-// ---------------- builder ----------------
-uint64_t part_by_2(uint64_t v) {  // new_octree.rs:813-822
-    uint64_t x = v & 0x1fffff;
-    x = (x | x << 32) & 0x1f00000000ffffULL;
-    x = (x | x << 16) & 0x1f0000ff0000ffULL;
-    x = (x | x << 8) & 0x100f00f00f00f00fULL;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ULL;
-    x = (x | x << 2) & 0x1249249249249249ULL;
-    return x;
-}
-inline uint64_t morton(uint64_t x, uint64_t y, uint64_t z) { return (part_by_2(z) << 2) + (part_by_2(y) << 1) + part_by_2(x); }
-
-struct CellPrim {
-    uint64_t code;
-    uint32_t prim;
-    bool operator<(const CellPrim &o) const { return code != o.code ? code < o.code : prim < o.prim; }
-};
-
-// Pre-order octant emission.  node() returns the child its parent stores: an octant
-// id, or with compaction a leaf payload when the octant's eight children are leaves holding the same
-// primitive list (Octant::is_compactable, new_octree.rs:227-233, applied bottom-up at every level as
-// RegionOctreeBuilder::recursive_build does, :679-690: the octant becomes Lod(get_child(0))).  The
-// root is never merged away (a Lod root stays one octant of eight equal leaves, :534-545).
-struct Builder {
-    octpt_octree *t;
-    std::vector<uint64_t> leaf_code;
-    uint32_t depth;
-    bool compact;
-    struct Child {
-        bool leaf;
-        uint32_t v;
-    };
-    bool same_leaf(uint32_t a, uint32_t b) const {
-        const uint32_t n = t->leaf_count[a];
-        return n == t->leaf_count[b] &&
-               std::memcmp(&t->leaf_prims[t->leaf_first[a]], &t->leaf_prims[t->leaf_first[b]], n * sizeof(uint32_t)) == 0;
-    }
-    Child node(uint32_t level, uint32_t lo, uint32_t hi) {
-        const uint32_t id = (uint32_t)t->octants.size();
-        t->octants.push_back(octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
-        const uint32_t shift = 3 * (depth - 1 - level);
-        uint32_t a = lo;
-        for (uint32_t c = 0; c < 8; ++c) {
-            uint32_t b = a;
-            while (b < hi && ((leaf_code[b] >> shift) & 7u) == c) ++b;
-            if (b == a) continue;
-            if (level + 1 == depth) {
-                t->octants[id].child_mask |= (uint16_t)((1u << c) | (1u << (c + 8)));
-                t->octants[id].children[c] = a;
-            } else {
-                const Child ch = node(level + 1, a, b);
-                t->octants[id].child_mask |= (uint16_t)(ch.leaf ? ((1u << c) | (1u << (c + 8))) : (1u << c));
-                t->octants[id].children[c] = ch.v;
-            }
-            a = b;
-        }
-        if (compact && level > 0 && t->octants[id].child_mask == 0xFFFFu) {
-            const uint32_t *ch = t->octants[id].children;
-            bool same = true;
-            for (int k = 1; k < 8 && same; ++k) same = same_leaf(ch[0], ch[k]);
-            if (same) {  // all children are leaves: this octant is the last one emitted
-                const uint32_t v = ch[0];
-                t->octants.pop_back();
-                return Child{true, v};
-            }
-        }
-        return Child{false, id};
-    }
-};
-
-// Block-value octree (C23): leaf payloads are block ids.  Pre-order emission over the Morton-sorted
-// cells as Builder does; with compaction an octant whose eight children are leaves holding the same
-// block value becomes one leaf of its parent (Octant::is_compactable, new_octree.rs:227-233: all eight
-// leaf bits set and every child value equal -- the reference's rule for leaf children), bottom-up at
-// every level as SectionOctantBuilder::insert_child_and_compact / RegionOctreeBuilder::recursive_build
-// apply it (:688-709, 582-587).  The root stays an octant.
-struct BlockBuilder {
-    octpt_octree *t;
-    const std::vector<std::pair<uint64_t, uint32_t>> &cells;  // (Morton code, block), sorted
-    uint32_t depth;
-    bool compact;
-    struct Child {
-        bool leaf;
-        uint32_t v;
-    };
-    Child node(uint32_t level, size_t lo, size_t hi) {
-        const uint32_t id = (uint32_t)t->octants.size();
-        t->octants.push_back(octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
-        const uint32_t shift = 3 * (depth - 1 - level);
-        size_t a = lo;
-        for (uint32_t c = 0; c < 8; ++c) {
-            size_t b = a;
-            while (b < hi && ((cells[b].first >> shift) & 7u) == c) ++b;
-            if (b == a) continue;
-            Child ch{true, cells[a].second};
-            if (level + 1 < depth) ch = node(level + 1, a, b);
-            t->octants[id].child_mask |= (uint16_t)(ch.leaf ? ((1u << c) | (1u << (c + 8))) : (1u << c));
-            t->octants[id].children[c] = ch.v;
-            a = b;
-        }
-        if (compact && level > 0 && t->octants[id].child_mask == 0xFFFFu) {
-            const uint32_t *ch = t->octants[id].children;
-            bool same = true;
-            for (int k = 1; k < 8 && same; ++k) same = ch[k] == ch[0];
-            if (same) {  // eight equal leaves: this octant is the last one emitted
-                const uint32_t v = ch[0];
-                t->octants.pop_back();
-                return Child{true, v};
-            }
-        }
-        return Child{false, id};
-    }
-};
-
-inline int32_t clamp_cell(float f, int32_t hi) {
-    if (!(f >= 0.0f)) return 0;  // also NaN
-    if (f >= (float)hi) return hi;
-    return (int32_t)f;
-}
-
-// Upper bound of the (cell, primitive) pairs: the clamped bounding-box cells of every primitive.
-// Leaf tables index pairs with uint32, and a scene past 2^31 pairs (>= 32 GiB of pairs) is refused
-// up front rather than discovered by allocating until bad_alloc.  Cuboid cells span floor(min) ..
-// ceil(max) - 1: a face on an integer plane does not claim the next cell, so a unit block
-// [x, x+1) is exactly one cell (the voxel world of C5).
-uint64_t pair_bound(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid *cuboids, uint32_t nc,
-                    uint32_t depth) {
-    const int32_t N = 1 << depth;
-    uint64_t bound = 0;
-    auto cub_hi = [](float lo, float hi) { return std::max(floorf(lo), ceilf(hi) - 1.0f); };
-    auto add_box = [&](const float *lo_f, const float *hi_f, bool half_open) {
-        uint64_t cells = 1;
-        for (int a = 0; a < 3; ++a) {
-            const float fl = floorf(lo_f[a]), fh = half_open ? cub_hi(lo_f[a], hi_f[a]) : floorf(hi_f[a]);
-            if (fh < 0.0f || fl > (float)(N - 1) || hi_f[a] < lo_f[a]) return;
-            cells *= (uint64_t)(clamp_cell(fh, N - 1) - clamp_cell(fl, N - 1) + 1);
-        }
-        bound = std::min<uint64_t>(bound + cells, UINT64_MAX / 2);
-    };
-    for (uint32_t i = 0; i < ns; ++i) {
-        const float *c = spheres[i].center, r = spheres[i].radius;
-        if (!(r > 0.0f)) continue;
-        const float lo_f[3] = {c[0] - r, c[1] - r, c[2] - r}, hi_f[3] = {c[0] + r, c[1] + r, c[2] + r};
-        add_box(lo_f, hi_f, false);
-    }
-    for (uint32_t i = 0; i < nc; ++i) add_box(cuboids[i].min, cuboids[i].max, true);
-    return bound;
-}
-
 // what build_block_octree_gpu's error word says (kCellErr*): the cells octpt_build_block_octree refuses,
 // and for a scene a block id beyond its block table
 octpt_status cell_error(octpt_ctx *ctx, uint32_t errors) {
@@ -1417,16 +1266,6 @@ octpt_status cell_error(octpt_ctx *ctx, uint32_t errors) {
     if (errors & kCellErrPaletteIndex)
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "a section index is >= its palette_count");
     return fail(ctx, OCTPT_ERR_INVALID_ARG, "two cells at one position");
-}
-
-// the section world's own refusals before any array is read: 0, or the status (the three entries share it)
-octpt_status section_world_status(const octpt_section_world *w, uint32_t depth) {
-    if (!w || depth < 4 || depth > kMaxDepth) return OCTPT_ERR_INVALID_ARG;
-    if ((w->section_count && !w->sections) || (w->palette_size && !w->palette) || (w->index_count && !w->indices))
-        return OCTPT_ERR_INVALID_ARG;
-    if (w->index_count % 4096u) return OCTPT_ERR_INVALID_ARG;
-    if (w->section_count >= kMaxBuildPairs) return OCTPT_ERR_OOM;  // one block of threads per section
-    return OCTPT_OK;
 }
 
 // the argument checks the two device section builds share (after the NULL-context check and join_inflight)
@@ -1453,48 +1292,171 @@ octpt_status check_block_build_args(octpt_ctx *ctx, const uint32_t *cells, uint3
     return OCTPT_OK;
 }
 
-// the device scene of a block-value octree the builder left in the scratch (the two device block scene builds):
-// its octants packed into the node slots in place, the tables uploaded, as octpt_scene_upload makes it
-octpt_status pack_block_scene(octpt_ctx *ctx, const octpt_scene_desc *d, const DeviceOctree &t) {
-    octpt_status st = OCTPT_OK;
+// what a device builder returned, as the entry's status: `what` names the build in a HIP failure's message, too_many_msg
+// is the entry's own text for a world past the pair / cell cap
+octpt_status build_status(octpt_ctx *ctx, hipError_t e, uint32_t errors, bool too_many, const char *what,
+                          const char *too_many_msg) {
+    if (e != hipSuccess) return hip_fail(ctx, e, what);
+    if (errors) return cell_error(ctx, errors);
+    if (too_many) return fail(ctx, OCTPT_ERR_OOM, too_many_msg);
+    return OCTPT_OK;
+}
+
+// The three device builders behind their two kinds of entry: dev == nullptr downloads the octree into `out` (the
+// octpt_build_*_device entries), else it stays in the build scratch as *dev (the octpt_scene_build_*_device entries).
+// block_count: the scene's block table size, 0 = not checked.
+octpt_status run_prim_build(octpt_ctx *ctx, const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid *cuboids,
+                            uint32_t nc, uint32_t depth, uint32_t flags, BuiltOctree &out, DeviceOctree *dev,
+                            float &ms) {
+    bool too_many = false;
+    const hipError_t e = build_octree_gpu(ctx->stream, ctx->build_scratch, spheres, ns, cuboids, nc, depth,
+                                          (flags & OCTPT_BUILD_COMPACT) != 0, kMaxBuildPairs, out, too_many, &ms, dev);
+    // too many pairs reads as the device running out of memory does (hip_fail: the same status and text)
+    return build_status(ctx, e, 0u, too_many, "octree build", "octree build: out of memory");
+}
+
+octpt_status run_block_build(octpt_ctx *ctx, const uint32_t *cells, uint32_t n, uint32_t depth, uint32_t flags,
+                             uint32_t block_count, BuiltOctree &out, DeviceOctree *dev, float &ms) {
+    uint32_t errors = 0u;
+    const hipError_t e = build_block_octree_gpu(ctx->stream, ctx->build_scratch, cells, n,
+                                                (flags & OCTPT_BUILD_CELLS_ON_DEVICE) != 0, depth,
+                                                (flags & OCTPT_BUILD_COMPACT) != 0, block_count, out, errors, &ms, dev);
+    return build_status(ctx, e, errors, false, "block octree build", "");
+}
+
+octpt_status run_section_build(octpt_ctx *ctx, const octpt_section_world *world, uint32_t depth, uint32_t flags,
+                               uint32_t block_count, BuiltOctree &out, DeviceOctree *dev, float &ms) {
+    uint32_t errors = 0u;
+    bool too_many = false;
+    const hipError_t e = build_section_octree_gpu(ctx->stream, ctx->build_scratch, *world,
+                                                  (flags & OCTPT_BUILD_SECTIONS_ON_DEVICE) != 0, depth,
+                                                  (flags & OCTPT_BUILD_COMPACT) != 0, block_count, kMaxBuildPairs, out,
+                                                  errors, too_many, &ms, dev);
+    return build_status(ctx, e, errors, too_many, "section octree build", "more than 2^31 cells");
+}
+
+// The frame of the octpt_build_*_device entries after their argument checks: build(octree, ms) selects the device and
+// runs its builder into the new handle; `what` names the build in the messages.
+template <class Build>
+octpt_status build_octree_handle(octpt_ctx *ctx, octpt_octree **out, const char *what, Build build) {
+    try {
+        std::unique_ptr<octpt_octree> t(new octpt_octree());
+        float ms = 0.0f;
+        const octpt_status st = build(*t, ms);
+        if (st != OCTPT_OK) return st;
+        ctx->build_ms = ms;
+        *out = t.release();
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, std::string(what) + ": host out of memory");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, std::string("unexpected exception in ") + what);
+    }
+}
+
+void commit_scene(octpt_ctx *ctx, const DevScene &S) {
+    ctx->S = S;
+    ctx->has_scene = true;
+    ++ctx->scene_gen;
+}
+
+// a scene entry on a multi-device context: entry(child) makes a replica on every device entry
+template <class F>
+octpt_status scene_on_every_sub(octpt_ctx *ctx, F entry) {
+    ctx->has_scene = false;
+    const octpt_status st = for_each_sub(ctx, [&](size_t i) { return entry(ctx->sub[i]); });
+    ctx->has_scene = st == OCTPT_OK;
+    return st;
+}
+
+// The device scene of an octree the builder left in the scratch, either leaf kind: its octants packed into the node
+// slots in place, exactly as octpt_scene_upload packs them on the host (§5), and the tables uploaded.  A block-value
+// scene's primitive tables are the empty ones it has after octpt_scene_upload (one zeroed element each: its
+// primitive counts are 0).  Its slots need no table, so they are filled, and the root's mask read, before the
+// tables are allocated; a primitive scene's fill writes the tables and comes after them.
+octpt_status pack_device_scene(octpt_ctx *ctx, const octpt_scene_desc *d, const DeviceOctree &t) {
     if ((uint64_t)t.n_octants * 8u >= 0xFFFFFFF0ull)  // the u32 slot scan cannot wrap
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "octree too large for the device build (>= 2^29 octants)");
     uint32_t *d_base = nullptr, n_slots = 0;
     HIP_TRY(ctx, slot_bases_gpu(ctx->stream, ctx->build_scratch, t, &d_base, n_slots));
-    const std::vector<uint32_t> bflags = block_slot_flags(d);
-    DevScene S{};
-    uint2 *d_child;
-    HIP_TRY(ctx, upload<uint2>(ctx, nullptr, (size_t)n_slots + 8, &d_child));  // zeroed: + 8 tail slots
-    HIP_TRY(ctx, fill_block_scene_gpu(ctx->stream, ctx->build_scratch, t, d_base, bflags.data(), d->block_count,
-                                      d_child));
     uint16_t root_mask = 0;  // the root is octant 0 (pre-order), base 0
-    HIP_TRY(ctx, hipMemcpy(&root_mask, &t.octants[0].child_mask, sizeof root_mask, hipMemcpyDeviceToHost));
-    // the empty primitive tables a block-value scene has after octpt_scene_upload (one zeroed element each)
-    uint32_t *d_prims, *d_sph_mat, *d_cmat;
-    float4 *d_sph, *d_cmin;
-    float2 *d_cmax;
-    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_prims));
-    HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_sph));
-    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_sph_mat));
-    HIP_TRY(ctx, upload<float4>(ctx, nullptr, 0, &d_cmin));
-    HIP_TRY(ctx, upload<float2>(ctx, nullptr, 0, &d_cmax));
-    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, 0, &d_cmat));
-    S.node_child = d_child;
-    S.leaf_prims = d_prims;
-    S.spheres = d_sph;
-    S.sphere_mat = d_sph_mat;
-    S.cub_a = d_cmin;
-    S.cub_b = d_cmax;
-    S.cub_mat = d_cmat;
+    auto read_root_mask = [&] {
+        return hipMemcpy(&root_mask, &t.octants[0].child_mask, sizeof root_mask, hipMemcpyDeviceToHost);
+    };
+    ScenePrimTables out{};
+    HIP_TRY(ctx, upload<uint2>(ctx, nullptr, (size_t)n_slots + 8, &out.node_child));  // zeroed: + 8 tail slots
+    if (d->blocks) {
+        const std::vector<uint32_t> bflags = block_slot_flags(d);
+        HIP_TRY(ctx, fill_block_scene_gpu(ctx->stream, ctx->build_scratch, t, d_base, bflags.data(), d->block_count,
+                                          out.node_child));
+        HIP_TRY(ctx, read_root_mask());
+    } else if (!d->cuboid_count) {
+        HIP_TRY(ctx, upload<float4>(ctx, nullptr, (size_t)n_slots + 8, &out.leaf_sph));
+    }
+    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, t.n_leaf_prims, &out.leaf_prims));
+    HIP_TRY(ctx, upload<float4>(ctx, nullptr, d->sphere_count, &out.spheres));
+    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, d->sphere_count, &out.sphere_mat));
+    HIP_TRY(ctx, upload<float4>(ctx, nullptr, d->cuboid_count, &out.cub_a));
+    HIP_TRY(ctx, upload<float2>(ctx, nullptr, d->cuboid_count, &out.cub_b));
+    HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, (size_t)d->cuboid_count * 6, &out.cub_mat));
+    if (!d->blocks) {
+        HIP_TRY(ctx, fill_scene_gpu(ctx->stream, t, d_base, out));
+        HIP_TRY(ctx, read_root_mask());
+    }
+    DevScene S{};
+    S.node_child = out.node_child;
+    S.leaf_sph = out.leaf_sph;
+    S.leaf_prims = out.leaf_prims;
+    S.spheres = out.spheres;
+    S.sphere_mat = out.sphere_mat;
+    S.cub_a = out.cub_a;
+    S.cub_b = out.cub_b;
+    S.cub_mat = out.cub_mat;
     S.root = 0u;
     S.root_mask = root_mask;
     S.n_octants = t.n_octants;
-    st = upload_tables(ctx, d, false, S);
+    const octpt_status st = upload_tables(ctx, d, false, S);
     if (st != OCTPT_OK) return st;
-    ctx->S = S;
-    ctx->has_scene = true;
-    ++ctx->scene_gen;
+    commit_scene(ctx, S);
     return OCTPT_OK;
+}
+
+// The three octpt_scene_build_*_device entries after their argument checks.  blocks: the entry builds a block-value
+// scene, else a primitive one (whose pair bound can only be taken once the scene's tables are checked, so it is
+// refused here).  build(ctx, octree, ms) runs the entry's builder with its result left in the build scratch; on a
+// multi-device context every device entry runs it for its own replica.  `what` names the entry in the message of
+// an unexpected exception.
+template <class Build>
+octpt_status build_scene_device(octpt_ctx *ctx, const octpt_scene_desc *d, bool blocks, const char *what, Build build) {
+    try {
+        if (is_multi(ctx))
+            return scene_on_every_sub(ctx, [&](octpt_ctx *c) { return build_scene_device(c, d, blocks, what, build); });
+        octpt_status st = validate_head(ctx, d, false);
+        if (st != OCTPT_OK) return st;
+        if (blocks && !d->blocks)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "the block build needs the scene's block table (blocks is NULL)");
+        if (!blocks && d->blocks)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "a block-value scene is uploaded with its octree");
+        st = validate_tables(ctx, d);
+        if (st != OCTPT_OK) return st;
+        if (!blocks && pair_bound(d->spheres, d->sphere_count, d->cuboids, d->cuboid_count, d->depth) > kMaxBuildPairs)
+            return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 (cell, primitive) pairs");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        free_scene(ctx);
+        DeviceOctree t;
+        float ms = 0.0f;
+        st = build(ctx, t, ms);
+        if (st != OCTPT_OK) return st;
+        ctx->build_ms = ms;
+        return pack_device_scene(ctx, d, t);
+    } catch (const std::bad_alloc &) {
+        free_scene(ctx);
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
+    } catch (...) {
+        free_scene(ctx);
+        return fail(ctx, OCTPT_ERR_INTERNAL, std::string("unexpected exception in ") + what);
+    }
 }
 
 }  // namespace
@@ -1663,12 +1625,7 @@ octpt_status octpt_scene_upload(octpt_ctx *ctx, const octpt_scene_desc *d) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     join_inflight(ctx);
     try {
-        if (is_multi(ctx)) {  // a replica on every device entry
-            ctx->has_scene = false;
-            const octpt_status st = for_each_sub(ctx, [&](size_t i) { return octpt_scene_upload(ctx->sub[i], d); });
-            ctx->has_scene = st == OCTPT_OK;
-            return st;
-        }
+        if (is_multi(ctx)) return scene_on_every_sub(ctx, [&](octpt_ctx *c) { return octpt_scene_upload(c, d); });
         std::vector<uint16_t> masks;  // reader-form child masks (C21)
         octpt_status st = validate_scene(ctx, d, masks);
         if (st != OCTPT_OK) return st;
@@ -1740,9 +1697,7 @@ octpt_status octpt_scene_upload(octpt_ctx *ctx, const octpt_scene_desc *d) {
         S.n_octants = d->octant_count;
         st = upload_tables(ctx, d, true, S);
         if (st != OCTPT_OK) return st;
-        ctx->S = S;
-        ctx->has_scene = true;
-        ++ctx->scene_gen;
+        commit_scene(ctx, S);
         return OCTPT_OK;
     } catch (const std::bad_alloc &) {
         free_scene(ctx);
@@ -1757,123 +1712,23 @@ octpt_status octpt_scene_build_device(octpt_ctx *ctx, const octpt_scene_desc *d,
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     join_inflight(ctx);
     if (flags & ~OCTPT_BUILD_COMPACT) return fail(ctx, OCTPT_ERR_INVALID_ARG, "unknown build flags");
-    try {
-        if (is_multi(ctx)) {  // every device entry builds its own replica
-            ctx->has_scene = false;
-            const octpt_status st =
-                for_each_sub(ctx, [&](size_t i) { return octpt_scene_build_device(ctx->sub[i], d, flags); });
-            ctx->has_scene = st == OCTPT_OK;
-            return st;
-        }
-        octpt_status st = validate_head(ctx, d, false);
-        if (st != OCTPT_OK) return st;
-        if (d->blocks) return fail(ctx, OCTPT_ERR_INVALID_ARG, "a block-value scene is uploaded with its octree");
-        st = validate_tables(ctx, d);
-        if (st != OCTPT_OK) return st;
-        if (pair_bound(d->spheres, d->sphere_count, d->cuboids, d->cuboid_count, d->depth) > kMaxBuildPairs)
-            return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 (cell, primitive) pairs");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        free_scene(ctx);
-        // the GPU builder (§4) with its result left in the build scratch
+    return build_scene_device(ctx, d, false, "device scene build", [=](octpt_ctx *c, DeviceOctree &t, float &ms) {
         BuiltOctree unused;
-        DeviceOctree t;
-        bool too_many = false;
-        float ms = 0.0f;
-        hipError_t e = build_octree_gpu(ctx->stream, ctx->build_scratch, d->spheres, d->sphere_count, d->cuboids,
-                                        d->cuboid_count, d->depth, (flags & OCTPT_BUILD_COMPACT) != 0, kMaxBuildPairs,
-                                        unused, too_many, &ms, &t);
-        if (too_many) return fail(ctx, OCTPT_ERR_OOM, "octree build: out of memory");
-        if (e != hipSuccess) return hip_fail(ctx, e, "octree build");
-        ctx->build_ms = ms;
-        // sparse child slots packed on the device, exactly as octpt_scene_upload packs them (§5)
-        if ((uint64_t)t.n_octants * 8u >= 0xFFFFFFF0ull)  // the u32 slot scan cannot wrap
-            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "octree too large for the device build (>= 2^29 octants)");
-        uint32_t *d_base = nullptr, n_slots = 0;
-        HIP_TRY(ctx, slot_bases_gpu(ctx->stream, ctx->build_scratch, t, &d_base, n_slots));
-        ScenePrimTables out{};
-        HIP_TRY(ctx, upload<uint2>(ctx, nullptr, (size_t)n_slots + 8, &out.node_child));  // zeroed: + 8 tail slots
-        if (!d->cuboid_count) HIP_TRY(ctx, upload<float4>(ctx, nullptr, (size_t)n_slots + 8, &out.leaf_sph));
-        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, t.n_leaf_prims, &out.leaf_prims));
-        HIP_TRY(ctx, upload<float4>(ctx, nullptr, d->sphere_count, &out.spheres));
-        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, d->sphere_count, &out.sphere_mat));
-        HIP_TRY(ctx, upload<float4>(ctx, nullptr, d->cuboid_count, &out.cub_a));
-        HIP_TRY(ctx, upload<float2>(ctx, nullptr, d->cuboid_count, &out.cub_b));
-        HIP_TRY(ctx, upload<uint32_t>(ctx, nullptr, (size_t)d->cuboid_count * 6, &out.cub_mat));
-        HIP_TRY(ctx, fill_scene_gpu(ctx->stream, t, d_base, out));
-        uint16_t root_mask = 0;  // the root is octant 0 (pre-order), base 0
-        HIP_TRY(ctx, hipMemcpy(&root_mask, &t.octants[0].child_mask, sizeof root_mask, hipMemcpyDeviceToHost));
-        DevScene S{};
-        S.node_child = out.node_child;
-        S.leaf_sph = out.leaf_sph;
-        S.leaf_prims = out.leaf_prims;
-        S.spheres = out.spheres;
-        S.sphere_mat = out.sphere_mat;
-        S.cub_a = out.cub_a;
-        S.cub_b = out.cub_b;
-        S.cub_mat = out.cub_mat;
-        S.root = 0u;
-        S.root_mask = root_mask;
-        S.n_octants = t.n_octants;
-        st = upload_tables(ctx, d, false, S);
-        if (st != OCTPT_OK) return st;
-        ctx->S = S;
-        ctx->has_scene = true;
-        ++ctx->scene_gen;
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        free_scene(ctx);
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
-    } catch (...) {
-        free_scene(ctx);
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device scene build");
-    }
+        return run_prim_build(c, d->spheres, d->sphere_count, d->cuboids, d->cuboid_count, d->depth, flags, unused, &t,
+                              ms);
+    });
 }
 
 octpt_status octpt_scene_build_blocks_device(octpt_ctx *ctx, const octpt_scene_desc *d, const uint32_t *cells,
                                              uint32_t cell_count, uint32_t flags) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     join_inflight(ctx);
-    octpt_status st = check_block_build_args(ctx, cells, cell_count, flags);
+    const octpt_status st = check_block_build_args(ctx, cells, cell_count, flags);
     if (st != OCTPT_OK) return st;
-    try {
-        if (is_multi(ctx)) {  // every device entry builds its own replica
-            ctx->has_scene = false;
-            st = for_each_sub(ctx, [&](size_t i) {
-                return octpt_scene_build_blocks_device(ctx->sub[i], d, cells, cell_count, flags);
-            });
-            ctx->has_scene = st == OCTPT_OK;
-            return st;
-        }
-        st = validate_head(ctx, d, false);
-        if (st != OCTPT_OK) return st;
-        if (!d->blocks)
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "the block build needs the scene's block table (blocks is NULL)");
-        st = validate_tables(ctx, d);
-        if (st != OCTPT_OK) return st;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        free_scene(ctx);
-        // the GPU block builder (§4) with its octants left in the build scratch
+    return build_scene_device(ctx, d, true, "device block scene build", [=](octpt_ctx *c, DeviceOctree &t, float &ms) {
         BuiltOctree unused;
-        DeviceOctree t;
-        uint32_t errors = 0u;
-        float ms = 0.0f;
-        const hipError_t e = build_block_octree_gpu(ctx->stream, ctx->build_scratch, cells, cell_count,
-                                                    (flags & OCTPT_BUILD_CELLS_ON_DEVICE) != 0, d->depth,
-                                                    (flags & OCTPT_BUILD_COMPACT) != 0, d->block_count, unused, errors,
-                                                    &ms, &t);
-        if (e != hipSuccess) return hip_fail(ctx, e, "block octree build");
-        if (errors) return cell_error(ctx, errors);
-        ctx->build_ms = ms;
-        return pack_block_scene(ctx, d, t);
-    } catch (const std::bad_alloc &) {
-        free_scene(ctx);
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
-    } catch (...) {
-        free_scene(ctx);
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device block scene build");
-    }
+        return run_block_build(c, cells, cell_count, d->depth, flags, d->block_count, unused, &t, ms);
+    });
 }
 
 octpt_status octpt_scene_build_sections_device(octpt_ctx *ctx, const octpt_scene_desc *d,
@@ -1881,48 +1736,12 @@ octpt_status octpt_scene_build_sections_device(octpt_ctx *ctx, const octpt_scene
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     join_inflight(ctx);
     if (!d) return fail(ctx, OCTPT_ERR_INVALID_ARG, "scene NULL");
-    octpt_status st = check_section_build_args(ctx, world, d->depth, flags);
+    const octpt_status st = check_section_build_args(ctx, world, d->depth, flags);
     if (st != OCTPT_OK) return st;
-    try {
-        if (is_multi(ctx)) {  // every device entry builds its own replica
-            ctx->has_scene = false;
-            st = for_each_sub(ctx, [&](size_t i) {
-                return octpt_scene_build_sections_device(ctx->sub[i], d, world, flags);
-            });
-            ctx->has_scene = st == OCTPT_OK;
-            return st;
-        }
-        st = validate_head(ctx, d, false);
-        if (st != OCTPT_OK) return st;
-        if (!d->blocks)
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "the block build needs the scene's block table (blocks is NULL)");
-        st = validate_tables(ctx, d);
-        if (st != OCTPT_OK) return st;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        free_scene(ctx);
-        // the GPU section builder (§4) with its octants left in the build scratch
+    return build_scene_device(ctx, d, true, "device section scene build", [=](octpt_ctx *c, DeviceOctree &t, float &ms) {
         BuiltOctree unused;
-        DeviceOctree t;
-        uint32_t errors = 0u;
-        bool too_many = false;
-        float ms = 0.0f;
-        const hipError_t e = build_section_octree_gpu(ctx->stream, ctx->build_scratch, *world,
-                                                      (flags & OCTPT_BUILD_SECTIONS_ON_DEVICE) != 0, d->depth,
-                                                      (flags & OCTPT_BUILD_COMPACT) != 0, d->block_count, kMaxBuildPairs,
-                                                      unused, errors, too_many, &ms, &t);
-        if (e != hipSuccess) return hip_fail(ctx, e, "section octree build");
-        if (errors) return cell_error(ctx, errors);
-        if (too_many) return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 cells");
-        ctx->build_ms = ms;
-        return pack_block_scene(ctx, d, t);
-    } catch (const std::bad_alloc &) {
-        free_scene(ctx);
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
-    } catch (...) {
-        free_scene(ctx);
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in device section scene build");
-    }
+        return run_section_build(c, world, d->depth, flags, d->block_count, unused, &t, ms);
+    });
 }
 
 octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
@@ -2654,147 +2473,13 @@ octpt_status octpt_build_octree_device_ex(octpt_ctx *ctx, const octpt_sphere *sp
     *out = nullptr;
     if (depth < 1 || depth > kMaxDepth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "depth must be in [1, 21]");
     if ((ns && !spheres) || (nc && !cuboids)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "NULL primitive array");
-    try {
+    return build_octree_handle(ctx, out, "octree build", [=](BuiltOctree &t, float &ms) {
         join_inflight(ctx);
         if (pair_bound(spheres, ns, cuboids, nc, depth) > kMaxBuildPairs)
             return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 (cell, primitive) pairs");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        octpt_octree *t = new octpt_octree();
-        bool too_many = false;
-        float ms = 0.0f;
-        const hipError_t e = build_octree_gpu(ctx->stream, ctx->build_scratch, spheres, ns, cuboids, nc, depth,
-                                              (flags & OCTPT_BUILD_COMPACT) != 0, kMaxBuildPairs, *t, too_many, &ms);
-        if (e != hipSuccess || too_many) {
-            delete t;
-            if (e == hipErrorOutOfMemory || too_many) return fail(ctx, OCTPT_ERR_OOM, "octree build: out of memory");
-            return hip_fail(ctx, e, "octree build");
-        }
-        ctx->build_ms = ms;
-        *out = t;
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "octree build: host out of memory");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in octree build");
-    }
-}
-
-octpt_status octpt_build_octree(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid *cuboids, uint32_t nc,
-                                uint32_t depth, octpt_octree **out) {
-    return octpt_build_octree_ex(spheres, ns, cuboids, nc, depth, 0u, out);
-}
-
-octpt_status octpt_build_octree_ex(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid *cuboids, uint32_t nc,
-                                   uint32_t depth, uint32_t flags, octpt_octree **out) {
-    if (!out) return OCTPT_ERR_INVALID_ARG;
-    if (flags & ~OCTPT_BUILD_COMPACT) return OCTPT_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (depth < 1 || depth > kMaxDepth) return OCTPT_ERR_INVALID_ARG;
-    if ((ns && !spheres) || (nc && !cuboids)) return OCTPT_ERR_INVALID_ARG;
-    try {
-        const int32_t N = 1 << depth;
-        const uint64_t bound = pair_bound(spheres, ns, cuboids, nc, depth);
-        if (bound > kMaxBuildPairs) return OCTPT_ERR_OOM;
-        // cuboid cells are half-open at the top (pair_bound)
-        auto cub_hi = [](float lo, float hi) { return std::max(floorf(lo), ceilf(hi) - 1.0f); };
-        std::vector<CellPrim> cells;
-        cells.reserve((size_t)std::min<uint64_t>(bound, 1ull << 24));
-        for (uint32_t i = 0; i < ns; ++i) {
-            const float *c = spheres[i].center;
-            const float r = spheres[i].radius;
-            if (!(r > 0.0f)) continue;
-            int32_t lo[3], hi[3];
-            bool empty = false;
-            for (int a = 0; a < 3; ++a) {
-                const float fl = floorf(c[a] - r), fh = floorf(c[a] + r);
-                if (fh < 0.0f || fl > (float)(N - 1)) empty = true;
-                lo[a] = clamp_cell(fl, N - 1);
-                hi[a] = clamp_cell(fh, N - 1);
-            }
-            if (empty) continue;
-            const float r2 = r * r;
-            for (int32_t z = lo[2]; z <= hi[2]; ++z)
-                for (int32_t y = lo[1]; y <= hi[1]; ++y)
-                    for (int32_t x = lo[0]; x <= hi[0]; ++x) {
-                        const float bl[3] = {(float)x, (float)y, (float)z};
-                        float dd[3];
-                        for (int a = 0; a < 3; ++a) {
-                            const float l = bl[a], h = bl[a] + 1.0f;
-                            dd[a] = c[a] < l ? l - c[a] : (c[a] > h ? c[a] - h : 0.0f);
-                        }
-                        if ((dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2] <= r2)
-                            cells.push_back(CellPrim{morton((uint64_t)x, (uint64_t)y, (uint64_t)z), i});
-                    }
-        }
-        for (uint32_t i = 0; i < nc; ++i) {
-            const octpt_cuboid &b = cuboids[i];
-            int32_t lo[3], hi[3];
-            bool empty = false;
-            for (int a = 0; a < 3; ++a) {
-                const float fl = floorf(b.min[a]), fh = cub_hi(b.min[a], b.max[a]);
-                if (fh < 0.0f || fl > (float)(N - 1) || b.max[a] < b.min[a]) empty = true;
-                lo[a] = clamp_cell(fl, N - 1);
-                hi[a] = clamp_cell(fh, N - 1);
-            }
-            if (empty) continue;
-            for (int32_t z = lo[2]; z <= hi[2]; ++z)
-                for (int32_t y = lo[1]; y <= hi[1]; ++y)
-                    for (int32_t x = lo[0]; x <= hi[0]; ++x)
-                        cells.push_back(CellPrim{morton((uint64_t)x, (uint64_t)y, (uint64_t)z), i | kPrimCuboidBit});
-        }
-        std::sort(cells.begin(), cells.end());
-        octpt_octree *t = new octpt_octree();
-        t->depth = depth;
-        std::vector<uint64_t> codes;
-        t->leaf_prims.resize(cells.size());
-        for (size_t k = 0; k < cells.size(); ++k) {
-            if (k == 0 || cells[k].code != cells[k - 1].code) {
-                t->leaf_first.push_back((uint32_t)k);
-                t->leaf_count.push_back(0);
-                codes.push_back(cells[k].code);
-            }
-            t->leaf_count.back()++;
-            t->leaf_prims[k] = cells[k].prim;
-        }
-        Builder b{t, std::move(codes), depth, (flags & OCTPT_BUILD_COMPACT) != 0};
-        t->root = b.node(0, 0, (uint32_t)b.leaf_code.size()).v;
-        *out = t;
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return OCTPT_ERR_OOM;
-    } catch (...) {
-        return OCTPT_ERR_INTERNAL;
-    }
-}
-
-octpt_status octpt_build_block_octree(const uint32_t *cells, uint32_t n, uint32_t depth, uint32_t flags,
-                                      octpt_octree **out) {
-    if (!out) return OCTPT_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (flags & ~OCTPT_BUILD_COMPACT) return OCTPT_ERR_INVALID_ARG;
-    if (depth < 1 || depth > kMaxDepth || (n && !cells)) return OCTPT_ERR_INVALID_ARG;
-    try {
-        const uint32_t N = 1u << depth;
-        std::vector<std::pair<uint64_t, uint32_t>> sorted(n);
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t *c = cells + 4 * (size_t)k;
-            if (c[0] >= N || c[1] >= N || c[2] >= N || c[3] > kPrimIndexMask) return OCTPT_ERR_INVALID_ARG;
-            sorted[k] = {morton(c[0], c[1], c[2]), c[3]};
-        }
-        std::sort(sorted.begin(), sorted.end());
-        for (size_t k = 1; k < sorted.size(); ++k)
-            if (sorted[k].first == sorted[k - 1].first) return OCTPT_ERR_INVALID_ARG;  // two blocks in one cell
-        std::unique_ptr<octpt_octree> t(new octpt_octree());
-        t->depth = depth;
-        BlockBuilder b{t.get(), sorted, depth, (flags & OCTPT_BUILD_COMPACT) != 0};
-        t->root = b.node(0, 0, sorted.size()).v;
-        *out = t.release();
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return OCTPT_ERR_OOM;
-    } catch (...) {
-        return OCTPT_ERR_INTERNAL;
-    }
+        return run_prim_build(ctx, spheres, ns, cuboids, nc, depth, flags, t, nullptr, ms);
+    });
 }
 
 octpt_status octpt_build_block_octree_device(octpt_ctx *ctx, const uint32_t *cells, uint32_t n, uint32_t depth,
@@ -2806,94 +2491,10 @@ octpt_status octpt_build_block_octree_device(octpt_ctx *ctx, const uint32_t *cel
     if (depth < 1 || depth > kMaxDepth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "depth must be in [1, 21]");
     const octpt_status st = check_block_build_args(ctx, cells, n, flags);
     if (st != OCTPT_OK) return st;
-    try {
+    return build_octree_handle(ctx, out, "block octree build", [=](BuiltOctree &t, float &ms) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        std::unique_ptr<octpt_octree> t(new octpt_octree());
-        uint32_t errors = 0u;
-        float ms = 0.0f;
-        const hipError_t e = build_block_octree_gpu(ctx->stream, ctx->build_scratch, cells, n,
-                                                    (flags & OCTPT_BUILD_CELLS_ON_DEVICE) != 0, depth,
-                                                    (flags & OCTPT_BUILD_COMPACT) != 0, 0u, *t, errors, &ms);
-        if (e != hipSuccess) return hip_fail(ctx, e, "block octree build");
-        if (errors) return cell_error(ctx, errors);
-        ctx->build_ms = ms;
-        *out = t.release();
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "block octree build: host out of memory");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in block octree build");
-    }
-}
-
-octpt_status octpt_sections_to_cells(const octpt_section_world *w, uint32_t depth, uint32_t *cells, uint32_t capacity,
-                                     uint32_t *count) {
-    if (!count) return OCTPT_ERR_INVALID_ARG;
-    *count = 0u;
-    const octpt_status st = section_world_status(w, depth);
-    if (st != OCTPT_OK) return st;
-    try {
-        // validate and count: sections in ascending Morton code of their coordinates
-        std::vector<std::pair<uint64_t, uint32_t>> order(w->section_count);
-        uint64_t total = 0;
-        for (uint32_t s = 0; s < w->section_count; ++s) {
-            const octpt_section &sec = w->sections[s];
-            if ((sec.x | sec.y | sec.z) >> (depth - 4u)) return OCTPT_ERR_INVALID_ARG;
-            if (sec.palette_count == 0u || sec.palette_count > 4096u ||
-                (uint64_t)sec.palette_first + sec.palette_count > w->palette_size)
-                return OCTPT_ERR_INVALID_ARG;
-            const uint32_t *pal = w->palette + sec.palette_first;
-            for (uint32_t i = 0; i < sec.palette_count; ++i)
-                if (pal[i] > kPrimIndexMask) return OCTPT_ERR_INVALID_ARG;
-            if (sec.index_first == OCTPT_SECTION_UNIFORM) {
-                if (sec.palette_count != 1u) return OCTPT_ERR_INVALID_ARG;
-                total += pal[0] ? 4096u : 0u;
-            } else {
-                if ((sec.index_first & 4095u) || (uint64_t)sec.index_first + 4096u > w->index_count)
-                    return OCTPT_ERR_INVALID_ARG;
-                const uint16_t *idx = w->indices + sec.index_first;
-                for (uint32_t i = 0; i < 4096u; ++i) {
-                    if (idx[i] >= sec.palette_count) return OCTPT_ERR_INVALID_ARG;
-                    total += pal[idx[i]] ? 1u : 0u;
-                }
-            }
-            order[s] = {morton(sec.x, sec.y, sec.z), s};
-        }
-        std::sort(order.begin(), order.end());
-        for (size_t k = 1; k < order.size(); ++k)
-            if (order[k].first == order[k - 1].first) return OCTPT_ERR_INVALID_ARG;  // two sections at one position
-        if (total > kMaxBuildPairs) return OCTPT_ERR_OOM;
-        *count = (uint32_t)total;
-        if (!cells) return OCTPT_OK;
-        if (capacity < total) return OCTPT_ERR_INVALID_ARG;
-        uint32_t *out = cells;
-        for (const auto &ks : order) {
-            const octpt_section &sec = w->sections[ks.second];
-            const uint32_t *pal = w->palette + sec.palette_first;
-            const bool uniform = sec.index_first == OCTPT_SECTION_UNIFORM;
-            const uint16_t *idx = uniform ? nullptr : w->indices + sec.index_first;
-            for (uint32_t m = 0; m < 4096u; ++m) {  // local Morton order: x bit 0, y bit 1, z bit 2 per level
-                uint32_t x = 0, y = 0, z = 0;
-                for (uint32_t b = 0; b < 4u; ++b) {
-                    x |= ((m >> (3u * b)) & 1u) << b;
-                    y |= ((m >> (3u * b + 1u)) & 1u) << b;
-                    z |= ((m >> (3u * b + 2u)) & 1u) << b;
-                }
-                const uint32_t v = uniform ? pal[0] : pal[idx[y << 8 | z << 4 | x]];
-                if (!v) continue;
-                out[0] = 16u * sec.x + x;
-                out[1] = 16u * sec.y + y;
-                out[2] = 16u * sec.z + z;
-                out[3] = v;
-                out += 4;
-            }
-        }
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return OCTPT_ERR_OOM;
-    } catch (...) {
-        return OCTPT_ERR_INTERNAL;
-    }
+        return run_block_build(ctx, cells, n, depth, flags, 0u, t, nullptr, ms);
+    });
 }
 
 octpt_status octpt_build_block_octree_sections_device(octpt_ctx *ctx, const octpt_section_world *world, uint32_t depth,
@@ -2904,43 +2505,10 @@ octpt_status octpt_build_block_octree_sections_device(octpt_ctx *ctx, const octp
     *out = nullptr;
     const octpt_status st = check_section_build_args(ctx, world, depth, flags);
     if (st != OCTPT_OK) return st;
-    try {
+    return build_octree_handle(ctx, out, "section octree build", [=](BuiltOctree &t, float &ms) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        std::unique_ptr<octpt_octree> t(new octpt_octree());
-        uint32_t errors = 0u;
-        bool too_many = false;
-        float ms = 0.0f;
-        const hipError_t e = build_section_octree_gpu(ctx->stream, ctx->build_scratch, *world,
-                                                      (flags & OCTPT_BUILD_SECTIONS_ON_DEVICE) != 0, depth,
-                                                      (flags & OCTPT_BUILD_COMPACT) != 0, 0u, kMaxBuildPairs, *t, errors,
-                                                      too_many, &ms);
-        if (e != hipSuccess) return hip_fail(ctx, e, "section octree build");
-        if (errors) return cell_error(ctx, errors);
-        if (too_many) return fail(ctx, OCTPT_ERR_OOM, "more than 2^31 cells");
-        ctx->build_ms = ms;
-        *out = t.release();
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "section octree build: host out of memory");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in section octree build");
-    }
+        return run_section_build(ctx, world, depth, flags, 0u, t, nullptr, ms);
+    });
 }
-
-octpt_status octpt_octree_get_view(const octpt_octree *t, octpt_octree_view *v) {
-    if (!t || !v) return OCTPT_ERR_INVALID_ARG;
-    v->octants = t->octants.data();
-    v->octant_count = (uint32_t)t->octants.size();
-    v->root = t->root;
-    v->depth = t->depth;
-    v->leaf_first = t->leaf_first.data();
-    v->leaf_count = t->leaf_count.data();
-    v->leaf_table_size = (uint32_t)t->leaf_first.size();
-    v->leaf_prims = t->leaf_prims.data();
-    v->leaf_prim_count = (uint32_t)t->leaf_prims.size();
-    return OCTPT_OK;
-}
-
-void octpt_octree_free(octpt_octree *t) { delete t; }
 
 }  // extern "C"

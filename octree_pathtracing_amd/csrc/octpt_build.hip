@@ -54,7 +54,7 @@ __device__ __forceinline__ int32_t clamp_cell(float f, int32_t hi) {
     return (int32_t)f;
 }
 
-// the host builder's per-primitive cell box (octpt_api.cpp octpt_build_octree); false = no cells
+// the host builder's per-primitive cell box (octpt_build_host.cpp octpt_build_octree); false = no cells
 __device__ inline bool prim_box(const octpt_sphere *sp, uint32_t ns, const octpt_cuboid *cb, uint32_t i, int32_t N,
                                 int32_t lo[3], int32_t hi[3]) {
     if (i < ns) {
@@ -516,15 +516,40 @@ __global__ __launch_bounds__(kBuildBlock) void pack_octants_kernel(const uint32_
 
 inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + kBuildBlock - 1) / kBuildBlock); }
 
-// slots of the context's grow-only scratch, taken in a fixed order per build
+// The slot map of the context's grow-only scratch (BuildScratch): a region is slots [first, end), and a cursor takes
+// its region's slots in a fixed order per build, so a rebuild finds every buffer where the last one left it.
+//   kBuildSlots    a builder's own buffers; its result (DeviceOctree) points into them until the next build.
+//                  build_octree_gpu takes up to 0..25.
+//   kCellSlots     the block-value builds' part of it: 0 the uploaded input, 1 the error word, 2..5 the (Morton code,
+//                  block) streams and their sorted copies, 6..8 the tail's scan, 9..16 the octants.  The section
+//                  build writes its streams sorted, so it takes 2 and 4 and leaves 3 and 5 unused: its large
+//                  buffers share the cell build's slots, and a context that builds both ways does not hold them
+//                  twice.
+//   kSectionSlots  the section build's per-section arrays (keys, ids, counts, offsets, their sort's storage)
+//   kBaseSlots     slot_bases_gpu: the scene packing's child counts, slot bases and scan storage
+//   kFlagSlots     fill_block_scene_gpu: the block table's slot flags
+// Slots 26 and 31 are free.  The packing regions lie past kBuildSlots because they are filled while the octree in
+// it is still read.
+struct SlotRegion {
+    int first, end;
+};
+constexpr SlotRegion kBuildSlots{0, 26}, kCellSlots{0, 17}, kSectionSlots{17, 25}, kBaseSlots{27, 30}, kFlagSlots{30, 31};
+static_assert(kCellSlots.end <= kSectionSlots.first && kSectionSlots.end <= kBuildSlots.end &&
+                  kBuildSlots.end <= kBaseSlots.first && kBaseSlots.end <= kFlagSlots.first &&
+                  kFlagSlots.end <= BuildScratch::kSlots,
+              "scratch regions that are live together do not overlap");
+
 struct ScratchCursor {
     BuildScratch &s;
-    int next = 0;  // a build takes at most slots 0..25 in a fixed order (the section build's per-section arrays
-                   // 17..24), slot_bases_gpu 27..29, the block flags 30
+    int next, end;
+    ScratchCursor(BuildScratch &scratch, SlotRegion r) : s(scratch), next(r.first), end(r.end) {}
+    // leaves n slots untaken, for a build that shares another's slot order but not all its buffers (the section
+    // build); not bounded itself: the next get() refuses a cursor that left its region
+    void skip(int n) { next += n; }
     template <class T>
     hipError_t get(T **ptr, size_t n) {
         const int k = next++;
-        if (k >= BuildScratch::kSlots) return hipErrorInvalidValue;
+        if (k >= end) return hipErrorInvalidValue;  // a buffer too many would alias the next region's
         const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
         if (s.cap[k] < bytes) {
             if (s.dev[k]) (void)hipFree(s.dev[k]);
@@ -548,8 +573,6 @@ struct ScratchCursor {
         if (_e != hipSuccess) return _e;           \
     } while (0)
 
-// Builds on `stream` and returns the host arrays of octpt_octree.  too_many = the pair count
-// exceeded max_pairs (nothing else is built then).
 void BuildScratch::release() {
     for (int k = 0; k < kSlots; ++k) {
         if (dev[k]) (void)hipFree(dev[k]);
@@ -616,8 +639,78 @@ hipError_t octants_gpu(hipStream_t stream, ScratchCursor &pool, const uint64_t *
     return hipSuccess;
 }
 
+// the two events a build's kernel time is taken between
+struct BuildEvents {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t create() {
+        const hipError_t e = hipEventCreate(&e0);
+        return e != hipSuccess ? e : hipEventCreate(&e1);
+    }
+    ~BuildEvents() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// The ways a build ends.  `t` is the builder's own record of what it has on the device; a build hands it out as
+// *dev (the arrays stay in the scratch), or with dev == nullptr downloads the arrays into `out`.
+// result_init: out's fields before the octants exist (no leaf tables until a primitive build downloads its own)
+void result_init(BuiltOctree &out, uint32_t depth) {
+    out.depth = depth;
+    out.root = 0u;
+    out.leaf_first.clear();
+    out.leaf_count.clear();
+    out.leaf_prims.clear();
+}
+
+// nothing to build from: a childless root, as the host builders emit
+hipError_t empty_root(hipStream_t stream, ScratchCursor &pool, DeviceOctree t, BuiltOctree &out, float *ms,
+                      DeviceOctree *dev) {
+    if (ms) *ms = 0.0f;
+    if (dev) {
+        octpt_octant *d_root;
+        BTRY(pool.get(&d_root, 1));
+        BTRY(hipMemsetAsync(d_root, 0, sizeof(octpt_octant), stream));
+        BTRY(hipStreamSynchronize(stream));
+        t.octants = d_root;
+        t.n_octants = 1u;
+        *dev = t;
+        return hipSuccess;
+    }
+    out.octants.assign(1, octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
+    return hipSuccess;
+}
+
+// the octants (and a primitive build's leaf tables) are built: the end of the timed region, the hand-over or the
+// download, one synchronisation, the kernel time
+hipError_t finish_build(hipStream_t stream, const BuildEvents &ev, const DeviceOctree &t, BuiltOctree &out, float *ms,
+                        DeviceOctree *dev) {
+    BTRY(hipEventRecord(ev.e1, stream));
+    if (dev) {
+        *dev = t;
+    } else {
+        out.octants.resize(t.n_octants);
+        out.leaf_first.resize(t.n_leaves);
+        out.leaf_count.resize(t.n_leaves);
+        out.leaf_prims.resize(t.n_leaf_prims);
+        BTRY(hipMemcpyAsync(out.octants.data(), t.octants, (size_t)t.n_octants * sizeof(octpt_octant),
+                            hipMemcpyDeviceToHost, stream));
+        if (t.n_leaves) {
+            BTRY(hipMemcpyAsync(out.leaf_first.data(), t.leaf_first, (size_t)t.n_leaves * 4, hipMemcpyDeviceToHost, stream));
+            BTRY(hipMemcpyAsync(out.leaf_count.data(), t.leaf_count, (size_t)t.n_leaves * 4, hipMemcpyDeviceToHost, stream));
+            BTRY(hipMemcpyAsync(out.leaf_prims.data(), t.leaf_prims, (size_t)t.n_leaf_prims * 4, hipMemcpyDeviceToHost,
+                                stream));
+        }
+    }
+    BTRY(hipStreamSynchronize(stream));
+    if (ms) BTRY(hipEventElapsedTime(ms, ev.e0, ev.e1));
+    return hipSuccess;
+}
+
 }  // namespace
 
+// Builds on `stream` into `out`, or leaves the arrays in the scratch as *dev.  too_many = the pair count exceeded
+// max_pairs (nothing else is built then).
 hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const octpt_sphere *spheres, uint32_t ns,
                             const octpt_cuboid *cuboids, uint32_t nc, uint32_t depth, bool compact,
                             uint64_t max_pairs, BuiltOctree &out, bool &too_many, float *ms,
@@ -625,14 +718,9 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     too_many = false;
     const int32_t N = 1 << depth;
     const uint32_t np = ns + nc;
-    ScratchCursor pool{scratch};
-    hipEvent_t e0, e1;
-    BTRY(hipEventCreate(&e0));
-    BTRY(hipEventCreate(&e1));
-    struct EvGuard {
-        hipEvent_t a, b;
-        ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    } evg{e0, e1};
+    ScratchCursor pool{scratch, kBuildSlots};
+    BuildEvents ev;
+    BTRY(ev.create());
     octpt_sphere *d_sp;
     octpt_cuboid *d_cb;
     unsigned long long *d_cnt, *d_off;
@@ -642,7 +730,7 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     BTRY(pool.get(&d_off, np + 1));
     if (ns) BTRY(hipMemcpyAsync(d_sp, spheres, ns * sizeof(octpt_sphere), hipMemcpyHostToDevice, stream));
     if (nc) BTRY(hipMemcpyAsync(d_cb, cuboids, nc * sizeof(octpt_cuboid), hipMemcpyHostToDevice, stream));
-    BTRY(hipEventRecord(e0, stream));
+    BTRY(hipEventRecord(ev.e0, stream));
     unsigned long long total = 0;
     if (np) {
         hipLaunchKernelGGL(count_cells_kernel, dim3(blocks(np)), dim3(kBuildBlock), 0, stream, d_sp, ns, d_cb, nc, N,
@@ -662,33 +750,14 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
         return hipSuccess;
     }
     const uint32_t n = (uint32_t)total;
-    out.depth = depth;
-    out.root = 0u;
-    if (dev) {
-        *dev = DeviceOctree{};
-        dev->spheres = d_sp;
-        dev->cuboids = d_cb;
-        dev->ns = ns;
-        dev->nc = nc;
-        dev->depth = depth;
-    }
-    if (n == 0u) {  // empty world: a childless root, as the host builder emits
-        if (ms) *ms = 0.0f;
-        if (dev) {
-            octpt_octant *d_root;
-            BTRY(pool.get(&d_root, 1));
-            BTRY(hipMemsetAsync(d_root, 0, sizeof(octpt_octant), stream));
-            BTRY(hipStreamSynchronize(stream));
-            dev->octants = d_root;
-            dev->n_octants = 1u;
-            return hipSuccess;
-        }
-        out.octants.assign(1, octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
-        out.leaf_first.clear();
-        out.leaf_count.clear();
-        out.leaf_prims.clear();
-        return hipSuccess;
-    }
+    result_init(out, depth);
+    DeviceOctree t;
+    t.spheres = d_sp;
+    t.cuboids = d_cb;
+    t.ns = ns;
+    t.nc = nc;
+    t.depth = depth;
+    if (n == 0u) return empty_root(stream, pool, t, out, ms, dev);  // empty world
     uint64_t *d_code, *d_code_s;
     uint32_t *d_prim, *d_prim_s, *d_head, *d_incl;
     BTRY(pool.get(&d_code, n));
@@ -740,75 +809,23 @@ hipError_t build_octree_gpu(hipStream_t stream, BuildScratch &scratch, const oct
     octpt_octant *d_oct;
     BTRY(octants_gpu<false>(stream, pool, d_lcode, d_base, d_opens, L, depth, compact, nullptr, d_first, d_count,
                             d_prim_s, n_oct, &d_oct));
-    BTRY(hipEventRecord(e1, stream));
-    if (dev) {  // device-resident: the arrays stay in the scratch
-        dev->octants = d_oct;
-        dev->leaf_first = d_first;
-        dev->leaf_count = d_count;
-        dev->leaf_prims = d_prim_s;
-        dev->n_octants = n_oct;
-        dev->n_leaves = L;
-        dev->n_leaf_prims = n;
-        BTRY(hipStreamSynchronize(stream));
-        if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
-        return hipSuccess;
-    }
-    out.octants.resize(n_oct);
-    out.leaf_first.resize(L);
-    out.leaf_count.resize(L);
-    out.leaf_prims.resize(n);
-    BTRY(hipMemcpyAsync(out.octants.data(), d_oct, (size_t)n_oct * sizeof(octpt_octant), hipMemcpyDeviceToHost,
-                        stream));
-    BTRY(hipMemcpyAsync(out.leaf_first.data(), d_first, (size_t)L * 4, hipMemcpyDeviceToHost, stream));
-    BTRY(hipMemcpyAsync(out.leaf_count.data(), d_count, (size_t)L * 4, hipMemcpyDeviceToHost, stream));
-    BTRY(hipMemcpyAsync(out.leaf_prims.data(), d_prim_s, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-    BTRY(hipStreamSynchronize(stream));
-    if (ms) BTRY(hipEventElapsedTime(ms, e0, e1));
-    return hipSuccess;
+    t.octants = d_oct;
+    t.leaf_first = d_first;
+    t.leaf_count = d_count;
+    t.leaf_prims = d_prim_s;
+    t.n_octants = n_oct;
+    t.n_leaves = L;
+    t.n_leaf_prims = n;
+    return finish_build(stream, ev, t, out, ms, dev);
 }
 
 namespace {
 
-// the two events a build's kernel time is taken between
-struct BuildEvents {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t create() {
-        const hipError_t e = hipEventCreate(&e0);
-        return e != hipSuccess ? e : hipEventCreate(&e1);
-    }
-    ~BuildEvents() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-};
-
-// a block-value build's result fields before the octants exist
-void block_result_init(BuiltOctree &out, DeviceOctree *dev, uint32_t depth) {
-    out.depth = depth;
-    out.root = 0u;
-    out.leaf_first.clear();
-    out.leaf_count.clear();
-    out.leaf_prims.clear();
-    if (dev) {
-        *dev = DeviceOctree{};
-        dev->depth = depth;
-    }
-}
-
-// no cells: a childless root, as the host builder emits
-hipError_t block_empty_root(hipStream_t stream, ScratchCursor &pool, BuiltOctree &out, float *ms, DeviceOctree *dev) {
-    if (ms) *ms = 0.0f;
-    if (dev) {
-        octpt_octant *d_root;
-        BTRY(pool.get(&d_root, 1));
-        BTRY(hipMemsetAsync(d_root, 0, sizeof(octpt_octant), stream));
-        BTRY(hipStreamSynchronize(stream));
-        dev->octants = d_root;
-        dev->n_octants = 1u;
-        return hipSuccess;
-    }
-    out.octants.assign(1, octpt_octant{0, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
-    return hipSuccess;
+// a block-value build's record of its result: no leaf tables, no primitives
+DeviceOctree block_tree(uint32_t depth) {
+    DeviceOctree t;
+    t.depth = depth;
+    return t;
 }
 
 // The tail of the block-value builds, from n >= 1 Morton-sorted (code, block) pairs: every cell is a leaf -- the
@@ -836,31 +853,20 @@ hipError_t block_tail_gpu(hipStream_t stream, ScratchCursor &pool, const BuildEv
     octpt_octant *d_oct;
     BTRY(octants_gpu<true>(stream, pool, d_code_s, d_base, d_opens, n, depth, compact, d_blk_s, nullptr, nullptr, nullptr,
                            n_oct, &d_oct));
-    BTRY(hipEventRecord(ev.e1, stream));
-    if (dev) {  // device-resident: the octants stay in the scratch
-        dev->octants = d_oct;
-        dev->n_octants = n_oct;
-        BTRY(hipStreamSynchronize(stream));
-        if (ms) BTRY(hipEventElapsedTime(ms, ev.e0, ev.e1));
-        return hipSuccess;
-    }
-    out.octants.resize(n_oct);
-    BTRY(hipMemcpyAsync(out.octants.data(), d_oct, (size_t)n_oct * sizeof(octpt_octant), hipMemcpyDeviceToHost,
-                        stream));
-    BTRY(hipStreamSynchronize(stream));
-    if (ms) BTRY(hipEventElapsedTime(ms, ev.e0, ev.e1));
-    return hipSuccess;
+    DeviceOctree t = block_tree(depth);
+    t.octants = d_oct;
+    t.n_octants = n_oct;
+    return finish_build(stream, ev, t, out, ms, dev);
 }
 
 }  // namespace
 
 // The block-value builder (octpt_internal.h): the cell front end -- emit and radix sort -- and block_tail_gpu.
-// Scratch slots in a fixed order like build_octree_gpu's, at most 0..16.
 hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, const uint32_t *cells, uint32_t n,
                                   bool cells_on_device, uint32_t depth, bool compact, uint32_t block_count,
                                   BuiltOctree &out, uint32_t &errors, float *ms, DeviceOctree *dev) {
     errors = 0u;
-    ScratchCursor pool{scratch};
+    ScratchCursor pool{scratch, kCellSlots};
     BuildEvents ev;
     BTRY(ev.create());
     uint32_t *d_cells, *d_err;
@@ -872,8 +878,8 @@ hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, con
         d_in = d_cells;
     }
     BTRY(hipEventRecord(ev.e0, stream));
-    block_result_init(out, dev, depth);
-    if (n == 0u) return block_empty_root(stream, pool, out, ms, dev);
+    result_init(out, depth);
+    if (n == 0u) return empty_root(stream, pool, block_tree(depth), out, ms, dev);
     uint64_t *d_code, *d_code_s;
     uint32_t *d_blk, *d_blk_s, *d_opens, *d_base;
     BTRY(pool.get(&d_code, n));
@@ -898,16 +904,15 @@ hipError_t build_block_octree_gpu(hipStream_t stream, BuildScratch &scratch, con
                           base_bytes, out, errors, ms, dev);
 }
 
-// The section front end (octpt_internal.h) and block_tail_gpu.  The large streams take the cell build's slots
-// (2 codes, 4 blocks, 6..8 the tail's scan, 9..16 the octants; 3 and 5 only with OCTPT_SECTION_SORT), so a context
-// that builds both ways does not hold them twice; the per-section arrays take slots 17..24.
+// The section front end (octpt_internal.h) and block_tail_gpu.  The streams come out of the emit sorted: running the
+// cell build's radix sort over them anyway was measured and rejected (tools/rejected/section_sort.patch).
 hipError_t build_section_octree_gpu(hipStream_t stream, BuildScratch &scratch, const octpt_section_world &world,
                                     bool on_device, uint32_t depth, bool compact, uint32_t block_count,
                                     uint64_t max_cells, BuiltOctree &out, uint32_t &errors, bool &too_many, float *ms,
                                     DeviceOctree *dev) {
     errors = 0u;
     too_many = false;
-    ScratchCursor pool{scratch}, small{scratch, 17};
+    ScratchCursor pool{scratch, kCellSlots}, small{scratch, kSectionSlots};
     BuildEvents ev;
     BTRY(ev.create());
     const uint32_t n_sec = world.section_count;
@@ -931,8 +936,8 @@ hipError_t build_section_octree_gpu(hipStream_t stream, BuildScratch &scratch, c
         d_idx = reinterpret_cast<const uint16_t *>(d_in + idx_at);
     }
     BTRY(hipEventRecord(ev.e0, stream));
-    block_result_init(out, dev, depth);
-    if (n_sec == 0u) return block_empty_root(stream, pool, out, ms, dev);
+    result_init(out, depth);
+    if (n_sec == 0u) return empty_root(stream, pool, block_tree(depth), out, ms, dev);
     // count, order
     uint64_t *d_key, *d_key_s;
     uint32_t *d_id, *d_id_s, *d_cnt;
@@ -977,38 +982,23 @@ hipError_t build_section_octree_gpu(hipStream_t stream, BuildScratch &scratch, c
         return hipSuccess;
     }
     const uint32_t n = (uint32_t)total;
-    if (n == 0u) return block_empty_root(stream, pool, out, ms, dev);  // every cell is air
-    // emit: the streams come out sorted
-    uint64_t *d_code, *d_code_s;
-    uint32_t *d_blk, *d_blk_s, *d_opens, *d_base;
-#ifdef OCTPT_SECTION_SORT
-    const size_t n_sorted = n;  // A/B: the cell build's radix sort over the emitted streams
-#else
-    const size_t n_sorted = 0;
-#endif
+    if (n == 0u) return empty_root(stream, pool, block_tree(depth), out, ms, dev);  // every cell is air
+    // emit: the streams come out sorted, in the slots of the cell build's unsorted ones (its sorted copies' stay free)
+    uint64_t *d_code;
+    uint32_t *d_blk, *d_opens, *d_base;
     BTRY(pool.get(&d_code, n));
-    BTRY(pool.get(&d_code_s, n_sorted));
+    pool.skip(1);
     BTRY(pool.get(&d_blk, n));
-    BTRY(pool.get(&d_blk_s, n_sorted));
+    pool.skip(1);
     BTRY(pool.get(&d_opens, (size_t)n + 1));  // entry n = 0: the exclusive scan's last input
     BTRY(pool.get(&d_base, (size_t)n + 1));
     hipLaunchKernelGGL(section_emit_kernel, dim3(n_sec), dim3(kBuildBlock), 0, stream, d_secs, d_pal, d_idx, aligned,
                        d_key_s, d_id_s, d_off, n, d_code, d_blk);
     BTRY(hipGetLastError());
-    size_t sort_bytes = 0, base_bytes = 0;
+    size_t base_bytes = 0;
     BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, base_bytes, d_opens, d_base, n + 1, stream));
-#ifdef OCTPT_SECTION_SORT
-    BTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
-                                            (int)(3u * depth), stream));
-#endif
     char *d_tmp;
-    BTRY(pool.get(&d_tmp, std::max(sort_bytes, base_bytes)));
-#ifdef OCTPT_SECTION_SORT
-    BTRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sort_bytes, d_code, d_code_s, d_blk, d_blk_s, n, 0,
-                                            (int)(3u * depth), stream));
-    std::swap(d_code, d_code_s);
-    std::swap(d_blk, d_blk_s);
-#endif
+    BTRY(pool.get(&d_tmp, base_bytes));
     return block_tail_gpu(stream, pool, ev, d_code, d_blk, n, depth, compact, d_err, d_opens, d_base, d_tmp, base_bytes,
                           out, errors, ms, dev);
 }
@@ -1102,7 +1092,7 @@ __global__ __launch_bounds__(kBuildBlock) void prim_tables_kernel(const octpt_sp
 
 hipError_t slot_bases_gpu(hipStream_t stream, BuildScratch &scratch, const DeviceOctree &t, uint32_t **d_base,
                           uint32_t &n_slots) {
-    ScratchCursor pool{scratch, 27};  // after the build's own slots (0..25)
+    ScratchCursor pool{scratch, kBaseSlots};
     const uint32_t n = t.n_octants;
     uint32_t *d_cnt;
     BTRY(pool.get(&d_cnt, n + 1));
@@ -1139,7 +1129,7 @@ hipError_t fill_scene_gpu(hipStream_t stream, const DeviceOctree &t, const uint3
 
 hipError_t fill_block_scene_gpu(hipStream_t stream, BuildScratch &scratch, const DeviceOctree &t,
                                 const uint32_t *d_base, const uint32_t *bflags, uint32_t n_blocks, uint2 *node_child) {
-    ScratchCursor pool{scratch, 30};  // after slot_bases_gpu's slots (27..29)
+    ScratchCursor pool{scratch, kFlagSlots};
     uint32_t *d_bflags;
     BTRY(pool.get(&d_bflags, n_blocks));
     BTRY(hipMemcpyAsync(d_bflags, bflags, (size_t)n_blocks * 4, hipMemcpyHostToDevice, stream));

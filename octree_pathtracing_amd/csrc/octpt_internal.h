@@ -24,6 +24,7 @@ constexpr uint32_t kBeamTile = OCTPT_BEAM_TILE;
 constexpr uint32_t kTile = 8;          // 8x8 pixel tiles = one wave64 of primary rays
 constexpr uint32_t kBlock = 256;       // threads per block (4 waves)
 constexpr uint32_t kMaxDepth = 21;     // new_octree.rs:14
+constexpr uint64_t kMaxBuildPairs = 1ull << 31;  // octree builders: (cell, primitive) pair / cell cap
 
 // GPUMaterial (gpu_material.rs:67-76) + the material's texture kind and, for colour
 // textures, the pre-converted F32Color (colors/mod.rs:280-288): 48 B, three float4 loads
@@ -371,6 +372,13 @@ struct BuiltOctree {
     uint32_t root = 0, depth = 0;
 };
 
+// what the host builders (octpt_build_host.cpp) and the device entries (octpt_api.cpp) share: the upper bound of a
+// primitive world's (cell, primitive) pairs, and a section world's own refusals before any array is read
+// (OCTPT_OK, or the status)
+uint64_t pair_bound(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid *cuboids, uint32_t nc,
+                    uint32_t depth);
+octpt_status section_world_status(const octpt_section_world *w, uint32_t depth);
+
 // grow-only device scratch of the GPU octree builder, owned by the context: repeated builds
 // (scene edits) reuse it instead of paying hipMalloc / hipFree per buffer
 struct BuildScratch {
@@ -452,3 +460,5 @@ hipError_t fill_block_scene_gpu(hipStream_t stream, BuildScratch &scratch, const
                                 const uint32_t *d_base, const uint32_t *bflags, uint32_t n_blocks, uint2 *node_child);
 
 }  // namespace octpt
+
+struct octpt_octree : octpt::BuiltOctree {};  // the C ABI's octree handle

@@ -10,7 +10,7 @@ built compacted (as it is rendered), C5b not (nothing merges there).
 `--sections` runs the sections leg for them instead: the world packed once into a SectionWorld
 (outside the timed region), scene set-up through octpt_scene_build_sections_device from host arrays and from
 arrays on the device, against the cell path in the same run, the bytes each path uploads, and the build kernels'
-time -- with OCTPT_SECTION_LIB naming a -DOCTPT_SECTION_SORT build, also with the radix sort kept."""
+time."""
 import ctypes as C
 import sys
 import time
@@ -89,8 +89,6 @@ def block_leg(name, sc, depth):
 
 
 def section_leg(name, sc, depth):
-    import os
-
     import numpy as np
     import torch
 
@@ -124,16 +122,6 @@ def section_leg(name, sc, depth):
           f"({(times['cells, host array'] - times['sections, host arrays']) * 1e3:.2f} ms less); from device arrays "
           f"{times['cells, device array'] / times['sections, device arrays']:.2f}x; build kernels "
           f"{times['cells, device array kernels'] / times['sections, device arrays kernels']:.2f}x", flush=True)
-    alt = os.environ.get("OCTPT_SECTION_LIB")
-    if alt:  # the A/B: the same front end followed by the cell build's radix sort
-        r2 = HipRenderer(0, lib_path=alt)
-        fn = legs["sections, device arrays"]
-        fn(r2)
-        t2 = best_of(lambda: fn(r2), 5)
-        print(f"{name}: sections, device arrays, with the radix sort kept (-DOCTPT_SECTION_SORT): {t2 * 1e3:.2f} ms "
-              f"(build kernels {r2.stats()['build_ms']:.2f} ms against {times['sections, device arrays kernels']:.2f} ms "
-              f"without)", flush=True)
-        r2.close()
 
 
 args = [a for a in sys.argv[1:] if a != "--sections"]

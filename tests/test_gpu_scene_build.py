@@ -97,3 +97,37 @@ def test_scene_build_device_timing(torch_cuda, renderer, name):
     host_ms = (time.perf_counter() - t0) * 1e3
     print(f"\n{name}: device-resident scene set-up {dev_ms:.1f} ms, device build + host round trip {host_ms:.1f} ms")
     assert dev_ms < host_ms * 1.2
+
+
+def test_primitive_cell_and_section_scene_builds_alternate(torch_cuda, renderer):
+    """A primitive scene, a cell scene and a section scene built in turn on one context share the scene-build
+    driver, the packing step and the context's scratch (every region of its slot map): after each build the
+    render is the one of the same scene uploaded with its host-built octree."""
+    import dataclasses
+
+    from octree_pathtracing_amd import scene as S
+
+    keys = STAT_KEYS + ("block_tests",)
+    tiny, tiny_cam, tiny_rs = S.make_config("tiny", build=False)
+    cells, cells_cam, cells_rs = S.make_config("blocks-b", build=False)
+    aired = cells.with_air_block()  # what a SectionWorld can carry: block b becomes value b + 1
+    world = S.SectionWorld.from_cells(aired.cells_array(), aired._depth)
+    shots = {"tiny": (tiny, tiny_cam, tiny_rs), "cells": (cells, cells_cam, cells_rs),
+             "sections": (aired, cells_cam, cells_rs)}
+    uploaded = {}
+    for tag, (sc, cam, rs) in shots.items():  # the reference side, once per scene
+        host = dataclasses.replace(sc)
+        host.build_octree(sc._depth, compact=True)
+        uploaded[tag] = gpu_render(torch_cuda, renderer, host, cam, rs)
+    assert uploaded["cells"][2]["block_tests"] > 0 and uploaded["tiny"][2]["sphere_tests"] > 0
+    for step, tag in enumerate(("tiny", "cells", "sections", "tiny", "cells")):
+        sc, cam, rs = shots[tag]
+        if tag == "sections":
+            renderer.set_scene_built_sections(sc, sc._depth, world, compact=True)
+        else:
+            renderer.set_scene_built(sc, sc._depth, compact=True)
+        a, b = gpu_render(torch_cuda, renderer, sc, cam, rs, upload=False), uploaded[tag]
+        assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), f"step {step} ({tag}): radiance"
+        assert np.array_equal(a[1], b[1]), f"step {step} ({tag}): segment counts"
+        for k in keys:
+            assert a[2][k] == b[2][k], (step, tag, k, a[2][k], b[2][k])
