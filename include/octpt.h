@@ -423,6 +423,55 @@ octpt_status octpt_denoise_device(octpt_ctx *ctx, const octpt_denoise_params *p,
 octpt_status octpt_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const float *color,
                            const octpt_aov_buffers *guides, float *out);
 
+/* --- temporal reprojection of the preview history across camera moves ---------- */
+/* The step between "render" and "filter" of an interactive frame: the previous call's accumulated colour is
+ * carried to where its surfaces are in the current frame and blended with the new low-spp colour under a
+ * per-pixel history length.  For a pixel with finite depth, the point it sees (C24's camera ray at its depth) is
+ * projected through the previous camera to (fx, fy) and the depth zp the previous frame would have stored; the
+ * four bilinear taps around (fx, fy) count when they lie in the image, had a hit and a history (length > 0),
+ * |depth - zp| <= depth_tolerance * zp, normal . normal >= normal_threshold and, with OCTPT_TEMPORAL_MATCH_PRIM,
+ * the same prim.  With counted weight >= 2^-10: h = their weighted mean, N = min(min length + 1, max_history),
+ * out.rgb = h + (color - h) / N, out_length = N.  Without: out = color, out_length = 1 (a disocclusion).  A miss
+ * (depth not finite): out = color, out_length = 0.  Alpha is copied. */
+#define OCTPT_TEMPORAL_MATCH_PRIM 0x1u
+typedef struct octpt_temporal_params {
+    uint32_t width, height;
+    octpt_camera camera;      /* the camera the current colour and guides were rendered with */
+    octpt_camera prev_camera; /* the history's; orthonormal: |dir.dir - 1|, |up.up - 1|, |dir.up| <= 1e-4 */
+    uint32_t max_history;     /* 1..65535: the blend is the running mean up to it, exponential from there on */
+    float depth_tolerance;    /* > 0, finite: relative */
+    float normal_threshold;   /* in [-1, 1] */
+    uint32_t flags;           /* OCTPT_TEMPORAL_MATCH_PRIM */
+} octpt_temporal_params;
+/* The previous call's output (color, length) with the guides it was made with.  width * height pixels each. */
+typedef struct octpt_temporal_history {
+    const float *color;     /* 4 floats / pixel */
+    const float *normal;    /* 4 floats / pixel */
+    const float *depth;
+    const uint32_t *prim;   /* required with OCTPT_TEMPORAL_MATCH_PRIM */
+    const uint32_t *length;
+} octpt_temporal_history;
+/* Device buffers, full frames only.  d_guides: normal and depth required, prim with OCTPT_TEMPORAL_MATCH_PRIM.
+ * d_prev == NULL is the first frame: out = color, length 1 on hits and 0 on misses.  d_out may alias d_color;
+ * d_out must not be d_prev->color nor d_out_length d_prev->length (INVALID_ARG).  One launch on `hip_stream`, no
+ * host synchronisation, no memory of the context's; returns once enqueued.  On a multi-device context it runs
+ * on devices[0]. */
+octpt_status octpt_temporal_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
+                                   const octpt_aov_buffers *d_guides, const octpt_temporal_history *d_prev,
+                                   float *d_out, uint32_t *d_out_length, void *hip_stream);
+/* The same over host arrays (out may alias color). */
+octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color,
+                            const octpt_aov_buffers *guides, const octpt_temporal_history *prev, float *out,
+                            uint32_t *out_length);
+/* The mapping alone: prev_xy[2 * (y * width + x)] = (fx, fy), where pixel (x, y) of `camera`'s frame at depth[..]
+ * lay in prev_camera's frame (pixel centre x <-> fx = x, not clipped to the image), and prev_depth[..] = zp.  A
+ * pixel whose depth is not finite, or whose point is not in front of prev_camera, gets (NaN, NaN) and +inf.  The
+ * same f32 expressions in the same order as the kernel, bit for bit, as octpt_camera_rays is to the preview's
+ * ray: "where was this pixel last frame".  Both cameras follow octpt_set_camera's rules; prev_camera must be
+ * orthonormal as above.  Host-only, no context. */
+octpt_status octpt_reproject_coords(const octpt_camera *camera, const octpt_camera *prev_camera, uint32_t width,
+                                    uint32_t height, const float *depth, float *prev_xy, float *prev_depth);
+
 /* --- host octree builder (replaces the Rust-side build for primitive scenes) ---
  * Voxelises spheres/cuboids into depth-`depth` leaf cells, Morton-sorts
  * them (new_octree.rs:752-835 code order) and emits octants in pre-order. */

@@ -199,6 +199,23 @@ class DenoiseParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+TEMPORAL_MATCH_PRIM = 0x1  # OCTPT_TEMPORAL_MATCH_PRIM
+HISTORY_NAMES = ("color", "normal", "depth", "prim", "length")  # octpt_temporal_history field order
+
+
+class TemporalParams(C.Structure):
+    """octpt_temporal_params."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("camera", Camera), ("prev_camera", Camera),
+                ("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class TemporalHistory(C.Structure):
+    """octpt_temporal_history: the previous call's output and the guides it was made with."""
+    _fields_ = [("color", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("prim", C.c_void_p),
+                ("length", C.c_void_p)]
+
+
 # octpt_stats::drain order (OCTPT_STAT_*)
 STAT_NAMES = ("paths", "segments", "esvo_steps", "sphere_tests", "cuboid_tests", "shade_events", "texel_reads",
               "block_tests", "issued_bytes")
@@ -260,6 +277,11 @@ SIGNATURES = {
     "octpt_render_aov_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers), _vp]),
     "octpt_denoise_device": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp, _vp]),
     "octpt_denoise": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp]),
+    "octpt_temporal_device": (_i32, [_vp, C.POINTER(TemporalParams), _vp, C.POINTER(AovBuffers),
+                                     C.POINTER(TemporalHistory), _vp, _vp, _vp]),
+    "octpt_temporal": (_i32, [_vp, C.POINTER(TemporalParams), _vp, C.POINTER(AovBuffers),
+                              C.POINTER(TemporalHistory), _vp, _vp]),
+    "octpt_reproject_coords": (_i32, [C.POINTER(Camera), C.POINTER(Camera), _u32, _u32, _vp, _vp, _vp]),
     "octpt_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "octpt_reset_stats": (_i32, [_vp]),
     "octpt_build_octree": (_i32, [_vp, _u32, _vp, _u32, _u32, C.POINTER(_vp)]),

@@ -23,6 +23,7 @@
 #include "../../include/octpt.h"
 #include "octpt_internal.h"
 #include "octpt_mask.h"
+#include "octpt_reproject.h"
 
 using namespace octpt;
 
@@ -2321,6 +2322,148 @@ octpt_status octpt_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const 
         return OCTPT_OK;
     } catch (...) {
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise");
+    }
+}
+
+// ---------------- temporal reprojection of the preview history (C26) ----------------
+namespace {
+
+octpt_status check_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const void *color, const octpt_aov_buffers *g,
+                            const octpt_temporal_history *prev, const void *out, const void *out_length) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal params NULL");
+    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: zero frame size");
+    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: bad resolution");
+    if (p->max_history < 1u || p->max_history > 65535u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: max_history must be 1..65535");
+    if (!(p->depth_tolerance > 0.0f) || !std::isfinite(p->depth_tolerance))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: depth_tolerance must be positive and finite");
+    if (!(p->normal_threshold >= -1.0f && p->normal_threshold <= 1.0f))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: normal_threshold must be in [-1, 1]");
+    if (p->flags & ~OCTPT_TEMPORAL_MATCH_PRIM)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "temporal: unknown flag (full frames only: no shard or compact tile layout; OCTPT_TEMPORAL_MATCH_PRIM is the one flag)");
+    const char *why = nullptr;
+    const octpt_status st = check_reproject_cameras(&p->camera, &p->prev_camera, &why);
+    if (st != OCTPT_OK) return fail(ctx, st, std::string("temporal: ") + why);
+    const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
+    if (!color || !out || !out_length) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: NULL colour, output or output length buffer");
+    if (!g || !g->normal || !g->depth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the normal and depth guides are required");
+    if (match && !g->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: OCTPT_TEMPORAL_MATCH_PRIM needs the prim guide");
+    if (prev) {
+        if (!prev->color || !prev->normal || !prev->depth || !prev->length)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the history needs its colour, normal, depth and length");
+        if (match && !prev->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: OCTPT_TEMPORAL_MATCH_PRIM needs the history's prim");
+        // the pass gathers from the history while it writes: only the current colour may be the output
+        if (out == prev->color) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the output must not be the history colour");
+        if (out_length == prev->length)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the output length must not be the history length");
+    }
+    return OCTPT_OK;
+}
+
+DevCamera dev_camera(const octpt_camera &c) {
+    const CameraBasis b = camera_basis(c.eye, c.direction, c.up, c.fov);
+    DevCamera C{};
+    std::memcpy(C.eye, b.eye, 12);
+    std::memcpy(C.dir, b.dir, 12);
+    std::memcpy(C.right, b.right, 12);
+    std::memcpy(C.up, b.up, 12);
+    C.d_factor = b.d_factor;
+    return C;
+}
+
+}  // namespace
+
+octpt_status octpt_temporal_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
+                                   const octpt_aov_buffers *g, const octpt_temporal_history *prev, float *d_out,
+                                   uint32_t *d_out_length, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_temporal(ctx, p, d_color, g, prev, d_out, d_out_length);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_temporal_device(ctx->sub[0], p, d_color, g, prev, d_out, d_out_length, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
+        DevTemporal T{};
+        T.W = p->width;
+        T.H = p->height;
+        T.dim = (float)(p->width > p->height ? p->width : p->height);
+        T.cur = dev_camera(p->camera);
+        T.prev = dev_camera(p->prev_camera);
+        T.max_history = p->max_history;
+        T.depth_tolerance = p->depth_tolerance;
+        T.normal_threshold = p->normal_threshold;
+        T.match_prim = match ? 1u : 0u;
+        T.color = reinterpret_cast<const float4 *>(d_color);
+        T.normal = reinterpret_cast<const float4 *>(g->normal);
+        T.depth = g->depth;
+        T.prim = match ? g->prim : nullptr;
+        if (prev) {
+            T.h_color = reinterpret_cast<const float4 *>(prev->color);
+            T.h_normal = reinterpret_cast<const float4 *>(prev->normal);
+            T.h_depth = prev->depth;
+            T.h_prim = match ? prev->prim : nullptr;
+            T.h_length = prev->length;
+        }
+        T.out = reinterpret_cast<float4 *>(d_out);
+        T.out_length = d_out_length;
+        HIP_TRY(ctx, launch_temporal(T, static_cast<hipStream_t>(stream)));
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
+    }
+}
+
+octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color,
+                            const octpt_aov_buffers *g, const octpt_temporal_history *prev, float *out,
+                            uint32_t *out_length) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_temporal(ctx, p, color, g, prev, out, out_length);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_temporal(ctx->sub[0], p, color, g, prev, out, out_length);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
+        // colour (blended in place on the device), normal, depth, prim; the history's five; the output length
+        const void *h[9] = {color, g->normal, g->depth, match ? g->prim : nullptr,
+                            prev ? prev->color : nullptr, prev ? prev->normal : nullptr, prev ? prev->depth : nullptr,
+                            prev && match ? prev->prim : nullptr, prev ? prev->length : nullptr};
+        const size_t bpp[9] = {16, 16, 4, 4, 16, 16, 4, 4, 4};
+        void *d[10] = {};
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 9 && e == hipSuccess; ++i) {
+            if (!h[i]) continue;
+            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) e = hipMalloc(&d[9], n * 4);
+        if (e == hipSuccess) {
+            const octpt_aov_buffers dg{nullptr, static_cast<float *>(d[1]), static_cast<float *>(d[2]),
+                                       static_cast<uint32_t *>(d[3]), nullptr};
+            const octpt_temporal_history dp{static_cast<float *>(d[4]), static_cast<float *>(d[5]), static_cast<float *>(d[6]),
+                                            static_cast<uint32_t *>(d[7]), static_cast<uint32_t *>(d[8])};
+            st = octpt_temporal_device(ctx, p, static_cast<float *>(d[0]), &dg, prev ? &dp : nullptr,
+                                       static_cast<float *>(d[0]), static_cast<uint32_t *>(d[9]), ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out_length, d[9], n * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "temporal");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
     }
 }
 

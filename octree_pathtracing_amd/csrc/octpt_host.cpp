@@ -1,5 +1,5 @@
 // Host-side queries of the C ABI that need no device: Octree::get_traversal_data and, at the end,
-// the camera's pixel-centre rays (octpt_camera_rays).
+// the camera's pixel-centre rays (octpt_camera_rays) and the reprojection mapping (octpt_reproject_coords).
 //
 // get_traversal_data (octree_traversal.rs:537-714) is the reference's beam-start query: the
 // host walks one ray (GPURenderer::render_frame uses the camera's centre ray,
@@ -14,6 +14,7 @@
 
 #include "../../include/octpt.h"
 #include "octpt_mask.h"
+#include "octpt_reproject.h"
 
 namespace {
 constexpr uint32_t kMaxScale = 23u;   // OCTREE_MAX_SCALE, octree_traversal.rs:14
@@ -162,5 +163,31 @@ extern "C" octpt_status octpt_camera_rays(const octpt_camera *camera, uint32_t w
             o[5] = nd[2] * r;
         }
     }
+    return OCTPT_OK;
+}
+
+// The mapping of DESIGN.md C26 alone: csrc/octpt_reproject.h's reproject_pixel, the text temporal_kernel compiles,
+// over the whole frame.
+extern "C" octpt_status octpt_reproject_coords(const octpt_camera *camera, const octpt_camera *prev_camera, uint32_t width,
+                                               uint32_t height, const float *depth, float *prev_xy, float *prev_depth) {
+    if (!camera || !prev_camera || !depth || !prev_xy || !prev_depth) return OCTPT_ERR_INVALID_ARG;
+    if (width == 0u || height == 0u || (uint64_t)width * height >= (1ull << 31)) return OCTPT_ERR_INVALID_ARG;
+    const char *why = nullptr;
+    const octpt_status st = octpt::check_reproject_cameras(camera, prev_camera, &why);
+    if (st != OCTPT_OK) return st;
+    const octpt::CameraBasis cur = octpt::camera_basis(camera->eye, camera->direction, camera->up, camera->fov);
+    const octpt::CameraBasis prev =
+        octpt::camera_basis(prev_camera->eye, prev_camera->direction, prev_camera->up, prev_camera->fov);
+    const float dim = (float)(width > height ? width : height);
+    for (uint32_t y = 0; y < height; ++y)
+        for (uint32_t x = 0; x < width; ++x) {
+            const size_t p = (size_t)y * width + x;
+            float fx = NAN, fy = NAN, zp = INFINITY;
+            const float z = depth[p];
+            if (std::fabs(z) < INFINITY) (void)octpt::reproject_pixel(cur, prev, x, y, width, height, dim, z, fx, fy, zp);
+            prev_xy[2u * p] = fx;
+            prev_xy[2u * p + 1u] = fy;
+            prev_depth[p] = zp;
+        }
     return OCTPT_OK;
 }

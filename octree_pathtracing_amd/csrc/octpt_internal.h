@@ -183,6 +183,24 @@ struct DevDenoise {
     const float *depth;
 };
 
+// one temporal reprojection call (octpt_temporal_params + the buffers); passed by value
+struct DevTemporal {
+    uint32_t W, H;
+    float dim;                          // max(W, H)
+    DevCamera cur, prev;
+    uint32_t max_history;
+    float depth_tolerance, normal_threshold;
+    uint32_t match_prim;
+    const float4 *color, *normal;       // the current frame and its guides
+    const float *depth;
+    const uint32_t *prim;               // NULL without OCTPT_TEMPORAL_MATCH_PRIM
+    const float4 *h_color, *h_normal;   // the history; h_color NULL = first frame
+    const float *h_depth;
+    const uint32_t *h_prim, *h_length;
+    float4 *out;
+    uint32_t *out_length;
+};
+
 // frame tile at dealing position s (octpt_set_tile_order's permutation, or s itself)
 __host__ __device__ inline uint32_t dealt_tile(const uint32_t *order, uint32_t s) { return order ? order[s] : s; }
 
@@ -331,6 +349,8 @@ hipError_t launch_denoise_prep(uint32_t W, uint32_t H, const float4 *color, cons
                                float4 *sig, hipStream_t stream);
 hipError_t launch_atrous(const DevDenoise &D, uint32_t iter, bool last, const float4 *src, float4 *dst,
                          hipStream_t stream);
+// temporal reprojection: one launch, one thread per pixel of the current frame
+hipError_t launch_temporal(const DevTemporal &T, hipStream_t stream);
 hipError_t launch_tonemap(const float4 *accum, uchar4 *out, uint32_t n, const uint8_t *lut_byte,
                           hipStream_t stream);
 hipError_t launch_unshard(uint32_t W, uint32_t H, uint32_t shard_count, const uint32_t *tile_pos, const float4 *shards,

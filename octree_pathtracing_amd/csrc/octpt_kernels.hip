@@ -17,6 +17,7 @@
 // implements as `forward_accumulation`.
 #include "octpt_internal.h"
 #include "octpt_rcp.h"
+#include "octpt_reproject.h"
 
 #ifndef OCTPT_RCP_FAST
 #define OCTPT_RCP_FAST 1  // esvo_begin's t_coef by rcp_rn (A/B: -DOCTPT_RCP_FAST=0, the division: extend +0.2..0.6 %)
@@ -3026,6 +3027,78 @@ __global__ __launch_bounds__(256) void atrous_kernel(DevDenoise D, uint32_t iter
     dst[p] = o;
 }
 
+// ===========================================================================
+// Temporal reprojection of the preview history.  One thread per pixel of the current frame, the
+// denoiser's 32 x 8 tiles: under translation and small rotation a wave's taps fall on a few rows of the previous
+// frame.  The mapping is csrc/octpt_reproject.h's text, which octpt_reproject_coords compiles for the host; the
+// rest is the contract's arithmetic, operation for operation.  Every tap is a global gather (its footprint
+// depends on the camera move, so no LDS staging); a tap inside the image loads all its five values before any is
+// tested, so the four taps' loads are in flight together.  out may alias color (no __restrict__): a thread reads
+// its own pixel of color before it writes it and no other.
+// ===========================================================================
+__global__ __launch_bounds__(256) void temporal_kernel(DevTemporal T) {
+    const uint32_t x = blockIdx.x * kDnX + threadIdx.x % kDnX, y = blockIdx.y * kDnY + threadIdx.x / kDnX;
+    if (x >= T.W || y >= T.H) return;
+    const size_t p = (size_t)y * T.W + (size_t)x;
+    const float kInf = __builtin_inff();
+    const float4 c = T.color[p];
+    const float z = T.depth[p];
+    if (!(fabsf(z) < kInf)) {  // a miss: copied through, no history to carry
+        T.out[p] = c;
+        T.out_length[p] = 0u;
+        return;
+    }
+    float4 o = c;
+    uint32_t N = 1u;  // no history: a first frame or a disocclusion
+    float fx, fy, zp;
+    if (T.h_color && octpt::reproject_pixel(T.cur, T.prev, x, y, T.W, T.H, T.dim, z, fx, fy, zp) && fx >= -1.0f &&
+        fx < (float)T.W && fy >= -1.0f && fy < (float)T.H) {  // false on NaN
+        const float x0f = floorf(fx), y0f = floorf(fy);
+        const float wx = fx - x0f, wy = fy - y0f;
+        const int x0 = (int)x0f, y0 = (int)y0f, W = (int)T.W, H = (int)T.H;
+        const float4 np = T.normal[p];
+        const uint32_t prim_p = T.match_prim ? T.prim[p] : 0u;
+        float B = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;
+        uint32_t n_prev = 0xFFFFFFFFu;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const float b = (i ? wx : 1.0f - wx) * (j ? wy : 1.0f - wy);
+                const int qx = x0 + i, qy = y0 + j;
+                if (!(b > 0.0f) || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                const size_t q = (size_t)qy * T.W + (size_t)qx;
+                const float zq = T.h_depth[q];
+                const uint32_t len_q = T.h_length[q];
+                const float4 nq = T.h_normal[q];
+                const float4 cq = T.h_color[q];
+                const uint32_t prim_q = T.match_prim ? T.h_prim[q] : 0u;
+                const bool counts = fabsf(zq) < kInf && len_q > 0u && fabsf(zq - zp) <= T.depth_tolerance * zp &&
+                                    (np.x * nq.x + np.y * nq.y) + np.z * nq.z >= T.normal_threshold && prim_q == prim_p;
+                if (!counts) continue;
+                B = B + b;
+                hx = hx + b * cq.x;
+                hy = hy + b * cq.y;
+                hz = hz + b * cq.z;
+                n_prev = len_q < n_prev ? len_q : n_prev;
+            }
+        }
+        if (B >= 0x1p-10f) {  // keeps the quotient away from vanishing weights
+            const uint32_t cap = T.max_history - 1u;
+            N = (n_prev < cap ? n_prev : cap) + 1u;  // min(n_prev + 1, max_history), no wrap at a length of 2^32 - 1
+            const float a = 1.0f / (float)N;
+            hx = hx / B;
+            hy = hy / B;
+            hz = hz / B;
+            o.x = hx + (c.x - hx) * a;
+            o.y = hy + (c.y - hy) * a;
+            o.z = hz + (c.z - hz) * a;
+        }
+    }
+    T.out[p] = o;
+    T.out_length[p] = N;
+}
+
 }  // namespace
 
 // ESVO stack levels 1..depth-1 (level 0 is never used, see esvo_step)
@@ -3098,6 +3171,12 @@ hipError_t launch_atrous(const DevDenoise &D, uint32_t iter, bool last, const fl
                          hipStream_t stream) {
     const dim3 grid((D.W + kDnX - 1u) / kDnX, (D.H + kDnY - 1u) / kDnY);
     hipLaunchKernelGGL(last ? atrous_kernel<true> : atrous_kernel<false>, grid, dim3(256), 0, stream, D, iter, src, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal(const DevTemporal &T, hipStream_t stream) {
+    const dim3 grid((T.W + kDnX - 1u) / kDnX, (T.H + kDnY - 1u) / kDnY);
+    hipLaunchKernelGGL(temporal_kernel, grid, dim3(256), 0, stream, T);
     return hipGetLastError();
 }
 

@@ -398,6 +398,56 @@ class HipRenderer:
         self._check(self._lib.octpt_denoise_device(self._ctx, C.byref(params), C.c_void_p(d_color), C.byref(b),
                                                    C.c_void_p(d_out), C.c_void_p(stream) if stream else None))
 
+    # ------------------------------------------------------------ temporal reprojection (C26)
+    def temporal(self, color: np.ndarray, aov: dict, history: dict | None = None, prev_camera: Camera | None = None,
+                 max_history: int = 32, depth_tolerance: float = 0.1, normal_threshold: float = 0.9,
+                 match_prim: bool = True) -> dict:
+        """Carry `history` (the dict a previous call returned, None on the first frame) to the current camera's
+        frame and blend the new [H, W, 4] `color` into it (octpt_temporal), guided by render_aov's normal, depth
+        and (with match_prim) prim of the current frame.  prev_camera: the history's camera, by default the one
+        it recorded.  Returns the new history: color (the blended frame, what denoise takes next), normal, depth,
+        prim, length (u32 [H, W]: samples of history per pixel, 0 on misses) and camera."""
+        color = np.ascontiguousarray(color, np.float32)
+        H, W = color.shape[:2]
+        keep = []
+
+        def ptr(src, name, dt):
+            if src.get(name) is None:
+                return None  # the library reports what is missing
+            a = np.ascontiguousarray(src[name], dt)
+            if a.size != W * H * (4 if name in ("color", "normal") else 1):
+                raise ValueError(f"{name} does not match the {W} x {H} frame")
+            keep.append(a)
+            return a.ctypes.data
+
+        names = ("normal", "depth") + (("prim",) if match_prim else ())
+        dtype = {"color": np.float32, "normal": np.float32, "depth": np.float32, "prim": np.uint32, "length": np.uint32}
+        g = _lib.AovBuffers(**{k: ptr(aov, k, dtype[k]) for k in names})
+        prev = None
+        if history is not None:
+            prev = _lib.TemporalHistory(**{k: ptr(history, k, dtype[k]) for k in ("color", "length") + names})
+            prev_camera = prev_camera or history.get("camera")
+        cam = self._camera
+        p = _lib.TemporalParams(W, H, _c_camera(cam), _c_camera(prev_camera or cam), max_history, depth_tolerance,
+                                normal_threshold, _lib.TEMPORAL_MATCH_PRIM if match_prim else 0)
+        out = np.empty_like(color)
+        length = np.empty((H, W), np.uint32)
+        self._check(self._lib.octpt_temporal(self._ctx, C.byref(p), color.ctypes.data_as(C.c_void_p), C.byref(g),
+                                             C.byref(prev) if prev is not None else None,
+                                             out.ctypes.data_as(C.c_void_p), length.ctypes.data_as(C.c_void_p)))
+        return {"color": out, "normal": aov.get("normal"), "depth": aov.get("depth"), "prim": aov.get("prim"),
+                "length": length, "camera": cam}
+
+    def temporal_device(self, params: "_lib.TemporalParams", d_color: int, guides: dict, prev: dict | None, d_out: int,
+                        d_out_length: int, stream: int | None = None) -> None:
+        """Enqueue octpt_temporal_device on raw device pointers: guides {normal, depth, prim}, prev {color,
+        normal, depth, prim, length} or None for the first frame (d_out may equal d_color)."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in guides.items() if v})
+        h = _lib.TemporalHistory(**{k: C.c_void_p(int(v)) for k, v in prev.items() if v}) if prev is not None else None
+        self._check(self._lib.octpt_temporal_device(self._ctx, C.byref(params), C.c_void_p(d_color), C.byref(b),
+                                                    C.byref(h) if h is not None else None, C.c_void_p(d_out),
+                                                    C.c_void_p(d_out_length), C.c_void_p(stream) if stream else None))
+
     def stats(self) -> dict:
         s = _lib.Stats()
         self._check(self._lib.octpt_get_stats(self._ctx, C.byref(s)))
@@ -433,6 +483,29 @@ def camera_rays(camera: Camera, W: int, H: int) -> np.ndarray:
     if st != 0:
         raise _lib.OctptError(st, "octpt_camera_rays")
     return rays
+
+
+def _c_camera(camera: Camera) -> "_lib.Camera":
+    return _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction), (C.c_float * 3)(*camera.up),
+                       camera.fov, 0.0, 0.0)
+
+
+def reproject_coords(camera: Camera, prev_camera: Camera, W: int, H: int, depth: np.ndarray):
+    """octpt_reproject_coords: where each pixel of `camera`'s W x H frame, at its `depth`, lay in prev_camera's
+    frame -> (xy [H, W, 2] f32 in pixel units, pixel centre x <-> fx = x; depth [H, W] f32 from prev_camera's
+    eye).  (NaN, NaN) and +inf where the depth is not finite or the point is not in front of prev_camera.  The
+    temporal kernel's own mapping, bit for bit (host-only, no context)."""
+    depth = np.ascontiguousarray(depth, np.float32)
+    if depth.size != W * H:
+        raise ValueError(f"depth holds {depth.size} pixels, not {W} x {H}")
+    xy = np.zeros((H, W, 2), np.float32)
+    zp = np.zeros((H, W), np.float32)
+    st = _lib.load().octpt_reproject_coords(C.byref(_c_camera(camera)), C.byref(_c_camera(prev_camera)), W, H,
+                                            depth.ctypes.data_as(C.c_void_p), xy.ctypes.data_as(C.c_void_p),
+                                            zp.ctypes.data_as(C.c_void_p))
+    if st != 0:
+        raise _lib.OctptError(st, "octpt_reproject_coords")
+    return xy, zp
 
 
 def shard_pixels(W: int, H: int, shard_index: int, shard_count: int) -> int:
