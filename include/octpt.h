@@ -472,6 +472,83 @@ octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, cons
 octpt_status octpt_reproject_coords(const octpt_camera *camera, const octpt_camera *prev_camera, uint32_t width,
                                     uint32_t height, const float *depth, float *prev_xy, float *prev_depth);
 
+/* --- luminance moments, variance and the variance-guided filter (SVGF, Schied et al. 2017) ---
+ * The a-trous filter above stops at colour edges under one global sigma_color.  With temporal accumulation in
+ * front of it the right control is per pixel: a pixel with a long history needs almost no filtering, a pixel
+ * disoccluded this frame needs all of it.  These three passes carry the first and second moments of the working
+ * signal's luminance l = (0.2126 r + 0.7152 g) + 0.0722 b through the reprojection, turn them into a variance,
+ * and filter with a luminance weight scaled by the local standard deviation.
+ * A frame: octpt_render_device (low spp) -> octpt_render_aov_device -> octpt_temporal_moments_device (history in,
+ * new history out) -> octpt_variance_device -> octpt_denoise_variance_device -> tone map.  The history that the
+ * next frame reads is the temporal pass's output -- the *unfiltered* colour and moments with this frame's guides --
+ * never the filter's: filtered history would be filtered again every frame.  Pass the same demodulate choice to
+ * the temporal and the filter pass, so that the variance is that of the signal the filter works on. */
+
+/* C27.  octpt_temporal with the moments alongside: d_out and d_out_length are octpt_temporal_device's, bit for
+ * bit.  Moments planes hold 2 floats / pixel (m1, m2).  The pixel's own moments are mu = (l(s), l(s)^2) of
+ * s = color.rgb, or color.rgb / max(albedo.rgb, 1e-3) with OCTPT_TEMPORAL_DEMODULATE (d_guides->albedo then
+ * required).  With history: hm = the weighted mean of the counted taps' moments, out_m = hm + (mu - hm) / N.
+ * Without: out_m = mu.  A miss: (0, 0).  d_prev and d_prev_moments are both NULL (the first frame) or both set;
+ * d_out_moments must not be d_prev_moments, besides octpt_temporal_device's alias rules (INVALID_ARG).  One launch
+ * on `hip_stream`, no host synchronisation, no memory of the context's.  octpt_temporal itself refuses the flag. */
+#define OCTPT_TEMPORAL_DEMODULATE 0x2u
+octpt_status octpt_temporal_moments_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
+                                           const octpt_aov_buffers *d_guides, const octpt_temporal_history *d_prev,
+                                           const float *d_prev_moments, float *d_out, uint32_t *d_out_length,
+                                           float *d_out_moments, void *hip_stream);
+/* The same over host arrays (out may alias color). */
+octpt_status octpt_temporal_moments(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color,
+                                    const octpt_aov_buffers *guides, const octpt_temporal_history *prev,
+                                    const float *prev_moments, float *out, uint32_t *out_length, float *out_moments);
+
+/* C28.  The variance of the luminance from C27's moments and lengths and the frame's normal and depth guides, one
+ * float / pixel, never negative.  A miss (depth not finite, or length 0): 0.  A pixel with length N >= min_history:
+ * max(m2 - m1^2, 0), the temporal estimate.  A shorter one: the same of the 7 x 7 mean of the moments around it,
+ * each tap weighted by the filter's normal and depth weights with their exponential correctly rounded (taps outside
+ * the image, misses and length-0 taps skipped), times min_history / N: a spatial estimate, inflated while the history is short. */
+typedef struct octpt_variance_params {
+    uint32_t width, height;
+    uint32_t min_history;            /* 1..65535; SVGF uses 4 */
+    float sigma_normal, sigma_depth; /* > 0, finite: octpt_denoise's */
+} octpt_variance_params;
+/* Device buffers, full frames only; d_guides: normal and depth.  d_out is distinct from the inputs.  One launch on
+ * `hip_stream`, no host synchronisation, no memory of the context's; on a multi-device context it runs on
+ * devices[0]. */
+octpt_status octpt_variance_device(octpt_ctx *ctx, const octpt_variance_params *p, const float *d_moments,
+                                   const uint32_t *d_length, const octpt_aov_buffers *d_guides, float *d_out,
+                                   void *hip_stream);
+/* The same over host arrays. */
+octpt_status octpt_variance(octpt_ctx *ctx, const octpt_variance_params *p, const float *moments,
+                            const uint32_t *length, const octpt_aov_buffers *guides, float *out);
+
+/* C29.  octpt_denoise with the colour weight replaced by a luminance weight under the local standard deviation.
+ * Working signal, miss pixels, alpha and the re-modulation after the last pass are octpt_denoise's.  Pass i, pixel
+ * p: vbar = the 3 x 3 (1/4, 1/2, 1/4)^2 mean of the variance around p at spacing 1; k = 1 / (sigma_luminance *
+ * sqrtf(vbar) + luminance_floor); taps as octpt_denoise's with wc replaced by wl = expf(-(|l(s_p) - l(s_q)| * k));
+ * out = sum(w s_q) / sum(w), variance out = sum(w^2 v_q) / sum(w)^2.  sigma_luminance is not scaled per pass: the
+ * variance shrinks instead.  The variance is that of the working signal and is not re-modulated; it must be >= 0;
+ * miss pixels keep theirs. */
+typedef struct octpt_denoise_variance_params {
+    uint32_t width, height;
+    uint32_t iterations;   /* 1..5 */
+    float sigma_luminance; /* > 0, finite; SVGF uses 4 */
+    float luminance_floor; /* > 0, finite: the weight's scale where the variance is 0 */
+    float sigma_normal, sigma_depth; /* > 0, finite */
+    uint32_t flags;        /* OCTPT_DENOISE_DEMODULATE */
+} octpt_denoise_variance_params;
+/* d_color, d_out: 4 floats / pixel (d_out may alias d_color); d_variance: 1 float / pixel; d_out_variance: NULL or
+ * 1 float / pixel, the filtered variance (may alias d_variance).  One prep launch and one launch per iteration
+ * on `hip_stream`, no host synchronisation.  The working frames are octpt_denoise_device's two, owned by the
+ * context: its denoise and denoise_variance calls on different streams must be ordered by the caller.  On a
+ * multi-device context it runs on devices[0]. */
+octpt_status octpt_denoise_variance_device(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const float *d_color,
+                                           const float *d_variance, const octpt_aov_buffers *d_guides, float *d_out,
+                                           float *d_out_variance, void *hip_stream);
+/* The same over host arrays (out may alias color, out_variance may alias variance or be NULL). */
+octpt_status octpt_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const float *color,
+                                    const float *variance, const octpt_aov_buffers *guides, float *out,
+                                    float *out_variance);
+
 /* --- host octree builder (replaces the Rust-side build for primitive scenes) ---
  * Voxelises spheres/cuboids into depth-`depth` leaf cells, Morton-sorts
  * them (new_octree.rs:752-835 code order) and emits octants in pre-order. */

@@ -216,6 +216,22 @@ class TemporalHistory(C.Structure):
                 ("length", C.c_void_p)]
 
 
+TEMPORAL_DEMODULATE = 0x2  # OCTPT_TEMPORAL_DEMODULATE: the moments entries alone (C27)
+
+
+class VarianceParams(C.Structure):
+    """octpt_variance_params."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("min_history", C.c_uint32),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
+class DenoiseVarianceParams(C.Structure):
+    """octpt_denoise_variance_params."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("luminance_floor", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
 # octpt_stats::drain order (OCTPT_STAT_*)
 STAT_NAMES = ("paths", "segments", "esvo_steps", "sphere_tests", "cuboid_tests", "shade_events", "texel_reads",
               "block_tests", "issued_bytes")
@@ -281,6 +297,16 @@ SIGNATURES = {
                                      C.POINTER(TemporalHistory), _vp, _vp, _vp]),
     "octpt_temporal": (_i32, [_vp, C.POINTER(TemporalParams), _vp, C.POINTER(AovBuffers),
                               C.POINTER(TemporalHistory), _vp, _vp]),
+    "octpt_temporal_moments_device": (_i32, [_vp, C.POINTER(TemporalParams), _vp, C.POINTER(AovBuffers),
+                                             C.POINTER(TemporalHistory), _vp, _vp, _vp, _vp, _vp]),
+    "octpt_temporal_moments": (_i32, [_vp, C.POINTER(TemporalParams), _vp, C.POINTER(AovBuffers),
+                                      C.POINTER(TemporalHistory), _vp, _vp, _vp, _vp]),
+    "octpt_variance_device": (_i32, [_vp, C.POINTER(VarianceParams), _vp, _vp, C.POINTER(AovBuffers), _vp, _vp]),
+    "octpt_variance": (_i32, [_vp, C.POINTER(VarianceParams), _vp, _vp, C.POINTER(AovBuffers), _vp]),
+    "octpt_denoise_variance_device": (_i32, [_vp, C.POINTER(DenoiseVarianceParams), _vp, _vp, C.POINTER(AovBuffers),
+                                             _vp, _vp, _vp]),
+    "octpt_denoise_variance": (_i32, [_vp, C.POINTER(DenoiseVarianceParams), _vp, _vp, C.POINTER(AovBuffers), _vp,
+                                      _vp]),
     "octpt_reproject_coords": (_i32, [C.POINTER(Camera), C.POINTER(Camera), _u32, _u32, _vp, _vp, _vp]),
     "octpt_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "octpt_reset_stats": (_i32, [_vp]),

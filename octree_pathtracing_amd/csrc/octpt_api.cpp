@@ -2328,37 +2328,56 @@ octpt_status octpt_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const 
 // ---------------- temporal reprojection of the preview history (C26) ----------------
 namespace {
 
-octpt_status check_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const void *color, const octpt_aov_buffers *g,
-                            const octpt_temporal_history *prev, const void *out, const void *out_length) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal params NULL");
-    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: zero frame size");
+// `who` names the pass in the messages; moments: the C27 entries, which also accept OCTPT_TEMPORAL_DEMODULATE
+octpt_status check_temporal(octpt_ctx *ctx, const char *who, bool moments, const octpt_temporal_params *p, const void *color,
+                            const octpt_aov_buffers *g, const octpt_temporal_history *prev, const void *out,
+                            const void *out_length) {
+    const std::string w = std::string(who) + ": ";
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, std::string(who) + " params NULL");
+    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "zero frame size");
     if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: bad resolution");
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "bad resolution");
     if (p->max_history < 1u || p->max_history > 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: max_history must be 1..65535");
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "max_history must be 1..65535");
     if (!(p->depth_tolerance > 0.0f) || !std::isfinite(p->depth_tolerance))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: depth_tolerance must be positive and finite");
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "depth_tolerance must be positive and finite");
     if (!(p->normal_threshold >= -1.0f && p->normal_threshold <= 1.0f))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: normal_threshold must be in [-1, 1]");
-    if (p->flags & ~OCTPT_TEMPORAL_MATCH_PRIM)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "normal_threshold must be in [-1, 1]");
+    if (p->flags & ~(OCTPT_TEMPORAL_MATCH_PRIM | (moments ? OCTPT_TEMPORAL_DEMODULATE : 0u)))
         return fail(ctx, OCTPT_ERR_INVALID_ARG,
-                    "temporal: unknown flag (full frames only: no shard or compact tile layout; OCTPT_TEMPORAL_MATCH_PRIM is the one flag)");
+                    w + (moments ? "unknown flag (full frames only: no shard or compact tile layout; OCTPT_TEMPORAL_MATCH_PRIM and OCTPT_TEMPORAL_DEMODULATE are the flags)"
+                                 : "unknown flag (full frames only: no shard or compact tile layout; OCTPT_TEMPORAL_MATCH_PRIM is the one flag)"));
     const char *why = nullptr;
     const octpt_status st = check_reproject_cameras(&p->camera, &p->prev_camera, &why);
-    if (st != OCTPT_OK) return fail(ctx, st, std::string("temporal: ") + why);
+    if (st != OCTPT_OK) return fail(ctx, st, w + why);
     const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
-    if (!color || !out || !out_length) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: NULL colour, output or output length buffer");
-    if (!g || !g->normal || !g->depth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the normal and depth guides are required");
-    if (match && !g->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: OCTPT_TEMPORAL_MATCH_PRIM needs the prim guide");
+    if (!color || !out || !out_length) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "NULL colour, output or output length buffer");
+    if (!g || !g->normal || !g->depth) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the normal and depth guides are required");
+    if (match && !g->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "OCTPT_TEMPORAL_MATCH_PRIM needs the prim guide");
+    if ((p->flags & OCTPT_TEMPORAL_DEMODULATE) && !g->albedo)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "OCTPT_TEMPORAL_DEMODULATE needs the albedo guide");
     if (prev) {
         if (!prev->color || !prev->normal || !prev->depth || !prev->length)
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the history needs its colour, normal, depth and length");
-        if (match && !prev->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: OCTPT_TEMPORAL_MATCH_PRIM needs the history's prim");
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the history needs its colour, normal, depth and length");
+        if (match && !prev->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "OCTPT_TEMPORAL_MATCH_PRIM needs the history's prim");
         // the pass gathers from the history while it writes: only the current colour may be the output
-        if (out == prev->color) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the output must not be the history colour");
+        if (out == prev->color) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the output must not be the history colour");
         if (out_length == prev->length)
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal: the output length must not be the history length");
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the output length must not be the history length");
     }
+    return OCTPT_OK;
+}
+
+// C27's own arguments, after check_temporal
+octpt_status check_moments(octpt_ctx *ctx, const octpt_temporal_history *prev, const void *prev_moments,
+                           const void *out_moments) {
+    if (!out_moments) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: NULL output moments buffer");
+    if (prev && !prev_moments)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: a history needs its moments");
+    if (!prev && prev_moments)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: previous moments without a history (the first frame takes neither)");
+    if (out_moments == prev_moments)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: the output moments must not be the history moments");
     return OCTPT_OK;
 }
 
@@ -2375,45 +2394,113 @@ DevCamera dev_camera(const octpt_camera &c) {
 
 }  // namespace
 
+namespace {
+
+// both temporal entries' device form after their checks; d_out_moments NULL = octpt_temporal_device (C26)
+octpt_status enqueue_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color, const octpt_aov_buffers *g,
+                              const octpt_temporal_history *prev, const float *d_prev_moments, float *d_out,
+                              uint32_t *d_out_length, float *d_out_moments, void *stream) {
+    join_inflight(ctx);
+    if (is_multi(ctx)) {
+        const octpt_status st = d_out_moments
+                                    ? octpt_temporal_moments_device(ctx->sub[0], p, d_color, g, prev, d_prev_moments, d_out,
+                                                                    d_out_length, d_out_moments, stream)
+                                    : octpt_temporal_device(ctx->sub[0], p, d_color, g, prev, d_out, d_out_length, stream);
+        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
+    DevTemporal T{};
+    T.W = p->width;
+    T.H = p->height;
+    T.dim = (float)(p->width > p->height ? p->width : p->height);
+    T.cur = dev_camera(p->camera);
+    T.prev = dev_camera(p->prev_camera);
+    T.max_history = p->max_history;
+    T.depth_tolerance = p->depth_tolerance;
+    T.normal_threshold = p->normal_threshold;
+    T.match_prim = match ? 1u : 0u;
+    T.color = reinterpret_cast<const float4 *>(d_color);
+    T.normal = reinterpret_cast<const float4 *>(g->normal);
+    T.depth = g->depth;
+    T.prim = match ? g->prim : nullptr;
+    if (prev) {
+        T.h_color = reinterpret_cast<const float4 *>(prev->color);
+        T.h_normal = reinterpret_cast<const float4 *>(prev->normal);
+        T.h_depth = prev->depth;
+        T.h_prim = match ? prev->prim : nullptr;
+        T.h_length = prev->length;
+        T.h_moments = reinterpret_cast<const float2 *>(d_prev_moments);
+    }
+    T.out = reinterpret_cast<float4 *>(d_out);
+    T.out_length = d_out_length;
+    T.albedo = (p->flags & OCTPT_TEMPORAL_DEMODULATE) ? reinterpret_cast<const float4 *>(g->albedo) : nullptr;
+    T.out_moments = reinterpret_cast<float2 *>(d_out_moments);
+    HIP_TRY(ctx, launch_temporal(T, d_out_moments != nullptr, static_cast<hipStream_t>(stream)));
+    return OCTPT_OK;
+}
+
+// both temporal entries' host form after their checks; out_moments NULL = octpt_temporal (C26)
+octpt_status temporal_host(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color, const octpt_aov_buffers *g,
+                           const octpt_temporal_history *prev, const float *prev_moments, float *out, uint32_t *out_length,
+                           float *out_moments) {
+    join_inflight(ctx);
+    if (is_multi(ctx)) {
+        const octpt_status st =
+            out_moments ? octpt_temporal_moments(ctx->sub[0], p, color, g, prev, prev_moments, out, out_length, out_moments)
+                        : octpt_temporal(ctx->sub[0], p, color, g, prev, out, out_length);
+        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)p->width * p->height;
+    const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
+    const bool demod = (p->flags & OCTPT_TEMPORAL_DEMODULATE) != 0u;
+    // colour (blended in place on the device), normal, depth, prim; the history's five; albedo and the history's
+    // moments (C27); then the two outputs
+    const void *h[11] = {color, g->normal, g->depth, match ? g->prim : nullptr,
+                         prev ? prev->color : nullptr, prev ? prev->normal : nullptr, prev ? prev->depth : nullptr,
+                         prev && match ? prev->prim : nullptr, prev ? prev->length : nullptr,
+                         demod ? g->albedo : nullptr, prev ? prev_moments : nullptr};
+    const size_t bpp[11] = {16, 16, 4, 4, 16, 16, 4, 4, 4, 16, 8};
+    void *d[13] = {};
+    octpt_status st = OCTPT_OK;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 11 && e == hipSuccess; ++i) {
+        if (!h[i]) continue;
+        if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMalloc(&d[11], n * 4);
+    if (e == hipSuccess && out_moments) e = hipMalloc(&d[12], n * 8);
+    if (e == hipSuccess) {
+        const octpt_aov_buffers dg{static_cast<float *>(d[9]), static_cast<float *>(d[1]), static_cast<float *>(d[2]),
+                                   static_cast<uint32_t *>(d[3]), nullptr};
+        const octpt_temporal_history dp{static_cast<float *>(d[4]), static_cast<float *>(d[5]), static_cast<float *>(d[6]),
+                                        static_cast<uint32_t *>(d[7]), static_cast<uint32_t *>(d[8])};
+        st = enqueue_temporal(ctx, p, static_cast<float *>(d[0]), &dg, prev ? &dp : nullptr, static_cast<float *>(d[10]),
+                              static_cast<float *>(d[0]), static_cast<uint32_t *>(d[11]), static_cast<float *>(d[12]),
+                              ctx->stream);
+        if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+        if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
+        if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out_length, d[11], n * 4, hipMemcpyDeviceToHost);
+        if (st == OCTPT_OK && e == hipSuccess && out_moments) e = hipMemcpy(out_moments, d[12], n * 8, hipMemcpyDeviceToHost);
+    }
+    for (void *q : d)
+        if (q) (void)hipFree(q);
+    if (st != OCTPT_OK) return st;
+    if (e != hipSuccess) return hip_fail(ctx, e, "temporal");
+    return OCTPT_OK;
+}
+
+}  // namespace
+
 octpt_status octpt_temporal_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
                                    const octpt_aov_buffers *g, const octpt_temporal_history *prev, float *d_out,
                                    uint32_t *d_out_length, void *stream) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_temporal(ctx, p, d_color, g, prev, d_out, d_out_length);
+    const octpt_status st = check_temporal(ctx, "temporal", false, p, d_color, g, prev, d_out, d_out_length);
     if (st != OCTPT_OK) return st;
     try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_temporal_device(ctx->sub[0], p, d_color, g, prev, d_out, d_out_length, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
-        DevTemporal T{};
-        T.W = p->width;
-        T.H = p->height;
-        T.dim = (float)(p->width > p->height ? p->width : p->height);
-        T.cur = dev_camera(p->camera);
-        T.prev = dev_camera(p->prev_camera);
-        T.max_history = p->max_history;
-        T.depth_tolerance = p->depth_tolerance;
-        T.normal_threshold = p->normal_threshold;
-        T.match_prim = match ? 1u : 0u;
-        T.color = reinterpret_cast<const float4 *>(d_color);
-        T.normal = reinterpret_cast<const float4 *>(g->normal);
-        T.depth = g->depth;
-        T.prim = match ? g->prim : nullptr;
-        if (prev) {
-            T.h_color = reinterpret_cast<const float4 *>(prev->color);
-            T.h_normal = reinterpret_cast<const float4 *>(prev->normal);
-            T.h_depth = prev->depth;
-            T.h_prim = match ? prev->prim : nullptr;
-            T.h_length = prev->length;
-        }
-        T.out = reinterpret_cast<float4 *>(d_out);
-        T.out_length = d_out_length;
-        HIP_TRY(ctx, launch_temporal(T, static_cast<hipStream_t>(stream)));
-        return OCTPT_OK;
+        return enqueue_temporal(ctx, p, d_color, g, prev, nullptr, d_out, d_out_length, nullptr, stream);
     } catch (...) {
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
     }
@@ -2423,47 +2510,242 @@ octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, cons
                             const octpt_aov_buffers *g, const octpt_temporal_history *prev, float *out,
                             uint32_t *out_length) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_temporal(ctx, p, color, g, prev, out, out_length);
+    const octpt_status st = check_temporal(ctx, "temporal", false, p, color, g, prev, out, out_length);
+    if (st != OCTPT_OK) return st;
+    try {
+        return temporal_host(ctx, p, color, g, prev, nullptr, out, out_length, nullptr);
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
+    }
+}
+
+// ---------------- luminance moments, variance and the variance-guided filter (C27-C29) ----------------
+octpt_status octpt_temporal_moments_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
+                                           const octpt_aov_buffers *g, const octpt_temporal_history *prev,
+                                           const float *d_prev_moments, float *d_out, uint32_t *d_out_length,
+                                           float *d_out_moments, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_temporal(ctx, "temporal_moments", true, p, d_color, g, prev, d_out, d_out_length);
+    if (st == OCTPT_OK) st = check_moments(ctx, prev, d_prev_moments, d_out_moments);
+    if (st != OCTPT_OK) return st;
+    try {
+        return enqueue_temporal(ctx, p, d_color, g, prev, d_prev_moments, d_out, d_out_length, d_out_moments, stream);
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal_moments");
+    }
+}
+
+octpt_status octpt_temporal_moments(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color,
+                                    const octpt_aov_buffers *g, const octpt_temporal_history *prev,
+                                    const float *prev_moments, float *out, uint32_t *out_length, float *out_moments) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_temporal(ctx, "temporal_moments", true, p, color, g, prev, out, out_length);
+    if (st == OCTPT_OK) st = check_moments(ctx, prev, prev_moments, out_moments);
+    if (st != OCTPT_OK) return st;
+    try {
+        return temporal_host(ctx, p, color, g, prev, prev_moments, out, out_length, out_moments);
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal_moments");
+    }
+}
+
+namespace {
+
+octpt_status check_variance(octpt_ctx *ctx, const octpt_variance_params *p, const void *moments, const void *length,
+                            const octpt_aov_buffers *g, const void *out) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance params NULL");
+    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: zero frame size");
+    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: bad resolution");
+    if (p->min_history < 1u || p->min_history > 65535u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: min_history must be 1..65535");
+    for (float s : {p->sigma_normal, p->sigma_depth})
+        if (!(s > 0.0f) || !std::isfinite(s))
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: sigma_normal and sigma_depth must be positive and finite");
+    if (!moments || !length || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: NULL moments, length or output buffer");
+    if (!g || !g->normal || !g->depth)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: the normal and depth guides are required");
+    return OCTPT_OK;
+}
+
+octpt_status check_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const void *color,
+                                    const void *variance, const octpt_aov_buffers *g, const void *out) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance params NULL");
+    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: zero frame size");
+    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: bad resolution");
+    if (p->iterations < 1u || p->iterations > 5u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: iterations must be 1..5");
+    for (float s : {p->sigma_luminance, p->luminance_floor, p->sigma_normal, p->sigma_depth})
+        if (!(s > 0.0f) || !std::isfinite(s))
+            return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                        "denoise_variance: sigma_luminance, luminance_floor, sigma_normal and sigma_depth must be positive and finite");
+    if (p->flags & ~OCTPT_DENOISE_DEMODULATE)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "denoise_variance: unknown flag (full frames only: no shard or compact tile layout; OCTPT_DENOISE_DEMODULATE is the one flag)");
+    if (!color || !variance || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: NULL colour, variance or output buffer");
+    if (!g || !g->normal || !g->depth)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: the normal and depth guides are required");
+    if ((p->flags & OCTPT_DENOISE_DEMODULATE) && !g->albedo)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: OCTPT_DENOISE_DEMODULATE needs the albedo guide");
+    return OCTPT_OK;
+}
+
+}  // namespace
+
+octpt_status octpt_variance_device(octpt_ctx *ctx, const octpt_variance_params *p, const float *d_moments,
+                                   const uint32_t *d_length, const octpt_aov_buffers *g, float *d_out, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_variance(ctx, p, d_moments, d_length, g, d_out);
     if (st != OCTPT_OK) return st;
     try {
         join_inflight(ctx);
         if (is_multi(ctx)) {
-            st = octpt_temporal(ctx->sub[0], p, color, g, prev, out, out_length);
+            st = octpt_variance_device(ctx->sub[0], p, d_moments, d_length, g, d_out, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        DevVariance V{};
+        V.W = p->width;
+        V.H = p->height;
+        V.min_history = p->min_history;
+        V.sn2 = p->sigma_normal * p->sigma_normal;
+        V.sz2 = p->sigma_depth * p->sigma_depth;
+        V.moments = reinterpret_cast<const float2 *>(d_moments);
+        V.length = d_length;
+        V.normal = reinterpret_cast<const float4 *>(g->normal);
+        V.depth = g->depth;
+        V.out = d_out;
+        HIP_TRY(ctx, launch_variance(V, static_cast<hipStream_t>(stream)));
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in variance");
+    }
+}
+
+octpt_status octpt_variance(octpt_ctx *ctx, const octpt_variance_params *p, const float *moments, const uint32_t *length,
+                            const octpt_aov_buffers *g, float *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_variance(ctx, p, moments, length, g, out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_variance(ctx->sub[0], p, moments, length, g, out);
             return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
         }
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         const size_t n = (size_t)p->width * p->height;
-        const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
-        // colour (blended in place on the device), normal, depth, prim; the history's five; the output length
-        const void *h[9] = {color, g->normal, g->depth, match ? g->prim : nullptr,
-                            prev ? prev->color : nullptr, prev ? prev->normal : nullptr, prev ? prev->depth : nullptr,
-                            prev && match ? prev->prim : nullptr, prev ? prev->length : nullptr};
-        const size_t bpp[9] = {16, 16, 4, 4, 16, 16, 4, 4, 4};
-        void *d[10] = {};
+        const void *h[4] = {moments, length, g->normal, g->depth};  // then the output
+        const size_t bpp[4] = {8, 4, 16, 4};
+        void *d[5] = {};
         hipError_t e = hipSuccess;
-        for (int i = 0; i < 9 && e == hipSuccess; ++i) {
-            if (!h[i]) continue;
+        for (int i = 0; i < 4 && e == hipSuccess; ++i)
             if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMalloc(&d[9], n * 4);
+        if (e == hipSuccess) e = hipMalloc(&d[4], n * 4);
         if (e == hipSuccess) {
-            const octpt_aov_buffers dg{nullptr, static_cast<float *>(d[1]), static_cast<float *>(d[2]),
-                                       static_cast<uint32_t *>(d[3]), nullptr};
-            const octpt_temporal_history dp{static_cast<float *>(d[4]), static_cast<float *>(d[5]), static_cast<float *>(d[6]),
-                                            static_cast<uint32_t *>(d[7]), static_cast<uint32_t *>(d[8])};
-            st = octpt_temporal_device(ctx, p, static_cast<float *>(d[0]), &dg, prev ? &dp : nullptr,
-                                       static_cast<float *>(d[0]), static_cast<uint32_t *>(d[9]), ctx->stream);
+            const octpt_aov_buffers dg{nullptr, static_cast<float *>(d[2]), static_cast<float *>(d[3]), nullptr, nullptr};
+            st = octpt_variance_device(ctx, p, static_cast<float *>(d[0]), static_cast<uint32_t *>(d[1]), &dg,
+                                       static_cast<float *>(d[4]), ctx->stream);
             if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out_length, d[9], n * 4, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[4], n * 4, hipMemcpyDeviceToHost);
         }
         for (void *q : d)
             if (q) (void)hipFree(q);
         if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "temporal");
+        if (e != hipSuccess) return hip_fail(ctx, e, "variance");
         return OCTPT_OK;
     } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in variance");
+    }
+}
+
+octpt_status octpt_denoise_variance_device(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const float *d_color,
+                                           const float *d_variance, const octpt_aov_buffers *g, float *d_out,
+                                           float *d_out_variance, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_denoise_variance(ctx, p, d_color, d_variance, g, d_out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_denoise_variance_device(ctx->sub[0], p, d_color, d_variance, g, d_out, d_out_variance, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        // octpt_denoise_device's two frames and its rule: (s.rgb, v) lives in frame 0 after the prep pass, then
+        // ping-pongs; the last iteration writes the caller's buffers.  A frame that has to grow may still be read by
+        // an earlier call on another stream: drain first
+        const bool two = p->iterations > 1u;
+        if (n > ctx->dn_cap[0] || (two && n > ctx->dn_cap[1])) HIP_TRY(ctx, hipDeviceSynchronize());
+        if ((st = grow_buf(ctx, ctx->dn_frame[0], ctx->dn_cap[0], n)) != OCTPT_OK) return st;
+        if (two && (st = grow_buf(ctx, ctx->dn_frame[1], ctx->dn_cap[1], n)) != OCTPT_OK) return st;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        DevDenoiseVar D{};
+        D.W = p->width;
+        D.H = p->height;
+        D.sigma_luminance = p->sigma_luminance;
+        D.luminance_floor = p->luminance_floor;
+        D.sn2 = p->sigma_normal * p->sigma_normal;
+        D.sz2 = p->sigma_depth * p->sigma_depth;
+        D.normal = reinterpret_cast<const float4 *>(g->normal);
+        D.albedo = (p->flags & OCTPT_DENOISE_DEMODULATE) ? reinterpret_cast<const float4 *>(g->albedo) : nullptr;
+        D.depth = g->depth;
+        D.color = reinterpret_cast<const float4 *>(d_color);
+        D.out = reinterpret_cast<float4 *>(d_out);
+        D.out_variance = d_out_variance;
+        HIP_TRY(ctx, launch_denoise_var_prep(D.W, D.H, D.color, d_variance, D.albedo, D.depth, ctx->dn_frame[0], s));
+        for (uint32_t i = 0; i < p->iterations; ++i) {
+            const bool last = i + 1u == p->iterations;
+            HIP_TRY(ctx, launch_atrous_var(D, i, last, ctx->dn_frame[i & 1u], last ? nullptr : ctx->dn_frame[(i + 1u) & 1u], s));
+        }
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise_variance");
+    }
+}
+
+octpt_status octpt_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const float *color,
+                                    const float *variance, const octpt_aov_buffers *g, float *out, float *out_variance) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_denoise_variance(ctx, p, color, variance, g, out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_denoise_variance(ctx->sub[0], p, color, variance, g, out, out_variance);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
+        // colour and variance (both filtered in place on the device), normal, depth, albedo
+        const void *h[5] = {color, variance, g->normal, g->depth, demod ? g->albedo : nullptr};
+        const size_t bpp[5] = {16, 4, 16, 4, 16};
+        void *d[5] = {};
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 5 && e == hipSuccess; ++i) {
+            if (!h[i]) continue;
+            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) {
+            const octpt_aov_buffers dg{static_cast<float *>(d[4]), static_cast<float *>(d[2]), static_cast<float *>(d[3]),
+                                       nullptr, nullptr};
+            st = octpt_denoise_variance_device(ctx, p, static_cast<float *>(d[0]), static_cast<float *>(d[1]), &dg,
+                                               static_cast<float *>(d[0]), out_variance ? static_cast<float *>(d[1]) : nullptr,
+                                               ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && out_variance) e = hipMemcpy(out_variance, d[1], n * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "denoise_variance");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise_variance");
     }
 }
 

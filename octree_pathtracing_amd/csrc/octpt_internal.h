@@ -199,6 +199,35 @@ struct DevTemporal {
     const uint32_t *h_prim, *h_length;
     float4 *out;
     uint32_t *out_length;
+    // C27, read by the moments instance alone: the history's and the output's (m1, m2) planes, and the albedo
+    // guide with OCTPT_TEMPORAL_DEMODULATE (NULL without)
+    const float4 *albedo;
+    const float2 *h_moments;
+    float2 *out_moments;
+};
+
+// one variance estimate (octpt_variance_params + the buffers), DESIGN.md C28
+struct DevVariance {
+    uint32_t W, H;
+    uint32_t min_history;
+    float sn2, sz2;                     // sigma_normal^2, sigma_depth^2
+    const float2 *moments;
+    const uint32_t *length;
+    const float4 *normal;
+    const float *depth;
+    float *out;
+};
+
+// one variance-guided denoise call (octpt_denoise_variance_params + the guides), DESIGN.md C29
+struct DevDenoiseVar {
+    uint32_t W, H;
+    float sigma_luminance, luminance_floor;
+    float sn2, sz2;                     // sigma_normal^2, sigma_depth^2
+    const float4 *normal, *albedo;      // albedo: NULL without OCTPT_DENOISE_DEMODULATE
+    const float *depth;
+    const float4 *color;                // the input frame: its alpha, read by the last pass alone
+    float4 *out;                        // the caller's frame, written by the last pass (may be `color`)
+    float *out_variance;                // nullable; written by the last pass
 };
 
 // frame tile at dealing position s (octpt_set_tile_order's permutation, or s itself)
@@ -349,8 +378,18 @@ hipError_t launch_denoise_prep(uint32_t W, uint32_t H, const float4 *color, cons
                                float4 *sig, hipStream_t stream);
 hipError_t launch_atrous(const DevDenoise &D, uint32_t iter, bool last, const float4 *src, float4 *dst,
                          hipStream_t stream);
-// temporal reprojection: one launch, one thread per pixel of the current frame
-hipError_t launch_temporal(const DevTemporal &T, hipStream_t stream);
+// temporal reprojection: one launch, one thread per pixel of the current frame; moments: the
+// instance that also carries the luminance moments (C27)
+hipError_t launch_temporal(const DevTemporal &T, bool moments, hipStream_t stream);
+// the variance estimate of C28: one launch, one thread per pixel
+hipError_t launch_variance(const DevVariance &V, hipStream_t stream);
+// the variance-guided a-trous filter.  prep: (color, variance) -> sig = (s.rgb, v), the working
+// signal as launch_denoise_prep makes it with the variance in w.  atrous_var: one iteration src -> the next
+// working frame dst, or with last (dst ignored) into D.out / D.out_variance
+hipError_t launch_denoise_var_prep(uint32_t W, uint32_t H, const float4 *color, const float *variance,
+                                   const float4 *albedo, const float *depth, float4 *sig, hipStream_t stream);
+hipError_t launch_atrous_var(const DevDenoiseVar &D, uint32_t iter, bool last, const float4 *src, float4 *dst,
+                             hipStream_t stream);
 hipError_t launch_tonemap(const float4 *accum, uchar4 *out, uint32_t n, const uint8_t *lut_byte,
                           hipStream_t stream);
 hipError_t launch_unshard(uint32_t W, uint32_t H, uint32_t shard_count, const uint32_t *tile_pos, const float4 *shards,

@@ -79,6 +79,11 @@ class FrameInFlight:
         self._r._lib.octpt_frame_cancel(self._h)
 
 
+# denoise_variance's default luminance_floor: the smallest power of ten at which the filter's f32
+# arithmetic stays well conditioned on low-spp frames (tests/test_gpu_svgf.py states the condition)
+LUMINANCE_FLOOR = 1e-2
+
+
 class HipRenderer:
     """RenderingBackend implemented on one MI355X (HIP device `device`), or on several GPUs of the node
     through one context (`devices`: a list of HIP device ids, octpt_create_multi; ids may repeat)."""
@@ -401,12 +406,17 @@ class HipRenderer:
     # ------------------------------------------------------------ temporal reprojection (C26)
     def temporal(self, color: np.ndarray, aov: dict, history: dict | None = None, prev_camera: Camera | None = None,
                  max_history: int = 32, depth_tolerance: float = 0.1, normal_threshold: float = 0.9,
-                 match_prim: bool = True) -> dict:
+                 match_prim: bool = True, moments: bool = False, demodulate: bool = False) -> dict:
         """Carry `history` (the dict a previous call returned, None on the first frame) to the current camera's
         frame and blend the new [H, W, 4] `color` into it (octpt_temporal), guided by render_aov's normal, depth
         and (with match_prim) prim of the current frame.  prev_camera: the history's camera, by default the one
         it recorded.  Returns the new history: color (the blended frame, what denoise takes next), normal, depth,
-        prim, length (u32 [H, W]: samples of history per pixel, 0 on misses) and camera."""
+        prim, length (u32 [H, W]: samples of history per pixel, 0 on misses) and camera.
+        moments: octpt_temporal_moments (C27) -- the luminance moments [H, W, 2] of the working signal travel with
+        the colour: read from history["moments"], returned as "moments"; demodulate (only with moments): the
+        working signal is color / max(albedo, 1e-3), as denoise_variance's is."""
+        if demodulate and not moments:
+            raise ValueError("demodulate applies to the moments (moments=True)")
         color = np.ascontiguousarray(color, np.float32)
         H, W = color.shape[:2]
         keep = []
@@ -415,14 +425,15 @@ class HipRenderer:
             if src.get(name) is None:
                 return None  # the library reports what is missing
             a = np.ascontiguousarray(src[name], dt)
-            if a.size != W * H * (4 if name in ("color", "normal") else 1):
+            if a.size != W * H * {"color": 4, "normal": 4, "albedo": 4, "moments": 2}.get(name, 1):
                 raise ValueError(f"{name} does not match the {W} x {H} frame")
             keep.append(a)
             return a.ctypes.data
 
         names = ("normal", "depth") + (("prim",) if match_prim else ())
-        dtype = {"color": np.float32, "normal": np.float32, "depth": np.float32, "prim": np.uint32, "length": np.uint32}
-        g = _lib.AovBuffers(**{k: ptr(aov, k, dtype[k]) for k in names})
+        dtype = {"color": np.float32, "normal": np.float32, "depth": np.float32, "prim": np.uint32, "length": np.uint32,
+                 "albedo": np.float32, "moments": np.float32}
+        g = _lib.AovBuffers(**{k: ptr(aov, k, dtype[k]) for k in names + (("albedo",) if demodulate else ())})
         prev = None
         if history is not None:
             prev = _lib.TemporalHistory(**{k: ptr(history, k, dtype[k]) for k in ("color", "length") + names})
@@ -432,11 +443,21 @@ class HipRenderer:
                                 normal_threshold, _lib.TEMPORAL_MATCH_PRIM if match_prim else 0)
         out = np.empty_like(color)
         length = np.empty((H, W), np.uint32)
+        res = {"color": out, "normal": aov.get("normal"), "depth": aov.get("depth"), "prim": aov.get("prim"),
+               "length": length, "camera": cam}
+        if moments:
+            p.flags |= _lib.TEMPORAL_DEMODULATE if demodulate else 0
+            res["moments"] = np.empty((H, W, 2), np.float32)
+            self._check(self._lib.octpt_temporal_moments(
+                self._ctx, C.byref(p), color.ctypes.data_as(C.c_void_p), C.byref(g),
+                C.byref(prev) if prev is not None else None,
+                ptr(history, "moments", np.float32) if history is not None else None, out.ctypes.data_as(C.c_void_p),
+                length.ctypes.data_as(C.c_void_p), res["moments"].ctypes.data_as(C.c_void_p)))
+            return res
         self._check(self._lib.octpt_temporal(self._ctx, C.byref(p), color.ctypes.data_as(C.c_void_p), C.byref(g),
                                              C.byref(prev) if prev is not None else None,
                                              out.ctypes.data_as(C.c_void_p), length.ctypes.data_as(C.c_void_p)))
-        return {"color": out, "normal": aov.get("normal"), "depth": aov.get("depth"), "prim": aov.get("prim"),
-                "length": length, "camera": cam}
+        return res
 
     def temporal_device(self, params: "_lib.TemporalParams", d_color: int, guides: dict, prev: dict | None, d_out: int,
                         d_out_length: int, stream: int | None = None) -> None:
@@ -447,6 +468,88 @@ class HipRenderer:
         self._check(self._lib.octpt_temporal_device(self._ctx, C.byref(params), C.c_void_p(d_color), C.byref(b),
                                                     C.byref(h) if h is not None else None, C.c_void_p(d_out),
                                                     C.c_void_p(d_out_length), C.c_void_p(stream) if stream else None))
+
+    def temporal_moments_device(self, params: "_lib.TemporalParams", d_color: int, guides: dict, prev: dict | None,
+                                d_prev_moments: int | None, d_out: int, d_out_length: int, d_out_moments: int,
+                                stream: int | None = None) -> None:
+        """Enqueue octpt_temporal_moments_device on raw device pointers: temporal_device's arguments (guides with
+        albedo under TEMPORAL_DEMODULATE) and the previous and the output moments planes."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in guides.items() if v})
+        h = _lib.TemporalHistory(**{k: C.c_void_p(int(v)) for k, v in prev.items() if v}) if prev is not None else None
+        self._check(self._lib.octpt_temporal_moments_device(
+            self._ctx, C.byref(params), C.c_void_p(d_color), C.byref(b), C.byref(h) if h is not None else None,
+            C.c_void_p(d_prev_moments) if d_prev_moments else None, C.c_void_p(d_out), C.c_void_p(d_out_length),
+            C.c_void_p(d_out_moments), C.c_void_p(stream) if stream else None))
+
+    # ------------------------------------------------------------ variance and the variance-guided filter (C28, C29)
+    def _guides(self, aov: dict, names, W: int, H: int, keep: list) -> "_lib.AovBuffers":
+        b = _lib.AovBuffers()
+        for name in names:
+            if aov.get(name) is None:
+                continue  # the library reports the missing guide
+            a = np.ascontiguousarray(aov[name], np.float32)
+            if a.size != W * H * (1 if name == "depth" else 4):
+                raise ValueError(f"{name} guide does not match the {W} x {H} frame")
+            keep.append(a)
+            setattr(b, name, a.ctypes.data)
+        return b
+
+    def variance(self, history: dict, aov: dict, min_history: int = 4, sigma_normal: float = 0.3,
+                 sigma_depth: float = 0.1) -> np.ndarray:
+        """The per-pixel variance [H, W] of the working signal's luminance (octpt_variance) from the moments and
+        length of `history` (what temporal(..., moments=True) returned) and render_aov's normal and depth: the
+        temporal estimate where the history is min_history long, a 7 x 7 spatial one where it is shorter."""
+        length = np.ascontiguousarray(history["length"], np.uint32)
+        H, W = length.shape
+        m = np.ascontiguousarray(history["moments"], np.float32)
+        if m.size != 2 * W * H:
+            raise ValueError(f"moments do not match the {W} x {H} frame")
+        keep = []
+        b = self._guides(aov, ("normal", "depth"), W, H, keep)
+        p = _lib.VarianceParams(W, H, min_history, sigma_normal, sigma_depth)
+        out = np.empty((H, W), np.float32)
+        self._check(self._lib.octpt_variance(self._ctx, C.byref(p), m.ctypes.data_as(C.c_void_p),
+                                             length.ctypes.data_as(C.c_void_p), C.byref(b),
+                                             out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def variance_device(self, params: "_lib.VarianceParams", d_moments: int, d_length: int, guides: dict, d_out: int,
+                        stream: int | None = None) -> None:
+        """Enqueue octpt_variance_device on raw device pointers: guides {normal, depth}."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in guides.items() if v})
+        self._check(self._lib.octpt_variance_device(self._ctx, C.byref(params), C.c_void_p(d_moments),
+                                                    C.c_void_p(d_length), C.byref(b), C.c_void_p(d_out),
+                                                    C.c_void_p(stream) if stream else None))
+
+    def denoise_variance(self, color: np.ndarray, variance: np.ndarray, aov: dict, iterations: int = 5,
+                         sigma_luminance: float = 4.0, luminance_floor: float = LUMINANCE_FLOOR,
+                         sigma_normal: float = 0.3, sigma_depth: float = 0.1, demodulate: bool = True):
+        """The variance-guided a-trous filter (octpt_denoise_variance) of a [H, W, 4] frame and its [H, W]
+        variance (variance()'s), guided by render_aov's normal and depth (and albedo with demodulate) ->
+        (filtered frame, filtered variance)."""
+        color = np.ascontiguousarray(color, np.float32)
+        H, W = color.shape[:2]
+        variance = np.ascontiguousarray(variance, np.float32)
+        if variance.size != W * H:
+            raise ValueError(f"variance does not match the {W} x {H} frame")
+        keep = []
+        b = self._guides(aov, ("normal", "depth") + (("albedo",) if demodulate else ()), W, H, keep)
+        p = _lib.DenoiseVarianceParams(W, H, iterations, sigma_luminance, luminance_floor, sigma_normal, sigma_depth,
+                                       _lib.DENOISE_DEMODULATE if demodulate else 0)
+        out, out_var = np.empty_like(color), np.empty((H, W), np.float32)
+        self._check(self._lib.octpt_denoise_variance(self._ctx, C.byref(p), color.ctypes.data_as(C.c_void_p),
+                                                     variance.ctypes.data_as(C.c_void_p), C.byref(b),
+                                                     out.ctypes.data_as(C.c_void_p), out_var.ctypes.data_as(C.c_void_p)))
+        return out, out_var
+
+    def denoise_variance_device(self, params: "_lib.DenoiseVarianceParams", d_color: int, d_variance: int, guides: dict,
+                                d_out: int, d_out_variance: int | None = None, stream: int | None = None) -> None:
+        """Enqueue octpt_denoise_variance_device on raw device pointers (d_out may equal d_color, d_out_variance
+        d_variance or None)."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in guides.items() if v})
+        self._check(self._lib.octpt_denoise_variance_device(
+            self._ctx, C.byref(params), C.c_void_p(d_color), C.c_void_p(d_variance), C.byref(b), C.c_void_p(d_out),
+            C.c_void_p(d_out_variance) if d_out_variance else None, C.c_void_p(stream) if stream else None))
 
     def stats(self) -> dict:
         s = _lib.Stats()
