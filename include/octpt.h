@@ -549,6 +549,92 @@ octpt_status octpt_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance
                                     const float *variance, const octpt_aov_buffers *guides, float *out,
                                     float *out_variance);
 
+/* --- adaptive sampling: tile-list renders, sample moments and the per-tile error ---
+ * The final-quality counterpart of the chain above: instead of one spp_count for every pixel, render until the noise
+ * of each 8x8 tile is below a threshold.  Converged tiles (sky, flat directly lit surfaces) stop after a few samples
+ * and the budget goes to the tiles that need it (penumbrae, glossy surfaces, emitters).  Three layers: a render entry
+ * that takes a list of tiles (C30), the luminance moments of the *samples* kept by resolve (C31; C27's are moments of
+ * frames), and a per-tile error with the driver that loops render -> estimate -> drop converged tiles (C32).  Tiles
+ * are the wavefront's own: frame tile t = ty * ceil(width / 8) + tx. */
+
+/* C30.  octpt_render_device's spp_count more samples into the listed tiles only.  tiles: a host array of n_tiles
+ * distinct frame tile indices in any order, copied by the call (it may be freed on return); NULL = every tile, in
+ * frame order (n_tiles is then ignored).  d_accum and d_seg_count (nullable) are full frames as octpt_render_device
+ * takes them; d_moments (nullable) holds 2 floats / pixel, full frame, image order (C31).  For every pixel of a
+ * listed tile accum, seg_count and moments are afterwards what a full-frame call with the same parameters leaves
+ * there -- accum and seg_count bit for bit octpt_render_device's, since the per-pixel RNG streams are keyed by
+ * (pixel, sample) -- and every pixel of an unlisted tile keeps all three untouched, bit for bit.  octpt_stats counts
+ * the listed tiles' paths only.  The list is the deal of a one-shard render, so seed, extend, shade, drain and resolve
+ * run as in any render; branch_count > 1 follows octpt_render_params' pass-boundary rules.  The wavefront state is
+ * grow-only: calls with shrinking lists do not reallocate it (octpt_stats.wave_allocs).
+ * INVALID_ARG, checked on the host before anything is launched (the buffers stay untouched): a tile index >= the
+ * frame's tile count or a duplicate; shard_count != 1, OCTPT_RENDER_SHARD_COMPACT, or a tile order set on the context.
+ * UNSUPPORTED: OCTPT_RENDER_MEGAKERNEL, OCTPT_RENDER_PREVIEW, a multi-device context.  tiles != NULL with n_tiles == 0:
+ * OK, nothing is launched.  Like octpt_render_device the call returns once the last kernel is enqueued on `hip_stream`. */
+octpt_status octpt_render_tiles_device(octpt_ctx *ctx, const octpt_render_params *p, const uint32_t *tiles,
+                                       uint32_t n_tiles, float *d_accum, float *d_moments, uint32_t *d_seg_count,
+                                       void *hip_stream);
+
+/* C31.  The moments octpt_render_tiles_device keeps with d_moments set: per pixel the running means (m1, m2) of l and
+ * l * l over the samples, l = (0.2126 r + 0.7152 g) + 0.0722 b (C27's expression) of each sample's colour, updated in
+ * sample order with the colour's own running-mean formula and weights: m = (m * (float)spp + v * (float)bc) *
+ * (1.0f / (float)(bc + spp)), spp = the samples held, bc = 1 -- or, with a branch schedule, the pass's branch count,
+ * the sample then being the pass's folded colour.  A render with spp_start == 0 starts them from (0, 0) as it starts
+ * accum from black; accum is bit for bit the same with and without d_moments. */
+
+/* C32.  The error of every 8x8 tile from C31's moments, one float per tile in frame tile order: the standard error of
+ * the tile's mean luminance relative to that luminance.  Tile t covers P pixels inside the image (1..64) and holds
+ * n = tile_spp[t] samples per pixel.  n < 2: +inf.  Else, per pixel v = max(m2 - m1 * m1, 0) (a NaN stays one), Sv =
+ * the sum of v and Sl = the sum of m1 over the tile's pixels inside the image (f32, summation order unspecified), and
+ * error = sqrtf((Sv / P) / (float)(n - 1)) / (Sl / P + luminance_floor); a result that is not finite is +inf. */
+typedef struct octpt_tile_error_params {
+    uint32_t width, height;
+    float luminance_floor; /* > 0, finite */
+} octpt_tile_error_params;
+/* Device buffers: d_moments width * height * 2 floats, d_tile_spp and d_error one entry per tile.  One launch on
+ * `hip_stream`, no host synchronisation, no memory of the context's; on a multi-device context it runs on devices[0]. */
+octpt_status octpt_tile_error_device(octpt_ctx *ctx, const octpt_tile_error_params *p, const float *d_moments,
+                                     const uint32_t *d_tile_spp, float *d_error, void *hip_stream);
+/* The same over host arrays. */
+octpt_status octpt_tile_error(octpt_ctx *ctx, const octpt_tile_error_params *p, const float *moments,
+                              const uint32_t *tile_spp, float *error);
+
+/* The adaptive driver: a fresh render (p->spp_start must be 0) of at most max_spp = p->spp_count samples per pixel
+ * (>= min_spp).  accum and moments are outputs, initialised by the call to (0, 0, 0, 1) and (0, 0).  The loop, which
+ * is the definition of the result:
+ *   1. active = every tile, n = 0;
+ *   2. each round k = min(n == 0 ? min_spp : step_spp, max_spp - n);
+ *   3. octpt_render_tiles_device(active, spp_start = n, spp_count = k);
+ *   4. n += k, tile_spp[t] = n for the active tiles t;
+ *   5. the error (above) of the active tiles;
+ *   6. active = the tiles of active with error > threshold, in frame order;
+ *   7. stop when active is empty or n == max_spp.
+ * All active tiles share one n, so a round is one render call and no per-tile sample key enters the kernels; the host
+ * reads one float per tile back per round (the wavefront loop is host-steered already).  result (nullable): rounds
+ * run, tile_samples = the sum of tile_spp, converged_tiles = tiles whose last error was <= threshold, total_tiles.
+ * UNSUPPORTED: branch_count > 1 (its pass boundaries fix the round sizes).  octpt_render_tiles_device's refusals
+ * apply; min_spp < 2, step_spp < 1, a threshold or luminance_floor that is not positive and finite: INVALID_ARG. */
+typedef struct octpt_adaptive_params {
+    uint32_t min_spp;      /* >= 2: the first round's samples */
+    uint32_t step_spp;     /* >= 1: every later round's */
+    float threshold;       /* > 0, finite: a tile stops once its error is <= it */
+    float luminance_floor; /* > 0, finite */
+} octpt_adaptive_params;
+typedef struct octpt_adaptive_result {
+    uint32_t rounds;
+    uint64_t tile_samples;
+    uint32_t converged_tiles, total_tiles;
+} octpt_adaptive_result;
+/* d_accum, d_moments: device, full frames; d_seg_count: nullable, device, += ray segments; tile_spp: host, out, one
+ * entry per tile.  The rounds run on `hip_stream`, which the call drains once per round. */
+octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
+                                          float *d_accum, float *d_moments, uint32_t *d_seg_count, uint32_t *tile_spp,
+                                          octpt_adaptive_result *result, void *hip_stream);
+/* The same into host arrays; moments, tile_spp, out_rgba8 (the tone-mapped final accum) and result are nullable. */
+octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
+                                   float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
+                                   octpt_adaptive_result *result);
+
 /* --- host octree builder (replaces the Rust-side build for primitive scenes) ---
  * Voxelises spheres/cuboids into depth-`depth` leaf cells, Morton-sorts
  * them (new_octree.rs:752-835 code order) and emits octants in pre-order. */

@@ -232,6 +232,29 @@ class DenoiseVarianceParams(C.Structure):
                 ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
 
 
+class TileErrorParams(C.Structure):
+    """octpt_tile_error_params."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("luminance_floor", C.c_float)]
+
+
+class AdaptiveParams(C.Structure):
+    """octpt_adaptive_params."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float),
+                ("luminance_floor", C.c_float)]
+
+
+class AdaptiveResult(C.Structure):
+    """octpt_adaptive_result."""
+    _fields_ = [("rounds", C.c_uint32), ("tile_samples", C.c_uint64), ("converged_tiles", C.c_uint32),
+                ("total_tiles", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+TILE = 8  # the wavefront's 8x8 pixel tiles: frame tile t = ty * ceil(W / TILE) + tx (C30)
+
+
 # octpt_stats::drain order (OCTPT_STAT_*)
 STAT_NAMES = ("paths", "segments", "esvo_steps", "sphere_tests", "cuboid_tests", "shade_events", "texel_reads",
               "block_tests", "issued_bytes")
@@ -307,6 +330,13 @@ SIGNATURES = {
                                              _vp, _vp, _vp]),
     "octpt_denoise_variance": (_i32, [_vp, C.POINTER(DenoiseVarianceParams), _vp, _vp, C.POINTER(AovBuffers), _vp,
                                       _vp]),
+    "octpt_render_tiles_device": (_i32, [_vp, C.POINTER(RenderParams), _vp, _u32, _vp, _vp, _vp, _vp]),
+    "octpt_tile_error_device": (_i32, [_vp, C.POINTER(TileErrorParams), _vp, _vp, _vp, _vp]),
+    "octpt_tile_error": (_i32, [_vp, C.POINTER(TileErrorParams), _vp, _vp, _vp]),
+    "octpt_render_adaptive_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp,
+                                            C.POINTER(AdaptiveResult), _vp]),
+    "octpt_render_adaptive": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp,
+                                     C.POINTER(AdaptiveResult)]),
     "octpt_reproject_coords": (_i32, [C.POINTER(Camera), C.POINTER(Camera), _u32, _u32, _vp, _vp, _vp]),
     "octpt_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "octpt_reset_stats": (_i32, [_vp]),

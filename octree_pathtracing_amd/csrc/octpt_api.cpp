@@ -149,13 +149,25 @@ struct octpt_ctx {
     uint64_t scene_gen = 0, camera_gen = 0, order_gen = 0;
     struct BeamKey {
         uint64_t scene = 0, camera = 0, order = 0;
+        // a tile-list render (octpt_render_tiles_device) computes only its tiles' starts: its list's number, a
+        // fresh one per call (0 = an ordinary render), so that no render takes such a table for its own
+        uint64_t list = 0;
         uint32_t w = 0, h = 0, shard_index = 0, shard_count = 0;
         bool valid = false;
         bool operator==(const BeamKey &o) const {
-            return valid && o.valid && scene == o.scene && camera == o.camera && order == o.order && w == o.w &&
-                   h == o.h && shard_index == o.shard_index && shard_count == o.shard_count;
+            return valid && o.valid && scene == o.scene && camera == o.camera && order == o.order && list == o.list &&
+                   w == o.w && h == o.h && shard_index == o.shard_index && shard_count == o.shard_count;
         }
     } beam_key;
+    // tile-list renders (C30): the list as the deal (DevRender::tile_order), grow-only like d_subs, and the
+    // number of the last list (BeamKey::list)
+    uint32_t *d_tiles = nullptr;
+    size_t tiles_cap = 0;
+    uint64_t list_gen = 0;
+    // the adaptive driver (C32): its device copies of tile_spp and the per-tile error, grow-only
+    uint32_t *d_tile_spp = nullptr;
+    float *d_tile_err = nullptr;
+    size_t tile_spp_cap = 0, tile_err_cap = 0;
     // recorded on the stream that computed the table: a render on another stream that reuses it waits for it
     hipEvent_t beam_ev = nullptr;
     hipStream_t beam_stream = nullptr;  // the stream the valid table was computed on
@@ -921,8 +933,10 @@ octpt_status enqueue_megakernel(octpt_ctx *ctx, const DevRender &R, float4 *d_ac
 // wavefront path tracer: per chunk of passes, seed the path pool, then
 // alternate extend/shade until the ray queue drains, then resolve the running means.  The
 // host steers the loop with a one-iteration lookahead on the queue length.
+// d_moments (nullable): resolve's moments instance (C31).  list: the number of a tile-list render's list (C30), 0 for
+// every other render.
 octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_accum, uint32_t *d_seg, hipStream_t s,
-                               const std::atomic<bool> *cancel) {
+                               const std::atomic<bool> *cancel, float2 *d_moments = nullptr, uint64_t list = 0) {
     const uint64_t n_px = R.total_items;
     uint32_t chunk_spp = 1;
     uint64_t chunk_max = 0;
@@ -999,7 +1013,15 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         key.h = R.H;
         key.shard_index = R.shard_index;
         key.shard_count = R.shard_count;
+        key.list = list;
         key.valid = true;
+        if (list != 0u) {
+            // a tile list reads a subset of the whole frame's table: one computed by an ordinary one-shard render
+            // of this scene, camera and size serves it (the adaptive driver's later rounds) and stays as it is
+            octpt_ctx::BeamKey whole = key;
+            whole.list = 0u;
+            if (whole == ctx->beam_key) key = whole;
+        }
         if (n_tiles > ctx->beam_cap) {
             HIP_TRY(ctx, hipDeviceSynchronize());  // an earlier render may still read the table
             if (ctx->d_beam) (void)hipFree(ctx->d_beam);
@@ -1102,13 +1124,14 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                 }
             }
         }
-        HIP_TRY(ctx, launch_wf_resolve(Rc, B, Rc.spp_count, d_accum, d_seg, s));
+        HIP_TRY(ctx, launch_wf_resolve(Rc, B, Rc.spp_count, d_accum, d_seg, d_moments, s));
     }
     return OCTPT_OK;
 }
 
 octpt_status enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d_accum, uint32_t *d_seg, hipStream_t s,
-                            bool megakernel, const std::atomic<bool> *cancel = nullptr) {
+                            bool megakernel, const std::atomic<bool> *cancel = nullptr, float2 *d_moments = nullptr,
+                            uint64_t list = 0) {
     if (R.spp_count == 0 || R.total_items == 0) return OCTPT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     EventPair ev{};
@@ -1122,7 +1145,7 @@ octpt_status enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d_accum,
         if (e != hipSuccess) st = hip_fail(ctx, e, "preview launch");
     } else {
         st = megakernel ? enqueue_megakernel(ctx, R, d_accum, d_seg, s)
-                        : enqueue_wavefront(ctx, R, d_accum, d_seg, s, cancel);
+                        : enqueue_wavefront(ctx, R, d_accum, d_seg, s, cancel, d_moments, list);
     }
     HIP_TRY(ctx, hipEventRecord(ev.stop, s));
     if (st == OCTPT_OK) ctx->launches++;
@@ -1609,6 +1632,9 @@ void octpt_destroy(octpt_ctx *ctx) {
     if (ctx->beam_ev) (void)hipEventDestroy(ctx->beam_ev);
     if (ctx->d_order) (void)hipFree(ctx->d_order);
     if (ctx->d_order_pos) (void)hipFree(ctx->d_order_pos);
+    if (ctx->d_tiles) (void)hipFree(ctx->d_tiles);
+    if (ctx->d_tile_spp) (void)hipFree(ctx->d_tile_spp);
+    if (ctx->d_tile_err) (void)hipFree(ctx->d_tile_err);
     if (ctx->m_acc) (void)hipFree(ctx->m_acc);
     if (ctx->m_seg) (void)hipFree(ctx->m_seg);
     for (float4 *f : ctx->dn_frame)
@@ -2746,6 +2772,264 @@ octpt_status octpt_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance
         return OCTPT_OK;
     } catch (...) {
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise_variance");
+    }
+}
+
+// ---------------- adaptive sampling: tile-list renders, sample moments, per-tile error ----------------
+namespace {
+
+// what a tile-list render refuses of the render parameters and the context (C30), before anything else is read
+octpt_status check_tile_render(octpt_ctx *ctx, const char *who, const octpt_render_params *p) {
+    const std::string w(who);
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + ": render params NULL");
+    if (p->flags & (OCTPT_RENDER_MEGAKERNEL | OCTPT_RENDER_PREVIEW))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + ": the wavefront path only (no megakernel, no preview)");
+    if (is_multi(ctx)) return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + ": not on a multi-device context");
+    if (p->shard_count != 1u || p->shard_index != 0u || (p->flags & OCTPT_RENDER_SHARD_COMPACT))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + ": full frames of one shard only (shard_count 1, no compact layout)");
+    if (!ctx->h_order.empty())
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + ": a tile order is set on the context (octpt_set_tile_order; NULL resets it)");
+    return OCTPT_OK;
+}
+
+// octpt_render_tiles_device after its NULL checks
+octpt_status render_tiles(octpt_ctx *ctx, const octpt_render_params *p, const uint32_t *tiles, uint32_t n_tiles,
+                          float4 *d_accum, float2 *d_moments, uint32_t *d_seg, hipStream_t s) {
+    octpt_status st = check_tile_render(ctx, "render_tiles", p);
+    if (st != OCTPT_OK) return st;
+    join_inflight(ctx);
+    DevRender R{};
+    if ((st = make_render(ctx, p, R)) != OCTPT_OK) return st;
+    uint64_t list = 0;
+    if (tiles) {
+        const uint32_t T = R.tiles_x * ((R.H + kTile - 1) / kTile);
+        if (n_tiles > T) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_tiles: more tiles than the frame has (a duplicate)");
+        std::vector<uint8_t> seen(T, 0);
+        for (uint32_t i = 0; i < n_tiles; ++i) {
+            if (tiles[i] >= T) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_tiles: tile index outside the frame");
+            if (seen[tiles[i]]) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_tiles: duplicate tile index");
+            seen[tiles[i]] = 1;
+        }
+        if (n_tiles == 0 || p->spp_count == 0) return OCTPT_OK;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        // the list is the deal.  An earlier render on any stream may still read the table: drain before overwriting
+        // it, as the branch schedule's and the tile order's tables do
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        if ((st = grow_buf(ctx, ctx->d_tiles, ctx->tiles_cap, (size_t)n_tiles)) != OCTPT_OK) return st;
+        HIP_TRY(ctx, hipMemcpy(ctx->d_tiles, tiles, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        R.tile_order = ctx->d_tiles;
+        R.shard_tiles = n_tiles;
+        R.total_items = n_tiles * 64u;
+        R.div_items = udiv_magic(R.total_items);
+        list = ++ctx->list_gen;
+    }
+    return enqueue_render(ctx, R, d_accum, d_seg, s, false, nullptr, d_moments, list);
+}
+
+octpt_status check_tile_error(octpt_ctx *ctx, const octpt_tile_error_params *p, const void *moments, const void *tile_spp,
+                              const void *error) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error params NULL");
+    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error: bad resolution");
+    if (!(p->luminance_floor > 0.0f) || !std::isfinite(p->luminance_floor))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error: luminance_floor must be positive and finite");
+    if (!moments || !tile_spp || !error)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error: NULL moments, tile_spp or error buffer");
+    return OCTPT_OK;
+}
+
+uint32_t frame_tiles(uint32_t W, uint32_t H) { return ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile); }
+
+}  // namespace
+
+octpt_status octpt_render_tiles_device(octpt_ctx *ctx, const octpt_render_params *p, const uint32_t *tiles,
+                                       uint32_t n_tiles, float *d_accum, float *d_moments, uint32_t *d_seg,
+                                       void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!d_accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "d_accum NULL");
+    try {
+        return render_tiles(ctx, p, tiles, n_tiles, reinterpret_cast<float4 *>(d_accum),
+                            reinterpret_cast<float2 *>(d_moments), d_seg, static_cast<hipStream_t>(stream));
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_tiles");
+    }
+}
+
+octpt_status octpt_tile_error_device(octpt_ctx *ctx, const octpt_tile_error_params *p, const float *d_moments,
+                                     const uint32_t *d_tile_spp, float *d_error, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_tile_error(ctx, p, d_moments, d_tile_spp, d_error);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_tile_error_device(ctx->sub[0], p, d_moments, d_tile_spp, d_error, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, launch_tile_error(p->width, p->height, p->luminance_floor, reinterpret_cast<const float2 *>(d_moments),
+                                       d_tile_spp, d_error, static_cast<hipStream_t>(stream)));
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error");
+    }
+}
+
+octpt_status octpt_tile_error(octpt_ctx *ctx, const octpt_tile_error_params *p, const float *moments,
+                              const uint32_t *tile_spp, float *error) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_tile_error(ctx, p, moments, tile_spp, error);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_tile_error(ctx->sub[0], p, moments, tile_spp, error);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height, T = frame_tiles(p->width, p->height);
+        void *d[3] = {};
+        hipError_t e = hipMalloc(&d[0], n * 8);
+        if (e == hipSuccess) e = hipMemcpy(d[0], moments, n * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc(&d[1], T * 4);
+        if (e == hipSuccess) e = hipMemcpy(d[1], tile_spp, T * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc(&d[2], T * 4);
+        if (e == hipSuccess) {
+            st = octpt_tile_error_device(ctx, p, static_cast<float *>(d[0]), static_cast<uint32_t *>(d[1]),
+                                         static_cast<float *>(d[2]), ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(error, d[2], T * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "tile_error");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error");
+    }
+}
+
+octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
+                                          float *d_accum, float *d_moments, uint32_t *d_seg, uint32_t *tile_spp,
+                                          octpt_adaptive_result *result, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_tile_render(ctx, "render_adaptive", p);
+    if (st != OCTPT_OK) return st;
+    if (!a) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: adaptive params NULL");
+    if (!d_accum || !d_moments || !tile_spp)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: NULL accum, moments or tile_spp buffer");
+    if (a->min_spp < 2u || a->step_spp < 1u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: min_spp must be >= 2 and step_spp >= 1");
+    for (float x : {a->threshold, a->luminance_floor})
+        if (!(x > 0.0f) || !std::isfinite(x))
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: threshold and luminance_floor must be positive and finite");
+    if (p->spp_start != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: a fresh render (spp_start must be 0)");
+    if (p->spp_count < a->min_spp)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: spp_count (the per-pixel cap) must be >= min_spp");
+    if (p->branch_count > 1u)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "render_adaptive: branch_count > 1 (its pass boundaries fix the round sizes)");
+    try {
+        join_inflight(ctx);
+        DevRender R{};
+        if ((st = make_render(ctx, p, R)) != OCTPT_OK) return st;  // the remaining refusals, before the buffers are touched
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const uint32_t T = frame_tiles(p->width, p->height), max_spp = p->spp_count;
+        // the two tables below are rewritten every round, each time after the stream has drained; a call on another
+        // stream ended with its own drain
+        if ((st = grow_buf(ctx, ctx->d_tile_spp, ctx->tile_spp_cap, (size_t)T)) != OCTPT_OK) return st;
+        if ((st = grow_buf(ctx, ctx->d_tile_err, ctx->tile_err_cap, (size_t)T)) != OCTPT_OK) return st;
+        float4 *acc = reinterpret_cast<float4 *>(d_accum);
+        float2 *mom = reinterpret_cast<float2 *>(d_moments);
+        HIP_TRY(ctx, launch_adaptive_init(p->width * p->height, acc, mom, s));
+        std::vector<uint32_t> active(T), next;
+        std::vector<float> err(T, INFINITY);
+        for (uint32_t t = 0; t < T; ++t) active[t] = t;
+        std::fill(tile_spp, tile_spp + T, 0u);
+        uint32_t n = 0, rounds = 0;
+        while (!active.empty() && n < max_spp) {
+            const uint32_t k = std::min(n == 0u ? a->min_spp : a->step_spp, max_spp - n);
+            octpt_render_params q = *p;
+            q.spp_start = n;
+            q.spp_count = k;
+            // round 1 is every tile in frame order: the plain deal (its beam starts serve the later lists)
+            st = render_tiles(ctx, &q, n == 0u ? nullptr : active.data(), (uint32_t)active.size(), acc, mom, d_seg, s);
+            if (st != OCTPT_OK) {
+                (void)hipStreamSynchronize(s);
+                return st;
+            }
+            n += k;
+            for (uint32_t t : active) tile_spp[t] = n;
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tile_spp, tile_spp, (size_t)T * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(ctx, launch_tile_error(p->width, p->height, a->luminance_floor, mom, ctx->d_tile_spp, ctx->d_tile_err, s));
+            HIP_TRY(ctx, hipMemcpyAsync(err.data(), ctx->d_tile_err, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            next.clear();
+            for (uint32_t t : active)
+                if (err[t] > a->threshold) next.push_back(t);
+            active.swap(next);
+            ++rounds;
+        }
+        if (result) {
+            octpt_adaptive_result r{};
+            r.rounds = rounds;
+            r.total_tiles = T;
+            for (uint32_t t = 0; t < T; ++t) {
+                r.tile_samples += tile_spp[t];
+                if (err[t] <= a->threshold) ++r.converged_tiles;
+            }
+            *result = r;
+        }
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_adaptive");
+    }
+}
+
+octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
+                                   float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
+                                   octpt_adaptive_result *result) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_tile_render(ctx, "render_adaptive", p);
+    if (st != OCTPT_OK) return st;
+    if (!accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: accum NULL");
+    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
+    try {
+        join_inflight(ctx);
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        std::vector<uint32_t> spp(frame_tiles(p->width, p->height));
+        void *d[3] = {};  // accum, moments, rgba8
+        hipError_t e = hipMalloc(&d[0], n * 16);
+        if (e == hipSuccess) e = hipMalloc(&d[1], n * 8);
+        if (e == hipSuccess && out_rgba8) e = hipMalloc(&d[2], n * 4);
+        if (e == hipSuccess) {
+            st = octpt_render_adaptive_device(ctx, p, a, static_cast<float *>(d[0]), static_cast<float *>(d[1]), nullptr,
+                                              spp.data(), result, ctx->stream);
+            if (st == OCTPT_OK && out_rgba8)
+                e = launch_tonemap(static_cast<float4 *>(d[0]), static_cast<uchar4 *>(d[2]), (uint32_t)n, ctx->d_lut_byte,
+                                   ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(accum, d[0], n * 16, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && moments) e = hipMemcpy(moments, d[1], n * 8, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d[2], n * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "render_adaptive");
+        if (tile_spp) std::copy(spp.begin(), spp.end(), tile_spp);
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_adaptive");
     }
 }
 

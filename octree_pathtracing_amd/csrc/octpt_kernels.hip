@@ -2551,9 +2551,26 @@ __global__ __launch_bounds__(kBlock) void wf_drain_kernel(DevScene S, DevRender 
     flush_counters(cnt, stats, kStatDrainRow);
 }
 
-// resolve: per pixel, the chunk's samples in sample order into the running mean
-__global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
-                                                            float4 *__restrict__ accum, uint32_t *__restrict__ segcount) {
+// C27's luminance (defined with the temporal kernel below)
+__device__ __forceinline__ float luminance(float r, float g, float b);
+
+// one sample of weight bc into the running means of its luminance and the luminance's square:
+// running_mean's own formula and weights
+__device__ __forceinline__ void running_moments(float2 &m, v3 c, uint32_t spp, uint32_t bc) {
+    const float s_inv = 1.0f / (float)(bc + spp);
+    const float fs = (float)spp, w = (float)bc;
+    const float l = luminance(c.x, c.y, c.z);
+    m.x = (m.x * fs + l * w) * s_inv;
+    m.y = (m.y * fs + (l * l) * w) * s_inv;
+}
+
+// resolve: per pixel, the chunk's samples in sample order into the running mean.  kMoments: the
+// instance that also keeps the running means of the samples' luminance moments, one float2 read-modify-write
+// per pixel (`moments`: full frame, image order; the tile-list renders)
+template <bool kMoments>
+__device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp,
+                                              float4 *__restrict__ accum, uint32_t *__restrict__ segcount,
+                                              float2 *__restrict__ moments) {
     const uint32_t px_item = blockIdx.x * kBlock + threadIdx.x;
     if (px_item >= R.total_items) return;
     uint32_t x, y;
@@ -2561,6 +2578,8 @@ __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuf
     if (x >= R.W || y >= R.H) return;
     const uint32_t acc_idx = R.compact ? px_item : y * R.W + x;
     float4 fb = accum[acc_idx];
+    float2 mo = make_float2(0.0f, 0.0f);
+    if constexpr (kMoments) mo = moments[acc_idx];
     uint32_t segs = 0u;
     v3 L0 = V(0.0f, 0.0f, 0.0f), sum = L0;
     bool split = false;
@@ -2570,6 +2589,7 @@ __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuf
         segs += w & 0x7FFFFFFFu;
         if (!R.subs) {
             running_mean(fb, V(c.x, c.y, c.z), R.spp_start + s, 1u);
+            if constexpr (kMoments) running_moments(mo, V(c.x, c.y, c.z), R.spp_start + s, 1u);
             continue;
         }
         // branch schedule (C20): a pass's branches fold into one sample of weight bc; the colour
@@ -2585,11 +2605,26 @@ __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuf
         }
         if (b + 1u == bc) {
             const float inv = 1.0f / (float)bc;
-            running_mean(fb, split ? vscale(sum, inv) : L0, sb.x, bc);
+            const v3 folded = split ? vscale(sum, inv) : L0;
+            running_mean(fb, folded, sb.x, bc);
+            if constexpr (kMoments) running_moments(mo, folded, sb.x, bc);
         }
     }
     accum[acc_idx] = fb;
+    if constexpr (kMoments) moments[acc_idx] = mo;
     if (segcount) segcount[acc_idx] += segs;
+}
+
+__global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
+                                                            float4 *__restrict__ accum, uint32_t *__restrict__ segcount) {
+    resolve_pixel<false>(R, B, chunk_spp, accum, segcount, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void wf_resolve_moments_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
+                                                                    float4 *__restrict__ accum,
+                                                                    uint32_t *__restrict__ segcount,
+                                                                    float2 *__restrict__ moments) {
+    resolve_pixel<true>(R, B, chunk_spp, accum, segcount, moments);
 }
 
 // one ray per thread closest-hit query (Scene::hit) for octpt_intersect
@@ -3195,6 +3230,54 @@ __global__ __launch_bounds__(256) void variance_kernel(DevVariance V) {
 }
 
 // ===========================================================================
+// The per-tile error of an adaptive render: the standard error of the tile's mean luminance relative
+// to that luminance, from the sample moments resolve keeps (C31).  One wave64 per 8 x 8 tile, lane = pixel, the
+// renderer's own mapping; the two sums are xor butterflies over the wave, so every lane ends with the same bits and
+// lane 0 writes.  Lanes over the image edge contribute 0 and the tile divides by its own pixel count.
+// ===========================================================================
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+    return v;
+}
+
+__global__ __launch_bounds__(kBlock) void tile_error_kernel(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles,
+                                                            float luminance_floor, const float2 *__restrict__ moments,
+                                                            const uint32_t *__restrict__ tile_spp,
+                                                            float *__restrict__ error) {
+    const uint32_t t = blockIdx.x * (kBlock / 64u) + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (t >= n_tiles) return;  // whole waves leave
+    const uint32_t ty = t / tiles_x, x0 = (t - ty * tiles_x) * kTile, y0 = ty * kTile;
+    const uint32_t x = x0 + (lane & 7u), y = y0 + (lane >> 3);
+    float v = 0.0f, m1 = 0.0f;
+    if (x < W && y < H) {
+        const float2 m = moments[(size_t)y * W + x];
+        const float d = m.y - m.x * m.x;
+        v = d < 0.0f ? 0.0f : d;  // a NaN stays one
+        m1 = m.x;
+    }
+    const float Sv = wave_sum_f32(v), Sl = wave_sum_f32(m1);
+    if (lane != 0u) return;
+    const float kInf = __builtin_inff();
+    const uint32_t n = tile_spp[t];
+    float e = kInf;
+    if (n >= 2u) {
+        const float P = (float)(min(kTile, W - x0) * min(kTile, H - y0));
+        e = sqrtf((Sv / P) / (float)(n - 1u)) / (Sl / P + luminance_floor);
+        if (!(fabsf(e) < kInf)) e = kInf;
+    }
+    error[t] = e;
+}
+
+// the start of an adaptive render (C32): accum = F32Color::BLACK (0, 0, 0, 1), moments = (0, 0)
+__global__ __launch_bounds__(256) void adaptive_init_kernel(uint32_t n, float4 *__restrict__ accum,
+                                                            float2 *__restrict__ moments) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    accum[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    moments[i] = make_float2(0.0f, 0.0f);
+}
+
+// ===========================================================================
 // The variance-guided a-trous filter (SVGF, Schied et al. 2017).  The working frames hold
 // (s.rgb, v) per pixel, so a tap's signal and variance come in one 16-byte load; the input's alpha is read by the
 // last pass alone, each thread its own pixel before it writes it (out may be the input frame: no __restrict__ on
@@ -3516,9 +3599,27 @@ hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_o
 }
 
 hipError_t launch_wf_resolve(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp, float4 *accum,
-                             uint32_t *segcount, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_resolve_kernel, dim3((R.total_items + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, R, B,
-                       chunk_spp, accum, segcount);
+                             uint32_t *segcount, float2 *moments, hipStream_t stream) {
+    const dim3 grid((R.total_items + kBlock - 1u) / kBlock);
+    if (moments)
+        hipLaunchKernelGGL(wf_resolve_moments_kernel, grid, dim3(kBlock), 0, stream, R, B, chunk_spp, accum, segcount,
+                           moments);
+    else
+        hipLaunchKernelGGL(wf_resolve_kernel, grid, dim3(kBlock), 0, stream, R, B, chunk_spp, accum, segcount);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_init(uint32_t n, float4 *accum, float2 *moments, hipStream_t stream) {
+    hipLaunchKernelGGL(adaptive_init_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, n, accum, moments);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_error(uint32_t W, uint32_t H, float luminance_floor, const float2 *moments,
+                             const uint32_t *tile_spp, float *error, hipStream_t stream) {
+    const uint32_t tiles_x = (W + kTile - 1u) / kTile, n_tiles = tiles_x * ((H + kTile - 1u) / kTile);
+    const uint32_t per_block = kBlock / 64u;
+    hipLaunchKernelGGL(tile_error_kernel, dim3((n_tiles + per_block - 1u) / per_block), dim3(kBlock), 0, stream, W, H,
+                       tiles_x, n_tiles, luminance_floor, moments, tile_spp, error);
     return hipGetLastError();
 }
 

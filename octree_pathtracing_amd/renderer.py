@@ -103,6 +103,7 @@ class HipRenderer:
         if st != _lib.OK:
             raise _lib.OctptError(st, f"{what} failed: no usable gfx950 device")
         self._ctx = ctx
+        self._device = int(device) if devices is None else int(devices[0])  # where the caller's buffers live
         self.device_entries = int(self._lib.octpt_device_entries(ctx))
         self._camera = Camera()
         self._resolution = tuple(resolution)
@@ -551,6 +552,107 @@ class HipRenderer:
             self._ctx, C.byref(params), C.c_void_p(d_color), C.c_void_p(d_variance), C.byref(b), C.c_void_p(d_out),
             C.c_void_p(d_out_variance) if d_out_variance else None, C.c_void_p(stream) if stream else None))
 
+    # ------------------------------------------------------------ adaptive sampling (C30-C32)
+    def render_tiles_device(self, params: "_lib.RenderParams", tiles, d_accum: int, d_moments: int | None = None,
+                            d_seg_count: int | None = None, stream: int | None = None) -> None:
+        """Enqueue octpt_render_tiles_device on raw device pointers: params.spp_count more samples into the listed
+        frame tiles only (tiles: distinct indices t = ty * ceil(W / 8) + tx in any order, a host sequence; None =
+        every tile).  d_moments: the samples' luminance moments, 2 floats / pixel (C31)."""
+        t = None if tiles is None else np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+        # an empty list is still a list (nothing is rendered): a pointer that is not NULL, never read
+        ptr = None if t is None else (t.ctypes.data_as(C.c_void_p) if len(t) else C.cast(C.pointer(C.c_uint32(0)), C.c_void_p))
+        self._check(self._lib.octpt_render_tiles_device(
+            self._ctx, C.byref(params), ptr, 0 if t is None else len(t), C.c_void_p(d_accum),
+            C.c_void_p(d_moments) if d_moments else None, C.c_void_p(d_seg_count) if d_seg_count else None,
+            C.c_void_p(stream) if stream else None))
+
+    def render_tiles(self, settings: RenderSettings, tiles=None, accum: np.ndarray | None = None,
+                     moments: np.ndarray | None = None, seg_count: np.ndarray | None = None, spp_start: int = 0):
+        """settings.spp more samples into the listed tiles of host frames (render_tiles_device through torch
+        buffers on this renderer's GPU): accum [H, W, 4] (black when None), moments [H, W, 2] and seg_count [H, W]
+        u32 (zeros when None), each holding spp_start samples.  Returns (accum, moments, seg_count); pixels of
+        unlisted tiles come back as they went in."""
+        import torch
+
+        W, H = settings.width, settings.height
+        if accum is None:
+            accum = np.zeros((H, W, 4), np.float32)
+            accum[..., 3] = 1.0
+        host = [np.ascontiguousarray(accum, np.float32).reshape(H, W, 4),
+                np.ascontiguousarray(np.zeros((H, W, 2)) if moments is None else moments, np.float32).reshape(H, W, 2),
+                np.ascontiguousarray(np.zeros((H, W)) if seg_count is None else seg_count, np.uint32).reshape(H, W)]
+        dev = torch.device("cuda", self._device)
+        d_acc, d_mom = (torch.from_numpy(a).to(dev) for a in host[:2])
+        d_seg = torch.from_numpy(host[2].view(np.int32)).to(dev)
+        self.max_depth = settings.max_depth
+        self.seed = settings.seed
+        p = self.params(W, H, spp_start, settings.spp)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            self.render_tiles_device(p, tiles, d_acc.data_ptr(), d_mom.data_ptr(), d_seg.data_ptr(), stream)
+            torch.cuda.synchronize()
+        return d_acc.cpu().numpy(), d_mom.cpu().numpy(), d_seg.cpu().numpy().view(np.uint32)
+
+    def tile_error(self, moments: np.ndarray, tile_spp: np.ndarray, luminance_floor: float = LUMINANCE_FLOOR) -> np.ndarray:
+        """The per-tile error (octpt_tile_error) of a [H, W, 2] moments frame whose tile t holds tile_spp[t]
+        samples per pixel: the standard error of the tile's mean luminance relative to it, one float per 8x8 tile
+        in frame tile order, +inf below 2 samples."""
+        m = np.ascontiguousarray(moments, np.float32)
+        H, W = m.shape[:2]
+        T = tile_count(W, H)
+        n = np.ascontiguousarray(tile_spp, np.uint32).reshape(-1)
+        if m.shape != (H, W, 2) or n.size != T:
+            raise ValueError(f"moments must be [H, W, 2] and tile_spp hold one entry per tile ({T})")
+        p = _lib.TileErrorParams(W, H, luminance_floor)
+        err = np.empty(T, np.float32)
+        self._check(self._lib.octpt_tile_error(self._ctx, C.byref(p), m.ctypes.data_as(C.c_void_p),
+                                               n.ctypes.data_as(C.c_void_p), err.ctypes.data_as(C.c_void_p)))
+        return err
+
+    def tile_error_device(self, params: "_lib.TileErrorParams", d_moments: int, d_tile_spp: int, d_error: int,
+                          stream: int | None = None) -> None:
+        """Enqueue octpt_tile_error_device on raw device pointers."""
+        self._check(self._lib.octpt_tile_error_device(self._ctx, C.byref(params), C.c_void_p(d_moments),
+                                                      C.c_void_p(d_tile_spp), C.c_void_p(d_error),
+                                                      C.c_void_p(stream) if stream else None))
+
+    def render_adaptive(self, settings: RenderSettings, min_spp: int, step_spp: int, threshold: float,
+                        luminance_floor: float = LUMINANCE_FLOOR, with_rgba: bool = False):
+        """Render until every 8x8 tile's error (tile_error) is at most `threshold`, or settings.spp samples per
+        pixel are reached (octpt_render_adaptive): min_spp samples everywhere, then rounds of step_spp into the
+        tiles still above the threshold.  Returns (accum [H, W, 4], moments [H, W, 2], tile_spp u32 per tile,
+        result dict: rounds, tile_samples, converged_tiles, total_tiles -- and "rgba" with with_rgba)."""
+        W, H = settings.width, settings.height
+        accum = np.empty((H, W, 4), np.float32)
+        moments = np.empty((H, W, 2), np.float32)
+        tile_spp = np.zeros(tile_count(W, H), np.uint32)
+        rgba = np.zeros((H, W, 4), np.uint8) if with_rgba else None
+        self.max_depth = settings.max_depth
+        self.seed = settings.seed
+        p = self.params(W, H, 0, settings.spp)
+        a = _lib.AdaptiveParams(min_spp, step_spp, threshold, luminance_floor)
+        res = _lib.AdaptiveResult()
+        self._check(self._lib.octpt_render_adaptive(
+            self._ctx, C.byref(p), C.byref(a), accum.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p),
+            tile_spp.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba is not None else None,
+            C.byref(res)))
+        result = res.as_dict()
+        if rgba is not None:
+            result["rgba"] = rgba
+        return accum, moments, tile_spp, result
+
+    def render_adaptive_device(self, params: "_lib.RenderParams", adaptive: "_lib.AdaptiveParams", d_accum: int,
+                               d_moments: int, d_seg_count: int | None = None, stream: int | None = None):
+        """octpt_render_adaptive_device on raw device pointers (params.spp_count is the per-pixel cap); returns
+        (tile_spp, result dict).  The call drains `stream` once per round."""
+        tile_spp = np.zeros(tile_count(params.width, params.height), np.uint32)
+        res = _lib.AdaptiveResult()
+        self._check(self._lib.octpt_render_adaptive_device(
+            self._ctx, C.byref(params), C.byref(adaptive), C.c_void_p(d_accum), C.c_void_p(d_moments),
+            C.c_void_p(d_seg_count) if d_seg_count else None, tile_spp.ctypes.data_as(C.c_void_p), C.byref(res),
+            C.c_void_p(stream) if stream else None))
+        return tile_spp, res.as_dict()
+
     def stats(self) -> dict:
         s = _lib.Stats()
         self._check(self._lib.octpt_get_stats(self._ctx, C.byref(s)))
@@ -609,6 +711,11 @@ def reproject_coords(camera: Camera, prev_camera: Camera, W: int, H: int, depth:
     if st != 0:
         raise _lib.OctptError(st, "octpt_reproject_coords")
     return xy, zp
+
+
+def tile_count(W: int, H: int) -> int:
+    """8x8 tiles of a W x H frame (the entries of tile_spp and tile_error, C30-C32)."""
+    return ((W + _lib.TILE - 1) // _lib.TILE) * ((H + _lib.TILE - 1) // _lib.TILE)
 
 
 def shard_pixels(W: int, H: int, shard_index: int, shard_count: int) -> int:
