@@ -2699,6 +2699,7 @@ constexpr uint32_t kBeamVisits = OCTPT_BEAM_VISITS;  // cells visited per tile; 
 #define OCTPT_BEAM_LOD 0.0f
 #endif
 constexpr float kBeamLod = OCTPT_BEAM_LOD;
+constexpr float kBeamEsvoSlack = 0x1p-21f;  // x (4 + |eye|) octree units: ESVO's positional rounding (beam_kernel's box test)
 
 // A tile's start t with, in its low kBeamIterBits bits, a bound of the reference iterations a ray of the
 // tile runs before it (t is rounded down first, so the packed value never exceeds it).  The reference
@@ -2756,6 +2757,7 @@ __global__ __launch_bounds__(64) void beam_kernel(DevScene S, DevCamera C, DevRe
     }
     // the eye as esvo_begin places a ray origin in octree space
     const v3 e = vadd(vscale(V(C.eye[0], C.eye[1], C.eye[2]), S.octree_scale), V(1.0f, 1.0f, 1.0f));
+    const float slack = kBeamEsvoSlack * (4.0f + fmaxf(fmaxf(fabsf(e.x), fabsf(e.y)), fabsf(e.z)));
     // distance from the eye to the box [lo, lo + h], or -1 when the box lies outside the pyramid
     auto box = [&](v3 lo, float h) -> float {
         const v3 a = vsub(lo, e), b = vsub(vadd(lo, V(h, h, h)), e);
@@ -2764,7 +2766,13 @@ __global__ __launch_bounds__(64) void beam_kernel(DevScene S, DevCamera C, DevRe
         for (int k = 0; k < 4; ++k) {
             const v3 n = pn[k];
             const float mx = (fmaxf(n.x * a.x, n.x * b.x) + fmaxf(n.y * a.y, n.y * b.y)) + fmaxf(n.z * a.z, n.z * b.z);
-            const float tol = 1e-5f * ((fabsf(n.x) + fabsf(n.y)) + fabsf(n.z)) * ext;
+            // slack: the rays ESVO walks are not the pyramid's exact lines.  Its t-values carry the roundings of
+            // t_bias = t_coef * ro, of the mirror 3 * t_coef - t_bias and of pos * t_coef - t_bias (pos < 2): in
+            // all at most (13 + 3 |ro|) 2^-24 |t_coef|, which moves a ray by that many octree units across its
+            // direction -- a whole cell at depth 21, where the walk enters (and may hit in) cells that lie just
+            // outside the exact pyramid.  Boxes within kBeamEsvoSlack (4 + |e|) = (32 + 8 |e|) 2^-24, twice that bound for any
+            // eye (esvo_begin's margin grows with the origin the same way), are kept.
+            const float tol = (1e-5f * ext + slack) * ((fabsf(n.x) + fabsf(n.y)) + fabsf(n.z));
             if (mx < -tol) return -1.0f;
         }
         const float dx = a.x > 0.0f ? a.x : (b.x < 0.0f ? -b.x : 0.0f);

@@ -51,6 +51,41 @@ PREVIEWS = {
 }
 
 
+# fixtures at octree depths 12 and 21 (tests/deep_worlds.py): name -> (generator case, preview); their
+# scenes are no make_config names, so the metadata carries "generator" instead of "config"
+DEEP = {
+    "deep_blocks21_small": ("blocks21", False),
+    "deep_blocks12_small": ("blocks12c", False),  # the compacted tree: LOD leaves
+    "deep_prims21_small": ("prims21", False),
+    "deep_blocks21_preview": ("blocks21", True),
+}
+DEEP_RAYS = {"deep_blocks21_rays": "blocks21"}
+
+
+def deep_fixture(name):
+    from tests import deep_worlds as DW
+
+    gen, preview = DEEP[name]
+    sc, cam, _ = DW.case(gen)
+    rs = DW.settings()
+    spp = 1 if preview else rs.spp
+    acc, seg, st = cpu_ref.render(sc, cam, rs.width, rs.height, spp, max_depth=rs.max_depth, seed=rs.seed,
+                                  forward=True, threads=8, preview=preview)
+    return dict(accum=acc, segcount=seg, stats=np.array([st[k] for k in STAT_KEYS], np.uint64),
+                meta=np.array(json.dumps(dict(generator=gen, width=rs.width, height=rs.height, spp=spp,
+                                              max_depth=rs.max_depth, seed=rs.seed, forward=True,
+                                              **(dict(preview=True) if preview else {})))))
+
+
+def deep_ray_fixture(name):
+    """4096 closest-hit queries around the depth-21 terrain (deep_worlds.random_rays)."""
+    from tests import deep_worlds as DW
+
+    gen = DEEP_RAYS[name]
+    rays, (t, prim, nrm, steps) = DW.ray_batch(gen)
+    return dict(rays=rays, t=t, prim=prim, normal=nrm, steps=steps, meta=np.array(json.dumps(dict(generator=gen))))
+
+
 def render_fixture(name):
     cfg, W, H, spp, md, *extra = RENDERS[name]
     opts = extra[0] if extra and isinstance(extra[0], dict) else {"variant": extra[0]} if extra else {}
@@ -94,7 +129,8 @@ def ray_fixture():
 
 
 def main(names):
-    makers = {**{n: render_fixture for n in RENDERS}, **{n: preview_fixture for n in PREVIEWS}}
+    makers = {**{n: render_fixture for n in RENDERS}, **{n: preview_fixture for n in PREVIEWS},
+              **{n: deep_fixture for n in DEEP}, **{n: deep_ray_fixture for n in DEEP_RAYS}}
     for name in names or [*makers, "c3_rays"]:
         if name == "c3_rays":
             np.savez_compressed(HERE / "c3_rays.npz", **ray_fixture())

@@ -455,12 +455,12 @@ def test_render_matches_golden_fixture(torch_cuda, renderer, name):
 
     from octree_pathtracing_amd import scene as S
 
+    from tests.test_golden_cpu import fixture_scene
+
     g = np.load(GOLDEN / f"{name}.npz", allow_pickle=False)
     m = json.loads(str(g["meta"]))
-    sc, cam, rs = S.make_config(m["config"])
-    if "sun_variant" in m:
-        S.with_sun_variant(sc, m["sun_variant"])
-    rs.width, rs.height, rs.spp, rs.max_depth, rs.seed = m["width"], m["height"], m["spp"], m["max_depth"], m["seed"]
+    sc, cam = fixture_scene(m)  # a make_config name, or a tests/deep_worlds.py case under "generator"
+    rs = S.RenderSettings(m["width"], m["height"], m["spp"], max_depth=m["max_depth"], seed=m["seed"])
     bc = m.get("branch_count", 1)
     acc, segs, st = gpu_render(torch_cuda, renderer, sc, cam, rs, preview=m.get("preview", False), branch_count=bc)
     keys = ("paths", "segments", "esvo_steps", "node_fetches", "prim_tests", "leaf_visits", "shade_events",
@@ -479,13 +479,15 @@ def test_render_matches_golden_fixture(torch_cuda, renderer, name):
     assert (acc == g["accum"]).mean() > 0.999
 
 
-def test_intersect_matches_golden_rays(renderer):
-    """octpt_intersect on the committed C3 ray fixture: prim ids, t, normals and ESVO step counts
-    all bit-exact."""
-    from octree_pathtracing_amd import scene as S
+def test_intersect_matches_golden_rays(renderer, name="c3_rays"):
+    """octpt_intersect on a committed ray fixture (the C3 one; tests/test_gpu_deep.py passes the depth-21 one): prim
+    ids, t, normals and ESVO step counts all bit-exact."""
+    import json
 
-    g = np.load(GOLDEN / "c3_rays.npz", allow_pickle=False)
-    sc, _, _ = S.make_config("C3")
+    from tests.test_golden_cpu import fixture_scene
+
+    g = np.load(GOLDEN / f"{name}.npz", allow_pickle=False)
+    sc = fixture_scene(json.loads(str(g["meta"])) if "meta" in g else {"config": "C3"})[0]
     renderer.set_scene(sc)
     t, prim, nrm, steps = renderer.intersect(g["rays"])
     assert np.array_equal(prim, g["prim"]) and np.array_equal(steps, g["steps"])
