@@ -635,6 +635,103 @@ octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p,
                                    float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
                                    octpt_adaptive_result *result);
 
+/* --- final-quality adaptive frames: sample clamp, seam rule, sample variance, one-pass filter ---
+ * What turns the tile loop above into a finished picture: a per-sample luminance clamp, so that one firefly does not
+ * hold its tile above the threshold up to the cap (C33); the error of a tile raised to a share of its neighbours', so
+ * that adjacent tiles stop at noise levels within a known factor of each other (C34); the variance of each pixel's
+ * mean from C31's sample moments (C35), which is what C29's filter needs and a final frame, with no history, cannot
+ * get from C27/C28; and one entry that runs render -> guides -> variance -> filter (C36). */
+
+/* C33.  A clamp on every sample's luminance, applied by resolve before the running means: c = the sample's colour
+ * (the pass's folded colour under a branch schedule), l = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b; if l > max_luminance:
+ * k = max_luminance / l, c = (c.r * k, c.g * k, c.b * k).  A NaN l compares false: the sample passes unchanged.  C31's
+ * moments are those of the clamped colour (l recomputed from it); segment counts are untouched.
+ * max_luminance 0 or +inf: off, the state of a new context -- every render is then bit for bit what it was, through
+ * the same kernels.  Any other positive finite value: on.  NaN or a negative value: INVALID_ARG, the setting stays.
+ * It holds for every later wavefront render of the context (octpt_render, _device, _async, octpt_render_tiles_device,
+ * the adaptive drivers and octpt_render_final), read when the render call is made; the call joins a frame in flight
+ * first.  OCTPT_RENDER_PREVIEW ignores it (it takes no samples); OCTPT_RENDER_MEGAKERNEL with a clamp on is
+ * UNSUPPORTED (it accumulates inside the kernel).  On a multi-device context the value is set on every entry. */
+octpt_status octpt_set_sample_clamp(octpt_ctx *ctx, float max_luminance);
+
+/* C34.  The seam rule: out[t] = max(error[t], w * M), w = neighbour_weight in [0, 1] (anything else, NaN included:
+ * INVALID_ARG), M = the maximum of error[u] over the up to eight tiles u adjacent to t in the tile grid (tiles outside
+ * the grid do not count).  w == 0: out[t] = error[t] exactly, no multiply is made (+inf * 0 never appears).  error and
+ * out hold one float per tile in frame tile order, as C32's planes; the inputs are C32's errors, never NaN.  A tile
+ * whose spread error is <= threshold has its own error <= threshold and every neighbour's <= threshold / w: adjacent
+ * tiles stop at noise levels within a factor 1 / w of each other.  The spread never lowers an error.
+ * d_out == d_error: INVALID_ARG.  One launch on `hip_stream`, one thread per tile, no host synchronisation, no memory
+ * of the context's; on a multi-device context it runs on devices[0]. */
+octpt_status octpt_tile_error_spread_device(octpt_ctx *ctx, uint32_t width, uint32_t height, float neighbour_weight,
+                                            const float *d_error, float *d_out, void *hip_stream);
+/* The same over host arrays. */
+octpt_status octpt_tile_error_spread(octpt_ctx *ctx, uint32_t width, uint32_t height, float neighbour_weight,
+                                     const float *error, float *out);
+
+/* The adaptive driver with the seam rule: the loop of octpt_render_adaptive_device with one change -- after step 5
+ * the round's error plane (every tile's: inactive tiles keep their moments and tile_spp, hence their last error) goes
+ * through C34, and steps 6 and 7 and converged_tiles use the spread plane, which is the one the host reads back.
+ * neighbour_weight == 0 is octpt_render_adaptive_device, bit for bit; the plain entries are these with weight 0.
+ * A non-zero reserved word or a neighbour_weight outside [0, 1]: INVALID_ARG; the plain entries' refusals apply. */
+typedef struct octpt_adaptive_params_ex {
+    uint32_t min_spp, step_spp;
+    float threshold, luminance_floor; /* octpt_adaptive_params' four */
+    float neighbour_weight;           /* [0, 1]; 0 = C32's loop */
+    uint32_t reserved[3];             /* 0 */
+} octpt_adaptive_params_ex;
+octpt_status octpt_render_adaptive_ex_device(octpt_ctx *ctx, const octpt_render_params *p,
+                                             const octpt_adaptive_params_ex *a, float *d_accum, float *d_moments,
+                                             uint32_t *d_seg_count, uint32_t *tile_spp, octpt_adaptive_result *result,
+                                             void *hip_stream);
+/* The same into host arrays; moments, tile_spp, out_rgba8 and result are nullable. */
+octpt_status octpt_render_adaptive_ex(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a,
+                                      float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
+                                      octpt_adaptive_result *result);
+
+/* C35.  The variance of each pixel's mean luminance from C31's sample moments, one float per pixel, never negative:
+ * what C29 filters under.  Pixel p in tile t with n = tile_spp[t]: depth not finite (a miss) or n < 2: 0.  Else
+ * d = m2 - m1 * m1, v = d > 0 ? d : 0 (a NaN becomes 0), v = v / (float)(n - 1).  With OCTPT_DENOISE_DEMODULATE:
+ * a = max(albedo.rgb, 1e-3) componentwise, la = luminance(a), v = v / (la * la) -- the variance moved into the
+ * demodulated signal C29 works on; exact for a grey albedo (luminance(c / a) = luminance(c) / la there), an
+ * approximation otherwise. */
+typedef struct octpt_sample_variance_params {
+    uint32_t width, height;
+    uint32_t flags; /* OCTPT_DENOISE_DEMODULATE */
+} octpt_sample_variance_params;
+/* Device buffers: d_moments width * height * 2 floats, d_tile_spp one entry per tile, d_guides->depth required and
+ * ->albedo with the flag, d_out one float per pixel, distinct from the inputs (INVALID_ARG).  One launch on
+ * `hip_stream`, one thread per pixel, no host synchronisation, no memory of the context's; on a multi-device context
+ * it runs on devices[0]. */
+octpt_status octpt_sample_variance_device(octpt_ctx *ctx, const octpt_sample_variance_params *p, const float *d_moments,
+                                          const uint32_t *d_tile_spp, const octpt_aov_buffers *d_guides, float *d_out,
+                                          void *hip_stream);
+/* The same over host arrays. */
+octpt_status octpt_sample_variance(octpt_ctx *ctx, const octpt_sample_variance_params *p, const float *moments,
+                                   const uint32_t *tile_spp, const octpt_aov_buffers *guides, float *out);
+
+/* C36.  The finished frame.  The result is, bit for bit, this composition of public entries on `hip_stream`:
+ *   1. octpt_render_adaptive_ex_device(p, &f->adaptive) -> d_accum, d_moments, tile_spp, result;
+ *   2. octpt_render_aov_device for normal and depth, and albedo with OCTPT_DENOISE_DEMODULATE in f->filter.flags, into
+ *      guide planes the context owns (grow-only, like its one variance plane);
+ *   3. octpt_sample_variance_device with that demodulate bit and the driver's final tile_spp;
+ *   4. octpt_denoise_variance_device(&f->filter, d_accum, variance, guides) -> d_out, d_out_variance (nullable).
+ * d_accum and d_moments keep the unfiltered result.  d_out must not alias d_accum (INVALID_ARG).  The driver's and the
+ * filter's refusals apply, and filter.width / height must equal the render's (INVALID_ARG); all are checked before any
+ * buffer is touched.  The clamp set on the context (C33) applies.  The context's planes are shared by its
+ * octpt_render_final calls: calls on different streams must be ordered by the caller. */
+typedef struct octpt_final_params {
+    octpt_adaptive_params_ex adaptive;
+    octpt_denoise_variance_params filter; /* width / height must equal the render's */
+} octpt_final_params;
+octpt_status octpt_render_final_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_final_params *f,
+                                       float *d_accum, float *d_moments, float *d_out, float *d_out_variance,
+                                       uint32_t *tile_spp, octpt_adaptive_result *result, void *hip_stream);
+/* The same into host arrays: out is required; accum, moments, out_variance, tile_spp, out_rgba8 (the tone map of out)
+ * and result are nullable. */
+octpt_status octpt_render_final(octpt_ctx *ctx, const octpt_render_params *p, const octpt_final_params *f, float *accum,
+                                float *moments, float *out, float *out_variance, uint32_t *tile_spp,
+                                uint8_t *out_rgba8, octpt_adaptive_result *result);
+
 /* --- host octree builder (replaces the Rust-side build for primitive scenes) ---
  * Voxelises spheres/cuboids into depth-`depth` leaf cells, Morton-sorts
  * them (new_octree.rs:752-835 code order) and emits octants in pre-order. */

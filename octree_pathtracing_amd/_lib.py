@@ -252,6 +252,22 @@ class AdaptiveResult(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class AdaptiveParamsEx(C.Structure):
+    """octpt_adaptive_params_ex: octpt_adaptive_params and the seam rule's neighbour weight."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float),
+                ("luminance_floor", C.c_float), ("neighbour_weight", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class SampleVarianceParams(C.Structure):
+    """octpt_sample_variance_params."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FinalParams(C.Structure):
+    """octpt_final_params: the adaptive driver's and the variance-guided filter's."""
+    _fields_ = [("adaptive", AdaptiveParamsEx), ("filter", DenoiseVarianceParams)]
+
+
 TILE = 8  # the wavefront's 8x8 pixel tiles: frame tile t = ty * ceil(W / TILE) + tx (C30)
 
 
@@ -337,6 +353,20 @@ SIGNATURES = {
                                             C.POINTER(AdaptiveResult), _vp]),
     "octpt_render_adaptive": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), _vp, _vp, _vp, _vp,
                                      C.POINTER(AdaptiveResult)]),
+    "octpt_set_sample_clamp": (_i32, [_vp, _f]),
+    "octpt_tile_error_spread_device": (_i32, [_vp, _u32, _u32, _f, _vp, _vp, _vp]),
+    "octpt_tile_error_spread": (_i32, [_vp, _u32, _u32, _f, _vp, _vp]),
+    "octpt_render_adaptive_ex_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParamsEx), _vp, _vp, _vp,
+                                               _vp, C.POINTER(AdaptiveResult), _vp]),
+    "octpt_render_adaptive_ex": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParamsEx), _vp, _vp, _vp, _vp,
+                                        C.POINTER(AdaptiveResult)]),
+    "octpt_sample_variance_device": (_i32, [_vp, C.POINTER(SampleVarianceParams), _vp, _vp, C.POINTER(AovBuffers), _vp,
+                                            _vp]),
+    "octpt_sample_variance": (_i32, [_vp, C.POINTER(SampleVarianceParams), _vp, _vp, C.POINTER(AovBuffers), _vp]),
+    "octpt_render_final_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(FinalParams), _vp, _vp, _vp, _vp, _vp,
+                                         C.POINTER(AdaptiveResult), _vp]),
+    "octpt_render_final": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(FinalParams), _vp, _vp, _vp, _vp, _vp, _vp,
+                                  C.POINTER(AdaptiveResult)]),
     "octpt_reproject_coords": (_i32, [C.POINTER(Camera), C.POINTER(Camera), _u32, _u32, _vp, _vp, _vp]),
     "octpt_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "octpt_reset_stats": (_i32, [_vp]),

@@ -168,6 +168,15 @@ struct octpt_ctx {
     uint32_t *d_tile_spp = nullptr;
     float *d_tile_err = nullptr;
     size_t tile_spp_cap = 0, tile_err_cap = 0;
+    // the sample clamp of resolve (C33, octpt_set_sample_clamp): 0 = off
+    float sample_clamp = 0.0f;
+    // the seam rule's spread error plane (C34, the _ex driver) and the finished frame's guide and variance planes
+    // (C36, octpt_render_final_device), grow-only
+    float *d_tile_spread = nullptr;
+    size_t tile_spread_cap = 0;
+    float4 *fin_normal = nullptr, *fin_albedo = nullptr;
+    float *fin_depth = nullptr, *fin_var = nullptr;
+    size_t fin_normal_cap = 0, fin_albedo_cap = 0, fin_depth_cap = 0, fin_var_cap = 0;
     // recorded on the stream that computed the table: a render on another stream that reuses it waits for it
     hipEvent_t beam_ev = nullptr;
     hipStream_t beam_stream = nullptr;  // the stream the valid table was computed on
@@ -672,6 +681,9 @@ octpt_status make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender
     if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
     if (p->max_depth == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "max_depth must be >= 1");
+    if (ctx->sample_clamp != 0.0f && (p->flags & OCTPT_RENDER_MEGAKERNEL) && !(p->flags & OCTPT_RENDER_PREVIEW))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED,
+                    "a sample clamp is set (octpt_set_sample_clamp): the megakernel accumulates inside the kernel");
     const uint32_t B = p->branch_count ? p->branch_count : 1u;
     if (B > 64u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "branch_count must be <= 64");
     if (p->shard_count == 0 || p->shard_index >= p->shard_count) return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad shard");
@@ -938,6 +950,8 @@ octpt_status enqueue_megakernel(octpt_ctx *ctx, const DevRender &R, float4 *d_ac
 octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_accum, uint32_t *d_seg, hipStream_t s,
                                const std::atomic<bool> *cancel, float2 *d_moments = nullptr, uint64_t list = 0) {
     const uint64_t n_px = R.total_items;
+    // the sample clamp (C33) as set when the render call was made: octpt_set_sample_clamp joins a frame in flight
+    const float clamp = ctx->sample_clamp;
     uint32_t chunk_spp = 1;
     uint64_t chunk_max = 0;
     octpt_status st = OCTPT_OK;
@@ -1124,7 +1138,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                 }
             }
         }
-        HIP_TRY(ctx, launch_wf_resolve(Rc, B, Rc.spp_count, d_accum, d_seg, d_moments, s));
+        HIP_TRY(ctx, launch_wf_resolve(Rc, B, Rc.spp_count, d_accum, d_seg, d_moments, clamp, s));
     }
     return OCTPT_OK;
 }
@@ -1635,6 +1649,9 @@ void octpt_destroy(octpt_ctx *ctx) {
     if (ctx->d_tiles) (void)hipFree(ctx->d_tiles);
     if (ctx->d_tile_spp) (void)hipFree(ctx->d_tile_spp);
     if (ctx->d_tile_err) (void)hipFree(ctx->d_tile_err);
+    for (void *q : {(void *)ctx->d_tile_spread, (void *)ctx->fin_normal, (void *)ctx->fin_albedo, (void *)ctx->fin_depth,
+                    (void *)ctx->fin_var})
+        if (q) (void)hipFree(q);
     if (ctx->m_acc) (void)hipFree(ctx->m_acc);
     if (ctx->m_seg) (void)hipFree(ctx->m_seg);
     for (float4 *f : ctx->dn_frame)
@@ -2912,25 +2929,48 @@ octpt_status octpt_tile_error(octpt_ctx *ctx, const octpt_tile_error_params *p, 
     }
 }
 
-octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
-                                          float *d_accum, float *d_moments, uint32_t *d_seg, uint32_t *tile_spp,
-                                          octpt_adaptive_result *result, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+namespace {
+
+// the plain driver's parameters as the _ex form's: neighbour weight 0, C32's loop
+octpt_adaptive_params_ex adaptive_ex_of(const octpt_adaptive_params &a) {
+    octpt_adaptive_params_ex x{};
+    x.min_spp = a.min_spp;
+    x.step_spp = a.step_spp;
+    x.threshold = a.threshold;
+    x.luminance_floor = a.luminance_floor;
+    return x;
+}
+
+// what the adaptive drivers refuse of their parameters (C32, C34b) besides make_render's own refusals; buffers: whether
+// the accum, moments and tile_spp pointers are all set
+octpt_status check_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a, bool buffers) {
     octpt_status st = check_tile_render(ctx, "render_adaptive", p);
     if (st != OCTPT_OK) return st;
     if (!a) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: adaptive params NULL");
-    if (!d_accum || !d_moments || !tile_spp)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: NULL accum, moments or tile_spp buffer");
+    if (!buffers) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: NULL accum, moments or tile_spp buffer");
     if (a->min_spp < 2u || a->step_spp < 1u)
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: min_spp must be >= 2 and step_spp >= 1");
     for (float x : {a->threshold, a->luminance_floor})
         if (!(x > 0.0f) || !std::isfinite(x))
             return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: threshold and luminance_floor must be positive and finite");
+    if (!(a->neighbour_weight >= 0.0f && a->neighbour_weight <= 1.0f))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: neighbour_weight must be in [0, 1]");
+    if (a->reserved[0] | a->reserved[1] | a->reserved[2])
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: the reserved words must be 0");
     if (p->spp_start != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: a fresh render (spp_start must be 0)");
     if (p->spp_count < a->min_spp)
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: spp_count (the per-pixel cap) must be >= min_spp");
     if (p->branch_count > 1u)
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "render_adaptive: branch_count > 1 (its pass boundaries fix the round sizes)");
+    return OCTPT_OK;
+}
+
+// the drivers' device form after the NULL-context check
+octpt_status adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a,
+                             float *d_accum, float *d_moments, uint32_t *d_seg, uint32_t *tile_spp,
+                             octpt_adaptive_result *result, void *stream) {
+    octpt_status st = check_adaptive(ctx, p, a, d_accum && d_moments && tile_spp);
+    if (st != OCTPT_OK) return st;
     try {
         join_inflight(ctx);
         DevRender R{};
@@ -2938,10 +2978,12 @@ octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_par
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = static_cast<hipStream_t>(stream);
         const uint32_t T = frame_tiles(p->width, p->height), max_spp = p->spp_count;
-        // the two tables below are rewritten every round, each time after the stream has drained; a call on another
+        const bool spread = a->neighbour_weight != 0.0f;  // C34: the plane the host reads is the spread one
+        // the tables below are rewritten every round, each time after the stream has drained; a call on another
         // stream ended with its own drain
         if ((st = grow_buf(ctx, ctx->d_tile_spp, ctx->tile_spp_cap, (size_t)T)) != OCTPT_OK) return st;
         if ((st = grow_buf(ctx, ctx->d_tile_err, ctx->tile_err_cap, (size_t)T)) != OCTPT_OK) return st;
+        if (spread && (st = grow_buf(ctx, ctx->d_tile_spread, ctx->tile_spread_cap, (size_t)T)) != OCTPT_OK) return st;
         float4 *acc = reinterpret_cast<float4 *>(d_accum);
         float2 *mom = reinterpret_cast<float2 *>(d_moments);
         HIP_TRY(ctx, launch_adaptive_init(p->width * p->height, acc, mom, s));
@@ -2965,7 +3007,11 @@ octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_par
             for (uint32_t t : active) tile_spp[t] = n;
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tile_spp, tile_spp, (size_t)T * 4, hipMemcpyHostToDevice, s));
             HIP_TRY(ctx, launch_tile_error(p->width, p->height, a->luminance_floor, mom, ctx->d_tile_spp, ctx->d_tile_err, s));
-            HIP_TRY(ctx, hipMemcpyAsync(err.data(), ctx->d_tile_err, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+            if (spread)
+                HIP_TRY(ctx, launch_tile_error_spread(p->width, p->height, a->neighbour_weight, ctx->d_tile_err,
+                                                      ctx->d_tile_spread, s));
+            HIP_TRY(ctx, hipMemcpyAsync(err.data(), spread ? ctx->d_tile_spread : ctx->d_tile_err, (size_t)T * 4,
+                                        hipMemcpyDeviceToHost, s));
             HIP_TRY(ctx, hipStreamSynchronize(s));
             next.clear();
             for (uint32_t t : active)
@@ -2991,10 +3037,9 @@ octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_par
     }
 }
 
-octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
-                                   float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
-                                   octpt_adaptive_result *result) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+// the drivers' host form after the NULL-context check
+octpt_status adaptive_host(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a, float *accum,
+                           float *moments, uint32_t *tile_spp, uint8_t *out_rgba8, octpt_adaptive_result *result) {
     octpt_status st = check_tile_render(ctx, "render_adaptive", p);
     if (st != OCTPT_OK) return st;
     if (!accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: accum NULL");
@@ -3010,8 +3055,8 @@ octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p,
         if (e == hipSuccess) e = hipMalloc(&d[1], n * 8);
         if (e == hipSuccess && out_rgba8) e = hipMalloc(&d[2], n * 4);
         if (e == hipSuccess) {
-            st = octpt_render_adaptive_device(ctx, p, a, static_cast<float *>(d[0]), static_cast<float *>(d[1]), nullptr,
-                                              spp.data(), result, ctx->stream);
+            st = adaptive_device(ctx, p, a, static_cast<float *>(d[0]), static_cast<float *>(d[1]), nullptr, spp.data(),
+                                 result, ctx->stream);
             if (st == OCTPT_OK && out_rgba8)
                 e = launch_tonemap(static_cast<float4 *>(d[0]), static_cast<uchar4 *>(d[2]), (uint32_t)n, ctx->d_lut_byte,
                                    ctx->stream);
@@ -3030,6 +3075,296 @@ octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p,
         return fail(ctx, OCTPT_ERR_OOM, "host allocation");
     } catch (...) {
         return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_adaptive");
+    }
+}
+
+}  // namespace
+
+octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
+                                          float *d_accum, float *d_moments, uint32_t *d_seg, uint32_t *tile_spp,
+                                          octpt_adaptive_result *result, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    const octpt_adaptive_params_ex x = a ? adaptive_ex_of(*a) : octpt_adaptive_params_ex{};
+    return adaptive_device(ctx, p, a ? &x : nullptr, d_accum, d_moments, d_seg, tile_spp, result, stream);
+}
+
+octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
+                                   float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
+                                   octpt_adaptive_result *result) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    const octpt_adaptive_params_ex x = a ? adaptive_ex_of(*a) : octpt_adaptive_params_ex{};
+    return adaptive_host(ctx, p, a ? &x : nullptr, accum, moments, tile_spp, out_rgba8, result);
+}
+
+octpt_status octpt_render_adaptive_ex_device(octpt_ctx *ctx, const octpt_render_params *p,
+                                             const octpt_adaptive_params_ex *a, float *d_accum, float *d_moments,
+                                             uint32_t *d_seg, uint32_t *tile_spp, octpt_adaptive_result *result,
+                                             void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    return adaptive_device(ctx, p, a, d_accum, d_moments, d_seg, tile_spp, result, stream);
+}
+
+octpt_status octpt_render_adaptive_ex(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a,
+                                      float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
+                                      octpt_adaptive_result *result) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    return adaptive_host(ctx, p, a, accum, moments, tile_spp, out_rgba8, result);
+}
+
+// ---------------- final-quality adaptive frames: clamp, seam rule, sample variance, finished frame ----------------
+octpt_status octpt_set_sample_clamp(octpt_ctx *ctx, float max_luminance) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!(max_luminance >= 0.0f)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample clamp must be >= 0 (0 or +inf: off), not NaN");
+    join_inflight(ctx);  // a frame in flight keeps the value its call was made with
+    ctx->sample_clamp = std::isfinite(max_luminance) ? max_luminance : 0.0f;
+    for (octpt_ctx *sc : ctx->sub) {
+        const octpt_status st = octpt_set_sample_clamp(sc, max_luminance);
+        if (st != OCTPT_OK) return fail(ctx, st, sc->err);
+    }
+    return OCTPT_OK;
+}
+
+namespace {
+
+octpt_status check_spread(octpt_ctx *ctx, uint32_t W, uint32_t H, float w, const void *error, const void *out) {
+    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: bad resolution");
+    if (!(w >= 0.0f && w <= 1.0f)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: neighbour_weight must be in [0, 1]");
+    if (!error || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: NULL error or output buffer");
+    if (error == out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: the output must not be the input plane");
+    return OCTPT_OK;
+}
+
+octpt_status check_sample_variance(octpt_ctx *ctx, const octpt_sample_variance_params *p, const void *moments,
+                                   const void *tile_spp, const octpt_aov_buffers *g, const void *out) {
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance params NULL");
+    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: bad resolution");
+    if (p->flags & ~OCTPT_DENOISE_DEMODULATE)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: unknown flag (OCTPT_DENOISE_DEMODULATE is the one flag)");
+    if (!moments || !tile_spp || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: NULL moments, tile_spp or output buffer");
+    if (!g || !g->depth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: the depth guide is required");
+    const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
+    if (demod && !g->albedo) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: OCTPT_DENOISE_DEMODULATE needs the albedo guide");
+    if (out == moments || out == tile_spp || out == g->depth || (demod && out == g->albedo))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: the output must be distinct from the inputs");
+    return OCTPT_OK;
+}
+
+}  // namespace
+
+octpt_status octpt_tile_error_spread_device(octpt_ctx *ctx, uint32_t W, uint32_t H, float w, const float *d_error,
+                                            float *d_out, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_spread(ctx, W, H, w, d_error, d_out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_tile_error_spread_device(ctx->sub[0], W, H, w, d_error, d_out, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, launch_tile_error_spread(W, H, w, d_error, d_out, static_cast<hipStream_t>(stream)));
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error_spread");
+    }
+}
+
+octpt_status octpt_tile_error_spread(octpt_ctx *ctx, uint32_t W, uint32_t H, float w, const float *error, float *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_spread(ctx, W, H, w, error, out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_tile_error_spread(ctx->sub[0], W, H, w, error, out);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t T = frame_tiles(W, H);
+        void *d[2] = {};
+        hipError_t e = hipMalloc(&d[0], T * 4);
+        if (e == hipSuccess) e = hipMemcpy(d[0], error, T * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc(&d[1], T * 4);
+        if (e == hipSuccess) {
+            st = octpt_tile_error_spread_device(ctx, W, H, w, static_cast<float *>(d[0]), static_cast<float *>(d[1]), ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[1], T * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "tile_error_spread");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error_spread");
+    }
+}
+
+octpt_status octpt_sample_variance_device(octpt_ctx *ctx, const octpt_sample_variance_params *p, const float *d_moments,
+                                          const uint32_t *d_tile_spp, const octpt_aov_buffers *g, float *d_out,
+                                          void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_sample_variance(ctx, p, d_moments, d_tile_spp, g, d_out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_sample_variance_device(ctx->sub[0], p, d_moments, d_tile_spp, g, d_out, stream);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
+        HIP_TRY(ctx, launch_sample_variance(p->width, p->height, reinterpret_cast<const float2 *>(d_moments), d_tile_spp,
+                                            g->depth, demod ? reinterpret_cast<const float4 *>(g->albedo) : nullptr, d_out,
+                                            static_cast<hipStream_t>(stream)));
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in sample_variance");
+    }
+}
+
+octpt_status octpt_sample_variance(octpt_ctx *ctx, const octpt_sample_variance_params *p, const float *moments,
+                                   const uint32_t *tile_spp, const octpt_aov_buffers *g, float *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_sample_variance(ctx, p, moments, tile_spp, g, out);
+    if (st != OCTPT_OK) return st;
+    try {
+        join_inflight(ctx);
+        if (is_multi(ctx)) {
+            st = octpt_sample_variance(ctx->sub[0], p, moments, tile_spp, g, out);
+            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height, T = frame_tiles(p->width, p->height);
+        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
+        // moments, tile_spp, depth, albedo, then the output
+        const void *h[4] = {moments, tile_spp, g->depth, demod ? g->albedo : nullptr};
+        const size_t bytes[4] = {n * 8, T * 4, n * 4, n * 16};
+        void *d[5] = {};
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+            if (!h[i]) continue;
+            if ((e = hipMalloc(&d[i], bytes[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], bytes[i], hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) e = hipMalloc(&d[4], n * 4);
+        if (e == hipSuccess) {
+            const octpt_aov_buffers dg{static_cast<float *>(d[3]), nullptr, static_cast<float *>(d[2]), nullptr, nullptr};
+            st = octpt_sample_variance_device(ctx, p, static_cast<float *>(d[0]), static_cast<uint32_t *>(d[1]), &dg,
+                                              static_cast<float *>(d[4]), ctx->stream);
+            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[4], n * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "sample_variance");
+        return OCTPT_OK;
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in sample_variance");
+    }
+}
+
+octpt_status octpt_render_final_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_final_params *f,
+                                       float *d_accum, float *d_moments, float *d_out, float *d_out_variance,
+                                       uint32_t *tile_spp, octpt_adaptive_result *result, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!f) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: final params NULL");
+    // every refusal of the four steps, before any buffer is touched
+    octpt_status st = check_adaptive(ctx, p, &f->adaptive, d_accum && d_moments && tile_spp);
+    if (st != OCTPT_OK) return st;
+    const bool demod = (f->filter.flags & OCTPT_DENOISE_DEMODULATE) != 0u;
+    {
+        // the filter's own checks of its parameters; its buffers are this call's and the context's planes
+        const octpt_aov_buffers some{d_accum, d_accum, d_accum, nullptr, nullptr};
+        if ((st = check_denoise_variance(ctx, &f->filter, d_accum, d_accum, &some, d_out)) != OCTPT_OK) return st;
+    }
+    if (f->filter.width != p->width || f->filter.height != p->height)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: the filter's width / height differ from the render's");
+    if (d_out == d_accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: d_out must not alias d_accum");
+    try {
+        join_inflight(ctx);
+        {
+            DevRender R{};
+            if ((st = make_render(ctx, p, R)) != OCTPT_OK) return st;
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height, T = frame_tiles(p->width, p->height);
+        // the context's planes, grow-only; one that has to grow may still be read by an earlier call on another
+        // stream: drain first
+        if (n > ctx->fin_normal_cap || n > ctx->fin_depth_cap || n > ctx->fin_var_cap || (demod && n > ctx->fin_albedo_cap) ||
+            T > ctx->tile_spp_cap)
+            HIP_TRY(ctx, hipDeviceSynchronize());
+        if ((st = grow_buf(ctx, ctx->fin_normal, ctx->fin_normal_cap, n)) != OCTPT_OK) return st;
+        if ((st = grow_buf(ctx, ctx->fin_depth, ctx->fin_depth_cap, n)) != OCTPT_OK) return st;
+        if ((st = grow_buf(ctx, ctx->fin_var, ctx->fin_var_cap, n)) != OCTPT_OK) return st;
+        if (demod && (st = grow_buf(ctx, ctx->fin_albedo, ctx->fin_albedo_cap, n)) != OCTPT_OK) return st;
+        // 1. the adaptive render; it leaves its final tile_spp in the context's device table
+        if ((st = octpt_render_adaptive_ex_device(ctx, p, &f->adaptive, d_accum, d_moments, nullptr, tile_spp, result,
+                                                  stream)) != OCTPT_OK)
+            return st;
+        // 2. the guides
+        const octpt_aov_buffers g{demod ? reinterpret_cast<float *>(ctx->fin_albedo) : nullptr,
+                                  reinterpret_cast<float *>(ctx->fin_normal), ctx->fin_depth, nullptr, nullptr};
+        if ((st = octpt_render_aov_device(ctx, p, &g, stream)) != OCTPT_OK) return st;
+        // 3. the variance of the pixel means
+        const octpt_sample_variance_params vp{p->width, p->height, f->filter.flags & OCTPT_DENOISE_DEMODULATE};
+        if ((st = octpt_sample_variance_device(ctx, &vp, d_moments, ctx->d_tile_spp, &g, ctx->fin_var, stream)) != OCTPT_OK)
+            return st;
+        // 4. the filter
+        return octpt_denoise_variance_device(ctx, &f->filter, d_accum, ctx->fin_var, &g, d_out, d_out_variance, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_final");
+    }
+}
+
+octpt_status octpt_render_final(octpt_ctx *ctx, const octpt_render_params *p, const octpt_final_params *f, float *accum,
+                                float *moments, float *out, float *out_variance, uint32_t *tile_spp, uint8_t *out_rgba8,
+                                octpt_adaptive_result *result) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_tile_render(ctx, "render_final", p);
+    if (st != OCTPT_OK) return st;
+    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: out NULL");
+    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
+    try {
+        join_inflight(ctx);
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t n = (size_t)p->width * p->height;
+        std::vector<uint32_t> spp(frame_tiles(p->width, p->height));
+        void *d[5] = {};  // accum, moments, out, out variance, rgba8
+        hipError_t e = hipMalloc(&d[0], n * 16);
+        if (e == hipSuccess) e = hipMalloc(&d[1], n * 8);
+        if (e == hipSuccess) e = hipMalloc(&d[2], n * 16);
+        if (e == hipSuccess && out_variance) e = hipMalloc(&d[3], n * 4);
+        if (e == hipSuccess && out_rgba8) e = hipMalloc(&d[4], n * 4);
+        if (e == hipSuccess) {
+            st = octpt_render_final_device(ctx, p, f, static_cast<float *>(d[0]), static_cast<float *>(d[1]),
+                                           static_cast<float *>(d[2]), static_cast<float *>(d[3]), spp.data(), result,
+                                           ctx->stream);
+            if (st == OCTPT_OK && out_rgba8)
+                e = launch_tonemap(static_cast<float4 *>(d[2]), static_cast<uchar4 *>(d[4]), (uint32_t)n, ctx->d_lut_byte,
+                                   ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[2], n * 16, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && accum) e = hipMemcpy(accum, d[0], n * 16, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && moments) e = hipMemcpy(moments, d[1], n * 8, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && out_variance) e = hipMemcpy(out_variance, d[3], n * 4, hipMemcpyDeviceToHost);
+            if (st == OCTPT_OK && e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d[4], n * 4, hipMemcpyDeviceToHost);
+        }
+        for (void *q : d)
+            if (q) (void)hipFree(q);
+        if (st != OCTPT_OK) return st;
+        if (e != hipSuccess) return hip_fail(ctx, e, "render_final");
+        if (tile_spp) std::copy(spp.begin(), spp.end(), tile_spp);
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
+    } catch (...) {
+        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_final");
     }
 }
 

@@ -360,14 +360,20 @@ hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuff
 // the host's snapshot of an iteration's counters: queue q's kSegs segment counts, then the kSegs item
 // counters, written by one 128-thread block into pinned host memory (enqueue_wavefront's steering)
 hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_out, hipStream_t stream);
-// moments (nullable, C31): the instance that also keeps the samples' luminance moments, full frame, image order
+// moments (nullable, C31): the instance that also keeps the samples' luminance moments, full frame, image order;
+// clamp (C33): 0 = off, else the instances that clamp each sample's luminance to it
 hipError_t launch_wf_resolve(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp, float4 *accum,
-                             uint32_t *segcount, float2 *moments, hipStream_t stream);
+                             uint32_t *segcount, float2 *moments, float clamp, hipStream_t stream);
 // an adaptive render's start (C32): n pixels of accum to (0, 0, 0, 1) and of moments to (0, 0)
 hipError_t launch_adaptive_init(uint32_t n, float4 *accum, float2 *moments, hipStream_t stream);
 // the per-tile error of C32: one launch, one wave64 per 8 x 8 tile of the W x H frame
 hipError_t launch_tile_error(uint32_t W, uint32_t H, float luminance_floor, const float2 *moments,
                              const uint32_t *tile_spp, float *error, hipStream_t stream);
+// the seam rule of C34: out[t] = max(error[t], w * the largest error of t's neighbours), one launch
+hipError_t launch_tile_error_spread(uint32_t W, uint32_t H, float w, const float *error, float *out, hipStream_t stream);
+// the variance of the pixel means of C35: one launch, one thread per pixel; albedo nullable (demodulate)
+hipError_t launch_sample_variance(uint32_t W, uint32_t H, const float2 *moments, const uint32_t *tile_spp,
+                                  const float *depth, const float4 *albedo, float *out, hipStream_t stream);
 int extend_blocks_per_cu(const DevScene &S);
 hipError_t launch_intersect(const DevScene &S, const float *rays, const uint32_t *last_prim,
                             const float *last_normal, uint32_t n, float *t, uint32_t *prim, float *normal,

@@ -2566,11 +2566,21 @@ __device__ __forceinline__ void running_moments(float2 &m, v3 c, uint32_t spp, u
 
 // resolve: per pixel, the chunk's samples in sample order into the running mean.  kMoments: the
 // instance that also keeps the running means of the samples' luminance moments, one float2 read-modify-write
-// per pixel (`moments`: full frame, image order; the tile-list renders)
-template <bool kMoments>
+// per pixel (`moments`: full frame, image order; the tile-list renders).  kClamp: the instances that
+// scale a sample whose luminance exceeds `clamp` down to it before both running means; only they read `clamp`
+__device__ __forceinline__ v3 clamp_sample(v3 c, float clamp) {
+    const float l = luminance(c.x, c.y, c.z);
+    if (l > clamp) {  // a NaN compares false: the sample passes unchanged
+        const float k = clamp / l;
+        c = V(c.x * k, c.y * k, c.z * k);
+    }
+    return c;
+}
+
+template <bool kMoments, bool kClamp>
 __device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp,
                                               float4 *__restrict__ accum, uint32_t *__restrict__ segcount,
-                                              float2 *__restrict__ moments) {
+                                              float2 *__restrict__ moments, float clamp) {
     const uint32_t px_item = blockIdx.x * kBlock + threadIdx.x;
     if (px_item >= R.total_items) return;
     uint32_t x, y;
@@ -2588,8 +2598,10 @@ __device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuff
         const uint32_t w = __float_as_uint(c.w);
         segs += w & 0x7FFFFFFFu;
         if (!R.subs) {
-            running_mean(fb, V(c.x, c.y, c.z), R.spp_start + s, 1u);
-            if constexpr (kMoments) running_moments(mo, V(c.x, c.y, c.z), R.spp_start + s, 1u);
+            v3 cs = V(c.x, c.y, c.z);
+            if constexpr (kClamp) cs = clamp_sample(cs, clamp);
+            running_mean(fb, cs, R.spp_start + s, 1u);
+            if constexpr (kMoments) running_moments(mo, cs, R.spp_start + s, 1u);
             continue;
         }
         // branch schedule (C20): a pass's branches fold into one sample of weight bc; the colour
@@ -2605,7 +2617,8 @@ __device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuff
         }
         if (b + 1u == bc) {
             const float inv = 1.0f / (float)bc;
-            const v3 folded = split ? vscale(sum, inv) : L0;
+            v3 folded = split ? vscale(sum, inv) : L0;
+            if constexpr (kClamp) folded = clamp_sample(folded, clamp);
             running_mean(fb, folded, sb.x, bc);
             if constexpr (kMoments) running_moments(mo, folded, sb.x, bc);
         }
@@ -2617,14 +2630,28 @@ __device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuff
 
 __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
                                                             float4 *__restrict__ accum, uint32_t *__restrict__ segcount) {
-    resolve_pixel<false>(R, B, chunk_spp, accum, segcount, nullptr);
+    resolve_pixel<false, false>(R, B, chunk_spp, accum, segcount, nullptr, 0.0f);
 }
 
 __global__ __launch_bounds__(kBlock) void wf_resolve_moments_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
                                                                     float4 *__restrict__ accum,
                                                                     uint32_t *__restrict__ segcount,
                                                                     float2 *__restrict__ moments) {
-    resolve_pixel<true>(R, B, chunk_spp, accum, segcount, moments);
+    resolve_pixel<true, false>(R, B, chunk_spp, accum, segcount, moments, 0.0f);
+}
+
+// the two instances with the sample clamp (C33): launched only while a clamp is set on the context
+__global__ __launch_bounds__(kBlock) void wf_resolve_clamp_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
+                                                                  float4 *__restrict__ accum,
+                                                                  uint32_t *__restrict__ segcount, float clamp) {
+    resolve_pixel<false, true>(R, B, chunk_spp, accum, segcount, nullptr, clamp);
+}
+
+__global__ __launch_bounds__(kBlock) void wf_resolve_moments_clamp_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
+                                                                          float4 *__restrict__ accum,
+                                                                          uint32_t *__restrict__ segcount,
+                                                                          float2 *__restrict__ moments, float clamp) {
+    resolve_pixel<true, true>(R, B, chunk_spp, accum, segcount, moments, clamp);
 }
 
 // one ray per thread closest-hit query (Scene::hit) for octpt_intersect
@@ -3285,6 +3312,60 @@ __global__ __launch_bounds__(256) void adaptive_init_kernel(uint32_t n, float4 *
     moments[i] = make_float2(0.0f, 0.0f);
 }
 
+// the seam rule: a tile's error raised to w times the largest error among its up to eight neighbours in
+// the tile grid.  One thread per tile, nine loads; w == 0 copies (no multiply: +inf * 0 never appears)
+__global__ __launch_bounds__(256) void tile_error_spread_kernel(uint32_t tiles_x, uint32_t tiles_y, float w,
+                                                                const float *__restrict__ error,
+                                                                float *__restrict__ out) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= tiles_x * tiles_y) return;
+    const float e = error[t];
+    if (w == 0.0f) {
+        out[t] = e;
+        return;
+    }
+    const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
+    const uint32_t x0 = tx > 0u ? tx - 1u : 0u, x1 = min(tx + 1u, tiles_x - 1u);
+    const uint32_t y0 = ty > 0u ? ty - 1u : 0u, y1 = min(ty + 1u, tiles_y - 1u);
+    bool any = false;
+    float M = 0.0f;
+    for (uint32_t y = y0; y <= y1; ++y)
+        for (uint32_t x = x0; x <= x1; ++x) {
+            if (x == tx && y == ty) continue;
+            const float u = error[y * tiles_x + x];
+            M = any ? fmaxf(M, u) : u;
+            any = true;
+        }
+    out[t] = any ? fmaxf(e, w * M) : e;  // a one-tile frame has no neighbour
+}
+
+// the variance of each pixel's mean luminance from the sample moments, for C29's filter: one thread
+// per pixel.  albedo (nullable): the variance moved into the demodulated signal
+__global__ __launch_bounds__(256) void sample_variance_kernel(uint32_t W, uint32_t H, uint32_t tiles_x,
+                                                              const float2 *__restrict__ moments,
+                                                              const uint32_t *__restrict__ tile_spp,
+                                                              const float *__restrict__ depth,
+                                                              const float4 *__restrict__ albedo,
+                                                              float *__restrict__ out) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= W * H) return;
+    const uint32_t y = p / W, x = p - y * W;
+    const uint32_t n = tile_spp[(y / kTile) * tiles_x + x / kTile];
+    float v = 0.0f;
+    if (fabsf(depth[p]) < __builtin_inff() && n >= 2u) {
+        const float2 m = moments[p];
+        const float d = m.y - m.x * m.x;
+        v = d > 0.0f ? d : 0.0f;  // a NaN becomes 0
+        v = v / (float)(n - 1u);
+        if (albedo) {
+            const float4 a = albedo[p];
+            const float la = luminance(fmaxf(a.x, 1e-3f), fmaxf(a.y, 1e-3f), fmaxf(a.z, 1e-3f));
+            v = v / (la * la);
+        }
+    }
+    out[p] = v;
+}
+
 // ===========================================================================
 // The variance-guided a-trous filter (SVGF, Schied et al. 2017).  The working frames hold
 // (s.rgb, v) per pixel, so a tap's signal and variance come in one 16-byte load; the input's alpha is read by the
@@ -3607,9 +3688,16 @@ hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_o
 }
 
 hipError_t launch_wf_resolve(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp, float4 *accum,
-                             uint32_t *segcount, float2 *moments, hipStream_t stream) {
+                             uint32_t *segcount, float2 *moments, float clamp, hipStream_t stream) {
     const dim3 grid((R.total_items + kBlock - 1u) / kBlock);
-    if (moments)
+    if (clamp != 0.0f) {  // C33: the clamp instances; off, the two kernels as they always were
+        if (moments)
+            hipLaunchKernelGGL(wf_resolve_moments_clamp_kernel, grid, dim3(kBlock), 0, stream, R, B, chunk_spp, accum,
+                               segcount, moments, clamp);
+        else
+            hipLaunchKernelGGL(wf_resolve_clamp_kernel, grid, dim3(kBlock), 0, stream, R, B, chunk_spp, accum, segcount,
+                               clamp);
+    } else if (moments)
         hipLaunchKernelGGL(wf_resolve_moments_kernel, grid, dim3(kBlock), 0, stream, R, B, chunk_spp, accum, segcount,
                            moments);
     else
@@ -3628,6 +3716,20 @@ hipError_t launch_tile_error(uint32_t W, uint32_t H, float luminance_floor, cons
     const uint32_t per_block = kBlock / 64u;
     hipLaunchKernelGGL(tile_error_kernel, dim3((n_tiles + per_block - 1u) / per_block), dim3(kBlock), 0, stream, W, H,
                        tiles_x, n_tiles, luminance_floor, moments, tile_spp, error);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_error_spread(uint32_t W, uint32_t H, float w, const float *error, float *out, hipStream_t stream) {
+    const uint32_t tiles_x = (W + kTile - 1u) / kTile, tiles_y = (H + kTile - 1u) / kTile;
+    hipLaunchKernelGGL(tile_error_spread_kernel, dim3((tiles_x * tiles_y + 255u) / 256u), dim3(256), 0, stream, tiles_x,
+                       tiles_y, w, error, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_variance(uint32_t W, uint32_t H, const float2 *moments, const uint32_t *tile_spp,
+                                  const float *depth, const float4 *albedo, float *out, hipStream_t stream) {
+    hipLaunchKernelGGL(sample_variance_kernel, dim3((W * H + 255u) / 256u), dim3(256), 0, stream, W, H,
+                       (W + kTile - 1u) / kTile, moments, tile_spp, depth, albedo, out);
     return hipGetLastError();
 }
 

@@ -617,11 +617,14 @@ class HipRenderer:
                                                       C.c_void_p(stream) if stream else None))
 
     def render_adaptive(self, settings: RenderSettings, min_spp: int, step_spp: int, threshold: float,
-                        luminance_floor: float = LUMINANCE_FLOOR, with_rgba: bool = False):
+                        luminance_floor: float = LUMINANCE_FLOOR, with_rgba: bool = False,
+                        neighbour_weight: float = 0.0):
         """Render until every 8x8 tile's error (tile_error) is at most `threshold`, or settings.spp samples per
         pixel are reached (octpt_render_adaptive): min_spp samples everywhere, then rounds of step_spp into the
-        tiles still above the threshold.  Returns (accum [H, W, 4], moments [H, W, 2], tile_spp u32 per tile,
-        result dict: rounds, tile_samples, converged_tiles, total_tiles -- and "rgba" with with_rgba)."""
+        tiles still above the threshold.  neighbour_weight > 0 (octpt_render_adaptive_ex): the seam rule -- a tile
+        goes on while a neighbour's error times the weight is above the threshold (tile_error_spread).  Returns
+        (accum [H, W, 4], moments [H, W, 2], tile_spp u32 per tile, result dict: rounds, tile_samples,
+        converged_tiles, total_tiles -- and "rgba" with with_rgba)."""
         W, H = settings.width, settings.height
         accum = np.empty((H, W, 4), np.float32)
         moments = np.empty((H, W, 2), np.float32)
@@ -630,9 +633,13 @@ class HipRenderer:
         self.max_depth = settings.max_depth
         self.seed = settings.seed
         p = self.params(W, H, 0, settings.spp)
-        a = _lib.AdaptiveParams(min_spp, step_spp, threshold, luminance_floor)
+        if neighbour_weight == 0:
+            entry, a = self._lib.octpt_render_adaptive, _lib.AdaptiveParams(min_spp, step_spp, threshold, luminance_floor)
+        else:
+            entry = self._lib.octpt_render_adaptive_ex
+            a = _lib.AdaptiveParamsEx(min_spp, step_spp, threshold, luminance_floor, neighbour_weight)
         res = _lib.AdaptiveResult()
-        self._check(self._lib.octpt_render_adaptive(
+        self._check(entry(
             self._ctx, C.byref(p), C.byref(a), accum.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p),
             tile_spp.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.c_void_p) if rgba is not None else None,
             C.byref(res)))
@@ -650,6 +657,107 @@ class HipRenderer:
         self._check(self._lib.octpt_render_adaptive_device(
             self._ctx, C.byref(params), C.byref(adaptive), C.c_void_p(d_accum), C.c_void_p(d_moments),
             C.c_void_p(d_seg_count) if d_seg_count else None, tile_spp.ctypes.data_as(C.c_void_p), C.byref(res),
+            C.c_void_p(stream) if stream else None))
+        return tile_spp, res.as_dict()
+
+    # ------------------------------------------------------------ final-quality adaptive frames (C33-C36)
+    def set_sample_clamp(self, max_luminance: float) -> None:
+        """Clamp every sample's luminance to max_luminance in resolve (octpt_set_sample_clamp), for every later
+        wavefront render of this renderer; 0 or +inf switch the clamp off."""
+        self._check(self._lib.octpt_set_sample_clamp(self._ctx, max_luminance))
+
+    def tile_error_spread(self, error: np.ndarray, W: int, H: int, neighbour_weight: float) -> np.ndarray:
+        """The seam rule (octpt_tile_error_spread): each tile's error raised to neighbour_weight times the largest
+        error among its up to eight neighbours in the W x H frame's tile grid."""
+        e = np.ascontiguousarray(error, np.float32).reshape(-1)
+        if e.size != tile_count(W, H):
+            raise ValueError(f"error must hold one entry per tile ({tile_count(W, H)})")
+        out = np.empty_like(e)
+        self._check(self._lib.octpt_tile_error_spread(self._ctx, W, H, neighbour_weight, e.ctypes.data_as(C.c_void_p),
+                                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def tile_error_spread_device(self, W: int, H: int, neighbour_weight: float, d_error: int, d_out: int,
+                                 stream: int | None = None) -> None:
+        """Enqueue octpt_tile_error_spread_device on raw device pointers (d_out must not be d_error)."""
+        self._check(self._lib.octpt_tile_error_spread_device(self._ctx, W, H, neighbour_weight, C.c_void_p(d_error),
+                                                             C.c_void_p(d_out), C.c_void_p(stream) if stream else None))
+
+    def sample_variance(self, moments: np.ndarray, tile_spp: np.ndarray, aov: dict, demodulate: bool = True) -> np.ndarray:
+        """The variance [H, W] of each pixel's mean luminance (octpt_sample_variance) from the sample moments
+        [H, W, 2] of a render whose tile t holds tile_spp[t] samples per pixel, with render_aov's depth (and albedo
+        with demodulate, which moves it into the signal denoise_variance filters): what denoise_variance takes."""
+        m = np.ascontiguousarray(moments, np.float32)
+        H, W = m.shape[:2]
+        n = np.ascontiguousarray(tile_spp, np.uint32).reshape(-1)
+        if m.shape != (H, W, 2) or n.size != tile_count(W, H):
+            raise ValueError(f"moments must be [H, W, 2] and tile_spp hold one entry per tile ({tile_count(W, H)})")
+        keep = []
+        b = self._guides(aov, ("depth",) + (("albedo",) if demodulate else ()), W, H, keep)
+        p = _lib.SampleVarianceParams(W, H, _lib.DENOISE_DEMODULATE if demodulate else 0)
+        out = np.empty((H, W), np.float32)
+        self._check(self._lib.octpt_sample_variance(self._ctx, C.byref(p), m.ctypes.data_as(C.c_void_p),
+                                                    n.ctypes.data_as(C.c_void_p), C.byref(b),
+                                                    out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sample_variance_device(self, params: "_lib.SampleVarianceParams", d_moments: int, d_tile_spp: int, guides: dict,
+                               d_out: int, stream: int | None = None) -> None:
+        """Enqueue octpt_sample_variance_device on raw device pointers: guides {depth, albedo}."""
+        b = _lib.AovBuffers(**{k: C.c_void_p(int(v)) for k, v in guides.items() if v})
+        self._check(self._lib.octpt_sample_variance_device(self._ctx, C.byref(params), C.c_void_p(d_moments),
+                                                           C.c_void_p(d_tile_spp), C.byref(b), C.c_void_p(d_out),
+                                                           C.c_void_p(stream) if stream else None))
+
+    def render_adaptive_ex_device(self, params: "_lib.RenderParams", adaptive: "_lib.AdaptiveParamsEx", d_accum: int,
+                                  d_moments: int, d_seg_count: int | None = None, stream: int | None = None):
+        """octpt_render_adaptive_ex_device on raw device pointers: render_adaptive_device with the seam rule's
+        neighbour weight; returns (tile_spp, result dict)."""
+        tile_spp = np.zeros(tile_count(params.width, params.height), np.uint32)
+        res = _lib.AdaptiveResult()
+        self._check(self._lib.octpt_render_adaptive_ex_device(
+            self._ctx, C.byref(params), C.byref(adaptive), C.c_void_p(d_accum), C.c_void_p(d_moments),
+            C.c_void_p(d_seg_count) if d_seg_count else None, tile_spp.ctypes.data_as(C.c_void_p), C.byref(res),
+            C.c_void_p(stream) if stream else None))
+        return tile_spp, res.as_dict()
+
+    def render_final(self, settings: RenderSettings, min_spp: int, step_spp: int, threshold: float,
+                     neighbour_weight: float = 0.5, luminance_floor: float = LUMINANCE_FLOOR, iterations: int = 5,
+                     sigma_luminance: float = 4.0, sigma_normal: float = 0.3, sigma_depth: float = 0.1,
+                     demodulate: bool = True, with_rgba: bool = False):
+        """A finished frame (octpt_render_final): render_adaptive with the seam rule, the guide buffers, the variance
+        of the pixel means (sample_variance) and the variance-guided filter (denoise_variance) in one call.  Returns
+        a dict: out [H, W, 4] (filtered), out_variance [H, W], accum and moments (unfiltered), tile_spp, result -- and
+        rgba (the tone map of out) with with_rgba.  The clamp of set_sample_clamp applies."""
+        W, H = settings.width, settings.height
+        r = {"accum": np.empty((H, W, 4), np.float32), "moments": np.empty((H, W, 2), np.float32),
+             "out": np.empty((H, W, 4), np.float32), "out_variance": np.empty((H, W), np.float32),
+             "tile_spp": np.zeros(tile_count(W, H), np.uint32)}
+        if with_rgba:
+            r["rgba"] = np.zeros((H, W, 4), np.uint8)
+        self.max_depth = settings.max_depth
+        self.seed = settings.seed
+        p = self.params(W, H, 0, settings.spp)
+        f = _lib.FinalParams(
+            _lib.AdaptiveParamsEx(min_spp, step_spp, threshold, luminance_floor, neighbour_weight),
+            _lib.DenoiseVarianceParams(W, H, iterations, sigma_luminance, luminance_floor, sigma_normal, sigma_depth,
+                                       _lib.DENOISE_DEMODULATE if demodulate else 0))
+        res = _lib.AdaptiveResult()
+        P = lambda k: r[k].ctypes.data_as(C.c_void_p) if k in r else None  # noqa: E731
+        self._check(self._lib.octpt_render_final(self._ctx, C.byref(p), C.byref(f), P("accum"), P("moments"), P("out"),
+                                                 P("out_variance"), P("tile_spp"), P("rgba"), C.byref(res)))
+        r["result"] = res.as_dict()
+        return r
+
+    def render_final_device(self, params: "_lib.RenderParams", final: "_lib.FinalParams", d_accum: int, d_moments: int,
+                            d_out: int, d_out_variance: int | None = None, stream: int | None = None):
+        """octpt_render_final_device on raw device pointers (d_out must not be d_accum); returns (tile_spp, result
+        dict).  The call drains `stream` once per adaptive round."""
+        tile_spp = np.zeros(tile_count(params.width, params.height), np.uint32)
+        res = _lib.AdaptiveResult()
+        self._check(self._lib.octpt_render_final_device(
+            self._ctx, C.byref(params), C.byref(final), C.c_void_p(d_accum), C.c_void_p(d_moments), C.c_void_p(d_out),
+            C.c_void_p(d_out_variance) if d_out_variance else None, tile_spp.ctypes.data_as(C.c_void_p), C.byref(res),
             C.c_void_p(stream) if stream else None))
         return tile_spp, res.as_dict()
 

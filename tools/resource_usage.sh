@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers, scratch, LDS and occupancy of the wavefront, preview, guide-buffer, denoise, temporal and variance kernels (octpt_kernels.hip) and of the
+# Registers, scratch, LDS and occupancy of the wavefront (resolve included), preview, guide-buffer, denoise, temporal, variance and tile-error kernels (octpt_kernels.hip) and of the
 # section builder's count and emit kernels (octpt_build.hip) as the compiler reports them (kernel-resource-usage
 # remarks): tools/resource_usage.sh [-DFLAG ...].  CPU only (device-only compiles).
 cd "$(dirname "$0")/.."
@@ -12,5 +12,5 @@ for SRC in octpt_kernels.hip octpt_build.hip; do
   /remark:     TotalSGPRs: / {sg = $NF}
   /ScratchSize/ {sc = $NF}
   /Occupancy/ {occ = $NF}
-  /LDS Size/ {if (n ~ /extend|shade|seed|drain|beam|preview|gbuffer|atrous|denoise|temporal|variance|section_count|section_emit/) printf "%-70s VGPR %3s SGPR %3s scratch %3s LDS %5s occ %s\n", substr(n, 1, 70), v, sg, sc, $NF, occ}'
+  /LDS Size/ {if (n ~ /extend|shade|seed|drain|resolve|beam|preview|gbuffer|atrous|denoise|temporal|variance|tile_error|section_count|section_emit/) printf "%-70s VGPR %3s SGPR %3s scratch %3s LDS %5s occ %s\n", substr(n, 1, 70), v, sg, sc, $NF, occ}'
 done
