@@ -900,7 +900,7 @@ static int next_intersection(ctx_t *c, ray_t *r, uint32_t *segs) {
 /* sky + sun (scene/mod.rs:216-268, 384-426)                                   */
 /* ------------------------------------------------------------------------- */
 static const float SKY_COLOR[4] = {0.5f, 0.7f, 1.0f, 1.0f}; /* scene/mod.rs:170 */
-static int sun_intersect(const sun_k *k, ray_t *r) { /* :384-405 */
+static int sun_intersect(const sun_k *k, ray_t *r, ref_stats *st) { /* :384-405 */
     v3 d = r->d;
     if (!k->draw_texture || vdot(d, k->sw) < 0.5f) return 0;
     float a = PI_F / 2.0f - ref_math_acos(vdot(d, k->su)) + k->width;
@@ -909,12 +909,13 @@ static int sun_intersect(const sun_k *k, ray_t *r) { /* :384-405 */
         if (b >= 0.0f && b < k->width2) {
             for (int i = 0; i < 4; i++) r->col[i] = k->tex[i];
             for (int i = 0; i < 3; i++) r->col[i] *= k->isect_mul[i];
+            st->sky_sun_textured++;
             return 1;
         }
     }
     return 0;
 }
-static int sun_intersect_diffuse(const sun_k *k, ray_t *r) { /* :406-426 */
+static int sun_intersect_diffuse(const sun_k *k, ray_t *r, ref_stats *st) { /* :406-426 */
     v3 d = r->d;
     if (vdot(d, k->sw) < 0.5f) return 0;
     float a = PI_F / 2.0f - ref_math_acos(vdot(d, k->su)) + k->width;
@@ -923,18 +924,19 @@ static int sun_intersect_diffuse(const sun_k *k, ray_t *r) { /* :406-426 */
         if (b >= 0.0f && b < k->width2) {
             for (int i = 0; i < 4; i++) r->col[i] = k->tex[i];
             for (int i = 0; i < 3; i++) r->col[i] *= k->diffuse_mul[i];
+            st->sky_sun_diffuse++;
             return 1;
         }
     }
     return 0;
 }
-static void add_sun_color(const sun_k *k, ray_t *r) { /* :244-253 */
+static void add_sun_color(const sun_k *k, ray_t *r, ref_stats *st) { /* :244-253 */
     float cr = r->col[0], cg = r->col[1], cb = r->col[2];
-    if (sun_intersect(k, r)) { r->col[0] += cr; r->col[1] += cg; r->col[2] += cb; }
+    if (sun_intersect(k, r, st)) { r->col[0] += cr; r->col[1] += cg; r->col[2] += cb; }
 }
-static void add_sun_color_diffuse_sun(const sun_k *k, ray_t *r) { /* :255-265 */
+static void add_sun_color_diffuse_sun(const sun_k *k, ray_t *r, ref_stats *st) { /* :255-265 */
     float cr = r->col[0], cg = r->col[1], cb = r->col[2];
-    if (sun_intersect_diffuse(k, r)) {
+    if (sun_intersect_diffuse(k, r, st)) {
         float m = k->luminosity;
         r->col[0] = r->col[0] * m + cr;
         r->col[1] = r->col[1] * m + cg;
@@ -942,22 +944,22 @@ static void add_sun_color_diffuse_sun(const sun_k *k, ray_t *r) { /* :255-265 */
     }
 }
 static void sky_set(ray_t *r) { memcpy(r->col, SKY_COLOR, sizeof SKY_COLOR); }
-static void get_sky_color_interp(const sun_k *k, ray_t *r) { sky_set(r); add_sun_color(k, r); r->col[3] = 1.0f; }
-static void get_sky_color(const sun_k *k, ray_t *r, int draw_sun) {
+static void get_sky_color_interp(const sun_k *k, ray_t *r, ref_stats *st) { sky_set(r); add_sun_color(k, r, st); r->col[3] = 1.0f; }
+static void get_sky_color(const sun_k *k, ray_t *r, int draw_sun, ref_stats *st) {
     sky_set(r);
-    if (draw_sun) add_sun_color(k, r);
+    if (draw_sun) add_sun_color(k, r, st);
     r->col[3] = 1.0f;
 }
-static void get_sky_color_diffuse_sun(const sun_k *k, ray_t *r, int diffuse_sun) {
+static void get_sky_color_diffuse_sun(const sun_k *k, ray_t *r, int diffuse_sun, ref_stats *st) {
     sky_set(r);
-    if (diffuse_sun) add_sun_color_diffuse_sun(k, r);
+    if (diffuse_sun) add_sun_color_diffuse_sun(k, r, st);
     r->col[3] = 1.0f;
 }
 
 /* ------------------------------------------------------------------------- */
 /* scatter kernels, src/ray/mod.rs:113-373                                     */
 /* ------------------------------------------------------------------------- */
-static void specular_reflection(const ray_t *self, float roughness, uint32_t *rng, ray_t *tmp) { /* :113-184 */
+static void specular_reflection(ctx_t *c, const ray_t *self, float roughness, uint32_t *rng, ray_t *tmp) { /* :113-184 */
     *tmp = *self;
     tmp->t = INFINITY;
     tmp->u = tmp->v = 0.0f;
@@ -965,6 +967,7 @@ static void specular_reflection(const ray_t *self, float roughness, uint32_t *rn
     tmp->cur_mat = tmp->prev_mat;
     v3 n = self->n, dir = self->d;
     if (roughness > RAY_EPSILON) {
+        c->st.reflect_rough++;
         float sdot = -2.0f * vdot(dir, n);
         v3 spec = vadd(vscale(n, sdot), dir);
         float x1 = ref_rng_next(rng), x2 = ref_rng_next(rng);
@@ -977,10 +980,12 @@ static void specular_reflection(const ray_t *self, float roughness, uint32_t *rn
         tmp->d = vnorm(vadd(vscale(nd, roughness), vscale(spec, 1.0f - roughness)));
         tmp->o = ray_at(tmp, RAY_OFFSET);
     } else {
+        c->st.reflect_mirror++;
         tmp->d = vsub(dir, vscale(n, 2.0f * vdot(dir, n)));
         tmp->o = ray_at(tmp, RAY_OFFSET);
     }
     if (signum_(vdot(n, tmp->d)) == signum_(vdot(n, dir))) { /* :175-181 */
+        c->st.signum_specular++;
         float factor = vdot(n, dir) * -RAY_EPSILON - vdot(tmp->d, n);
         tmp->d = vnorm(vadd(tmp->d, vscale(n, factor)));
     }
@@ -1018,10 +1023,12 @@ static float diffuse_reflection(ctx_t *c, ray_t *self, const ray_t *ray, uint32_
         if (alt_rel + cr > RAY_EPSILON) {
             if ((ref_math_hypot(stx, sty) + cr) + RAY_EPSILON < 1.0f) {
                 if (ref_rng_next(rng) < chance) {
+                    c->st.is_disc_sample++;
                     tx = stx + tx * cr;
                     ty = sty + ty * cr;
                     w = cr * cr / chance;
                 } else {
+                    c->st.is_disc_reject++;
                     while (ref_math_hypot(tx - stx, ty - sty) < cr) {
                         tx -= stx;
                         ty -= sty;
@@ -1037,14 +1044,17 @@ static float diffuse_reflection(ctx_t *c, ray_t *self, const ray_t *ray, uint32_
                 float sun_theta = ref_math_atan2(sty, stx);
                 float seg = ((max_r * max_r - min_r * min_r) * cr) / PI_F;
                 chance *= seg / (cr * cr);
+                if (chance > SUN_MAX_IMPORTANCE_SAMPLE_CHANCE) c->st.is_chance_clamp++;
                 chance = fmin_(chance, SUN_MAX_IMPORTANCE_SAMPLE_CHANCE);
                 if (ref_rng_next(rng) < chance) {
+                    c->st.is_horizon_sample++;
                     r = sqrtf(min_r * min_r * x1 + max_r * max_r * (1.0f - x1));
                     theta = sun_theta + (2.0f * x2 - 1.0f) * cr;
                     tx = r * ref_math_cos(theta);
                     ty = r * ref_math_sin(theta);
                     w = seg / chance;
                 } else {
+                    c->st.is_horizon_reject++;
                     for (;;) {
                         if (!(r > min_r && r < max_r)) break;
                         /* angle_distance, util.rs:134-137 (fmod exact for diff < 4*pi) */
@@ -1077,6 +1087,7 @@ static float diffuse_reflection(ctx_t *c, ray_t *self, const ray_t *ray, uint32_
     self->cur_mat = self->prev_mat;
     self->specular = 0;
     if (signum_(vdot(n, self->d)) == signum_(vdot(n, ray->d))) { /* :367-372 */
+        c->st.signum_diffuse++;
         float factor = signum_(vdot(n, ray->d)) * -RAY_EPSILON - vdot(self->d, self->n);
         self->d = vnorm(vadd(self->d, vscale(n, factor)));
     }
@@ -1093,7 +1104,7 @@ static int path_trace(ctx_t *c, ray_t *ray, int first, uint32_t *rng, fwd_t *fw,
 static int do_specular_reflection(ctx_t *c, const ray_t *ray, ray_t *next, float cum[4], int do_metal,
                                   uint32_t *rng, fwd_t *fw, uint32_t *segs) { /* :160-188 */
     int hit = 0;
-    specular_reflection(ray, c->s->materials[ray->cur_mat].roughness, rng, next);
+    specular_reflection(c, ray, c->s->materials[ray->cur_mat].roughness, rng, next);
     if (fw && do_metal) for (int i = 0; i < 3; i++) fw->T[i] = fw->T[i] * ray->col[i];
     if (path_trace(c, next, 0, rng, fw, segs)) {
         if (do_metal) for (int i = 0; i < 3; i++) cum[i] += ray->col[i] * next->col[i];
@@ -1114,11 +1125,16 @@ static void direct_light_attenuation(ctx_t *c, ray_t *r, float att[4], uint32_t 
         r->o = ray_at(r, RAY_OFFSET);
         if (!next_intersection(c, r, segs)) break;
         float mult = 1.0f - r->col[3];
+        if (r->col[3] == 0.0f) c->st.shadow_hit_alpha0++;
+        else if (r->col[3] == 1.0f) c->st.shadow_hit_opaque++;
+        else c->st.shadow_hit_partial++;
         for (int i = 0; i < 3; i++) att[i] *= r->col[i] * r->col[3] + mult;
         att[3] *= mult;
         if (c->sun.strict_direct_light &&
-            c->s->materials[r->prev_mat].ior != c->s->materials[r->cur_mat].ior)
+            c->s->materials[r->prev_mat].ior != c->s->materials[r->cur_mat].ior) {
+            if (att[3] > 0.0f) c->st.strict_cut++; /* the cut decided: light was still passing */
             att[3] = 0.0f;
+        }
     }
 }
 
@@ -1147,6 +1163,8 @@ static int diffuse_sun_sampling(ctx_t *c, ray_t *ray, ray_t *next, float cum[4],
     next->d = random_sun_direction(k, rng);
     int front_light = vdot(next->d, ray->n) > 0.0f;
     if (front_light || ((m->flags & MAT_FLAG_SUBSURFACE) && ref_rng_next(rng) < c->s->f_sub_surface)) {
+        if (front_light) c->st.shadow_cast_front++;
+        else c->st.shadow_cast_sss++;
         if (!front_light) next->o = vadd(next->o, vscale(ray->n, -RAY_OFFSET));
         next->cur_mat = next->prev_mat;
         float att[4];
@@ -1180,6 +1198,7 @@ static int do_diffuse_reflection(ctx_t *c, ray_t *ray, ray_t *next, float cum[4]
     /* emitter_sampling_strategy == NONE [C8]: (NONE || depth == 1) is always true */
     if (c->s->emitters_enabled && m->emittance > RAY_EPSILON) {
         for (int i = 0; i < 3; i++) emit[i] = ray->col[i] * ray->col[i] * m->emittance;
+        c->st.emission_added++;
         hit = 1;
     }
     if (c->sun.sun_sampling) return diffuse_sun_sampling(c, ray, next, cum, m, rng, fw, segs, emit, hit);
@@ -1214,7 +1233,8 @@ static int do_refraction(ctx_t *c, const ray_t *ray, ray_t *next, const ref_mate
     float cos_theta = -vdot(ray->d, ray->n);
     float radicand = 1.0f - n1n2 * n1n2 * (1.0f - cos_theta * cos_theta);
     if (refr && radicand < RAY_EPSILON) {
-        specular_reflection(ray, cur->roughness, rng, next);
+        c->st.tir++;
+        specular_reflection(c, ray, cur->roughness, rng, next);
         if (path_trace(c, next, 0, rng, fw, segs)) {
             hit = 1;
             for (int i = 0; i < 3; i++) cum[i] += next->col[i];
@@ -1228,7 +1248,8 @@ static int do_refraction(ctx_t *c, const ray_t *ray, ray_t *next, const ref_mate
     float c5 = ((cc * cc) * (cc * cc)) * cc; /* powi(5) [C11] */
     float rtheta = r0 + (1.0f - r0) * c5;
     if (ref_rng_next(rng) < rtheta) {
-        specular_reflection(ray, cur->roughness, rng, next);
+        c->st.fresnel_reflect++;
+        specular_reflection(c, ray, cur->roughness, rng, next);
         if (path_trace(c, next, 0, rng, fw, segs)) {
             hit = 1;
             for (int i = 0; i < 3; i++) cum[i] += next->col[i];
@@ -1236,6 +1257,8 @@ static int do_refraction(ctx_t *c, const ray_t *ray, ray_t *next, const ref_mate
         /* :395 re-traces the already-traced reflected ray; not replicated [C14] */
         return hit;
     }
+    if (refr) c->st.refract++;
+    else c->st.refract_straight++;
     if (refr) {
         float t2 = sqrtf(radicand);
         v3 n = ray->n, d;
@@ -1243,6 +1266,7 @@ static int do_refraction(ctx_t *c, const ray_t *ray, ray_t *next, const ref_mate
         else d = vsub(vscale(ray->d, n1n2), vscale(n, -n1n2 * cos_theta - t2));
         next->d = vnorm(d);
         if (signum_(vdot(next->n, next->d)) != signum_(vdot(next->n, ray->d))) {
+            c->st.signum_refract++;
             float factor = signum_(vdot(next->n, ray->d)) * -RAY_EPSILON - vdot(next->d, next->n);
             next->d = vnorm(vadd(next->d, vscale(next->n, factor)));
         }
@@ -1259,6 +1283,7 @@ static int do_refraction(ctx_t *c, const ray_t *ray, ray_t *next, const ref_mate
 static int do_transmission(ctx_t *c, const ray_t *ray, ray_t *next, float cum[4], float absorb, uint32_t *rng,
                            fwd_t *fw, uint32_t *segs) { /* :403-422 */
     int hit = 0;
+    c->st.transmission++;
     new_from_self(ray, next);
     next->o = ray_at(next, RAY_OFFSET);
     if (fw) for (int i = 0; i < 3; i++) fw->T[i] = fw->T[i] * (ray->col[i] * absorb);
@@ -1275,9 +1300,9 @@ static int path_trace(ctx_t *c, ray_t *ray, int first, uint32_t *rng, fwd_t *fw,
     for (;;) {
         if (c->path_segs >= MAX_PATH_SEGMENTS) break; /* [C15] */
         if (!next_intersection(c, ray, segs)) {
-            if (ray->depth == 0) get_sky_color_interp(&c->sun, ray);
-            else if (ray->specular) get_sky_color(&c->sun, ray, 1);
-            else get_sky_color_diffuse_sun(&c->sun, ray, c->sun.diffuse_sun);
+            if (ray->depth == 0) get_sky_color_interp(&c->sun, ray, &c->st);
+            else if (ray->specular) get_sky_color(&c->sun, ray, 1, &c->st);
+            else get_sky_color_diffuse_sun(&c->sun, ray, c->sun.diffuse_sun, &c->st);
             if (fw) for (int i = 0; i < 3; i++) fw->L[i] = fw->L[i] + fw->T[i] * ray->col[i];
             hit = 1;
             break;
@@ -1287,10 +1312,11 @@ static int path_trace(ctx_t *c, ray_t *ray, int first, uint32_t *rng, fwd_t *fw,
         float specular = cur->specular, diffuse = ray->col[3], absorb = ray->col[3];
         float ior1 = cur->ior, ior2 = prev->ior;
         if (ray->col[3] + specular < RAY_EPSILON && ior1 == ior2) { /* :52-54 [C4] */
+            c->st.c4_pass++;
             ray->o = ray_at(ray, RAY_OFFSET);
             continue;
         }
-        if (ray->depth + 1 >= c->max_depth) break; /* :56-58 */
+        if (ray->depth + 1 >= c->max_depth) { c->st.depth_cut++; break; } /* :56-58 */
         ray->depth += 1;
         c->st.shade_events++;
         float cum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1314,10 +1340,14 @@ static int path_trace(ctx_t *c, ray_t *ray, int first, uint32_t *rng, fwd_t *fw,
                 if (fw) *fw = fw0;
             }
             int do_metal = metal > RAY_EPSILON && ref_rng_next(rng) < metal;
-            if (do_metal || (specular > RAY_EPSILON && ref_rng_next(rng) < specular))
+            if (do_metal || (specular > RAY_EPSILON && ref_rng_next(rng) < specular)) {
+                if (do_metal) c->st.lobe_metal++;
+                else c->st.lobe_specular++;
                 hit |= do_specular_reflection(c, ray, &next, cum, do_metal, rng, fw, segs);
-            else if (ref_rng_next(rng) < diffuse)
+            } else if (ref_rng_next(rng) < diffuse) {
+                c->st.lobe_diffuse++;
                 hit |= do_diffuse_reflection(c, ray, &next, cum, cur, rng, fw, segs);
+            }
             else if (fabsf(ior1 - ior2) >= RAY_EPSILON)
                 hit |= do_refraction(c, ray, &next, cur, cum, ior1, ior2, absorb, rng, fw, segs);
             else
@@ -1367,7 +1397,7 @@ static void preview_pixel(ctx_t *c, ray_t *ray, uint32_t *segs, float col[3]) {
     }
     if (ray->cur_mat == 0) { /* get_sky_color_inner + add_sun_color */
         sky_set(ray);
-        add_sun_color(&c->sun, ray);
+        add_sun_color(&c->sun, ray, &c->st);
         for (int i = 0; i < 3; i++) col[i] = ray->col[i];
     } else {
         float shading = vdot(ray->n, c->sun.sw);
@@ -1476,6 +1506,9 @@ static void *render_worker(void *arg) {
     j->total.shade_events += c.st.shade_events;
     j->total.texel_reads += c.st.texel_reads;
     j->total.block_tests += c.st.block_tests;
+#define REF_STATS_SUM(n) j->total.n += c.st.n;
+    REF_SHADE_COUNTERS(REF_STATS_SUM)
+#undef REF_STATS_SUM
     if (c.st.max_path_segs > j->total.max_path_segs) j->total.max_path_segs = c.st.max_path_segs;
     pthread_mutex_unlock(&j->lock);
     return NULL;

@@ -134,6 +134,20 @@ typedef struct {
     uint64_t paths, segments, esvo_steps, node_fetches, prim_tests, leaf_visits, shade_events, texel_reads;
     uint64_t max_path_segs;
     uint64_t block_tests; /* block-value leaf tests [C23] */
+    /* shading branch counters (appended; tests/test_shading_cpu.py): one per arm of path_trace and its
+     * helpers.  They count, they never steer: radiance, segment counts and the totals above are the same
+     * with and without them.  The device keeps no such counters; the parity bar (equal per-pixel segment
+     * counts and work totals, radiance within tolerance) makes these the kernel's branch counts too. */
+#define REF_SHADE_COUNTERS(X) \
+    X(lobe_metal) X(lobe_specular) X(lobe_diffuse) X(emission_added) X(c4_pass) X(depth_cut) \
+    X(tir) X(fresnel_reflect) X(refract) X(refract_straight) X(transmission) \
+    X(reflect_rough) X(reflect_mirror) X(signum_specular) X(signum_diffuse) X(signum_refract) \
+    X(is_disc_sample) X(is_disc_reject) X(is_horizon_sample) X(is_horizon_reject) X(is_chance_clamp) \
+    X(shadow_cast_front) X(shadow_cast_sss) X(shadow_hit_alpha0) X(shadow_hit_partial) X(shadow_hit_opaque) \
+    X(strict_cut) X(sky_sun_textured) X(sky_sun_diffuse)
+#define REF_STATS_FIELD(n) uint64_t n;
+    REF_SHADE_COUNTERS(REF_STATS_FIELD)
+#undef REF_STATS_FIELD
 } ref_stats;
 
 /* --- math --- */

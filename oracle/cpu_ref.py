@@ -65,10 +65,19 @@ class RefParams(C.Structure):
                 ("row_end", C.c_uint32), ("preview", C.c_int32)]
 
 
+# the shading branch counters appended to ref_stats (REF_SHADE_COUNTERS in cpu_ref.h, the same order)
+SHADE_COUNTERS = ("lobe_metal", "lobe_specular", "lobe_diffuse", "emission_added", "c4_pass", "depth_cut", "tir",
+                  "fresnel_reflect", "refract", "refract_straight", "transmission", "reflect_rough", "reflect_mirror",
+                  "signum_specular", "signum_diffuse", "signum_refract", "is_disc_sample", "is_disc_reject",
+                  "is_horizon_sample", "is_horizon_reject", "is_chance_clamp", "shadow_cast_front", "shadow_cast_sss",
+                  "shadow_hit_alpha0", "shadow_hit_partial", "shadow_hit_opaque", "strict_cut", "sky_sun_textured",
+                  "sky_sun_diffuse")
+
+
 class RefStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("paths", "segments", "esvo_steps", "node_fetches", "prim_tests",
                                            "leaf_visits", "shade_events", "texel_reads", "max_path_segs",
-                                           "block_tests")]
+                                           "block_tests") + SHADE_COUNTERS]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
