@@ -42,6 +42,19 @@ constexpr uint32_t kMaxPool = 1u << 30;              // the sun-sampling planes 
 constexpr uint32_t kMinPool = 1u << 20;              // floor of the out-of-memory fallback (halving)
 constexpr uint32_t kDefaultRefill = 0;               // extend: idle lanes before a wave refills (0: adaptive)
 constexpr uint32_t kDefaultDrainRays = 4096;         // drain the chunk in one launch below this many queued rays
+#ifndef OCTPT_SAMPLE_GROUP_DEFAULT
+#define OCTPT_SAMPLE_GROUP_DEFAULT 4
+#endif
+// a pixel's samples per wave of the chunk's item order, at most (1, 4, 16 or 64; OCTPT_SAMPLE_GROUP)
+constexpr uint32_t kDefaultSampleGroup = OCTPT_SAMPLE_GROUP_DEFAULT;
+constexpr uint64_t kGroupMinItems = 1ull << 27;       // chunks below this many items keep G = 1 unless OCTPT_SAMPLE_GROUP is set
+
+// log2 of the largest G in {1, 4, 16, 64} that is at most `most` and divides the chunk's sample count
+uint32_t group_shift_of(uint32_t most, uint32_t chunk_spp) {
+    uint32_t g = 6u;
+    while (g && ((1u << g) > most || chunk_spp % (1u << g) != 0u)) g -= 2u;
+    return g;
+}
 
 uint32_t env_u32(const char *name, uint32_t dflt) {
     const char *v = std::getenv(name);
@@ -104,6 +117,8 @@ struct octpt_ctx {
     int shade_bpc_cache[2][2][3] = {};            // [sun sampling][LDS tables][shade_mode]
     bool lean_scene = false;  // no emitters, no sun sampling: the lean path state applies when the pool holds the chunk
     bool no_lean = false;     // OCTPT_LEAN=0: always the 40-B path state (A/B, tests)
+    bool sample_group_set = false;                // OCTPT_SAMPLE_GROUP given: no rule about where the order is grouped
+    uint32_t sample_group = kDefaultSampleGroup;  // OCTPT_SAMPLE_GROUP: the item order's G at most; 1 = one sample per wave
     // wavefront pool (grown on demand)
     WaveBuffers wb{};
     size_t pool = 0, color_cap = 0, nee_pool = 0;  // nee_pool: slots of the sun-sampling planes (wb.pd)
@@ -705,6 +720,7 @@ octpt_status make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender
     R.total_items = R.shard_tiles * 64u;
     R.div_tiles_x = udiv_magic(R.tiles_x);
     R.div_items = udiv_magic(R.total_items);
+    R.group_shift = 0u;  // the wavefront path sets it per chunk (enqueue_wavefront)
     R.dim = (float)std::max(p->width, p->height);
     R.jlo = -1.0f / R.dim;
     R.jhi = 1.0f / R.dim;
@@ -1077,6 +1093,16 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         Rc.spp_start = R.spp_start + c0;
         Rc.spp_count = c1 - c0;
         if (R.subs) Rc.subs = R.subs + c0;
+        // the item order's sample group (item_split): a power of four that divides the chunk's samples, so that every
+        // wave's G samples exist; a branch schedule keeps one sample per wave
+        // Without OCTPT_SAMPLE_GROUP the order is grouped only where it was measured to pay: scenes of
+        // spheres and cuboids alone, in chunks of at least kGroupMinItems items.  Elsewhere resolve's dearer read of
+        // the grouped colour records outweighs what extend gains (C2's 59 M-item frame -4.6 %, block-value C5b -1.2 %)
+        const bool grouped = ctx->sample_group_set ||
+                             (!ctx->S.has_blocks && !ctx->S.has_models && (uint64_t)Rc.spp_count * n_px >= kGroupMinItems);
+        Rc.group_shift = (R.subs || !grouped) ? 0u : group_shift_of(ctx->sample_group, Rc.spp_count);
+        if (std::getenv("OCTPT_DEBUG"))  // (tests/test_gpu_sample_group.py reads the G a chunk ran at from this line)
+            std::fprintf(stderr, "octpt: chunk of %u samples, sample group %u\n", Rc.spp_count, 1u << Rc.group_shift);
         Rc.beam = beam;
         const uint32_t chunk_items = (uint32_t)((uint64_t)Rc.spp_count * n_px);
         HIP_TRY(ctx, hipMemsetAsync(B.ctrl, 0, kCtrlWords * sizeof(uint32_t), s));
@@ -1540,6 +1566,9 @@ octpt_status octpt_create(int32_t device, octpt_ctx **out) {
     ctx->beam = !(beam_env && beam_env[0] == '0');
     const char *lean_env = std::getenv("OCTPT_LEAN");
     ctx->no_lean = lean_env && lean_env[0] == '0';
+    ctx->sample_group = std::min(env_u32("OCTPT_SAMPLE_GROUP", kDefaultSampleGroup), 64u);
+    const char *group_env = std::getenv("OCTPT_SAMPLE_GROUP");
+    ctx->sample_group_set = group_env && *group_env;  // set: that G at most in every chunk (A/B, tests)
     ctx->drain_models = env_u32("OCTPT_DRAIN_MODELS", 0u) != 0u;
     ctx->mem_limit = (size_t)env_u32("OCTPT_DEVICE_MEM_LIMIT", 0u) << 20;  // MiB, test hook (ensure_wave)
     if (hipSetDevice(device) != hipSuccess) return bail(OCTPT_ERR_DEVICE);

@@ -151,6 +151,8 @@ struct DevRender {
     uint64_t div_tiles_x, div_items;  // udiv_magic(tiles_x), udiv_magic(total_items)
     uint32_t shard_tiles;    // tiles owned by this shard
     uint32_t total_items;    // shard_tiles * 64 work items
+    uint32_t group_shift;    // log2 G, G = a pixel's samples in one wave of the chunk's item order (0, 2, 4 or 6;
+                             // item_split in octpt_kernels.hip); set per chunk, 0 everywhere else
     float dim;               // max(W, H)
     float jlo, jhi;          // -1 / dim, 1 / dim: the jitter range of render_tile_average (tile_renderer.rs:701-702),
                              // divided once on the host (IEEE division, the same bits as the device's)

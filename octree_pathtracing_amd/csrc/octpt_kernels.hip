@@ -1980,12 +1980,42 @@ __device__ __forceinline__ void load_path(const WaveBuffers &B, uint32_t slot, f
     unpack_path(B.pa[slot], B.pb[slot], B.pc[slot], r0, r1, ps, item);
 }
 
+// The chunk's item order.  With g = R.group_shift and G = 1 << g samples of a pixel per wave, the 64
+// items of wave v = (sample_group * shard_tiles + tile) * G + sub are lane = p * G + s_in_group: the G samples
+// sample_group * G + s_in_group of the 64 / G pixels p of block `sub` of the tile (4x4 pixels at G = 4, 2x2 at 16, one
+// pixel at 64; G = 1 is the whole 8x8 tile at one sample, item = s_local * total_items + px_item).  A pixel's place
+// in that order is its group key q = sub << (6 - g) | p, the pixel-in-tile index w = y * 8 + x with its two middle
+// bit fields swapped: w = [by py bx px] -> q = [by bx py px], block coordinates of g / 2 bits over pixel-in-block
+// coordinates of 3 - g / 2.  With pq = tile * 64 + q
+//     item = ((sample_group * total_items + pq) << g) + s_in_group
+// group_swap swaps the two fields of the three middle bits, which start at bit pos = 3 - g / 2 either way; low is the
+// width of the lower one: 3 - g / 2 for q -> w, g / 2 for w -> q.
+__device__ __forceinline__ uint32_t group_swap(uint32_t v, uint32_t pos, uint32_t low) {
+    const uint32_t mid = (v >> pos) & 7u;
+    return (v & ~(7u << pos)) | ((((mid & ((1u << low) - 1u)) << (3u - low)) | (mid >> low)) << pos);
+}
+// item -> (s_local, px_item); px_item is item_pixel's tile-major pixel index
+template <bool kFastDiv = true>
+__device__ __forceinline__ void item_split(const DevRender &R, uint32_t item, uint32_t &s_local, uint32_t &px_item) {
+    const uint32_t g = R.group_shift;
+    const uint32_t n = item >> g;
+    const uint32_t sg = kFastDiv ? udiv_c(n, R.div_items) : n / R.total_items;
+    const uint32_t pq = n - sg * R.total_items;
+    s_local = (sg << g) | (item & ((1u << g) - 1u));
+    px_item = g ? group_swap(pq, 3u - (g >> 1), 3u - (g >> 1)) : pq;
+}
+// the colour record of sample s_local of the pixel whose tile and group key are pq (item_split's inverse)
+__device__ __forceinline__ size_t item_of(const DevRender &R, uint32_t s_local, uint32_t pq) {
+    const uint32_t g = R.group_shift;
+    return (((size_t)(s_local >> g) * R.total_items + pq) << g) + (s_local & ((1u << g) - 1u));
+}
+
 // the path of chunk item `item`, its first segment begun; false when the pixel lies outside the image
 template <bool kFastDiv = true>
 __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R, uint32_t item, PathState &ps,
                                           uint32_t &x, uint32_t &y) {
-    const uint32_t s_local = kFastDiv ? udiv_c(item, R.div_items) : item / R.total_items;
-    const uint32_t px_item = item - s_local * R.total_items;
+    uint32_t s_local, px_item;
+    item_split<kFastDiv>(R, item, s_local, px_item);
     item_pixel<kFastDiv>(R, px_item, x, y);
     if (x >= R.W || y >= R.H) return false;
     uint32_t sample = R.spp_start + s_local, branch = 0u;
@@ -2593,8 +2623,11 @@ __device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuff
     uint32_t segs = 0u;
     v3 L0 = V(0.0f, 0.0f, 0.0f), sum = L0;
     bool split = false;
+    // the pixel's place in the chunk's item order (item_split): its samples lie in runs of G consecutive records
+    const uint32_t gh = R.group_shift >> 1;
+    const uint32_t pq = gh ? group_swap(px_item, 3u - gh, gh) : px_item;
     for (uint32_t s = 0; s < chunk_spp; ++s) {
-        const float4 c = B.color[(size_t)s * R.total_items + px_item];
+        const float4 c = B.color[item_of(R, s, pq)];
         const uint32_t w = __float_as_uint(c.w);
         segs += w & 0x7FFFFFFFu;
         if (!R.subs) {
