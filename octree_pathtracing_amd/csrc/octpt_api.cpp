@@ -43,7 +43,7 @@ constexpr uint32_t kMinPool = 1u << 20;              // floor of the out-of-memo
 constexpr uint32_t kDefaultRefill = 0;               // extend: idle lanes before a wave refills (0: adaptive)
 constexpr uint32_t kDefaultDrainRays = 4096;         // drain the chunk in one launch below this many queued rays
 #ifndef OCTPT_SAMPLE_GROUP_DEFAULT
-#define OCTPT_SAMPLE_GROUP_DEFAULT 4
+#define OCTPT_SAMPLE_GROUP_DEFAULT 64  // best on C3 once resolve reads a grouped chunk's records once
 #endif
 // a pixel's samples per wave of the chunk's item order, at most (1, 4, 16 or 64; OCTPT_SAMPLE_GROUP)
 constexpr uint32_t kDefaultSampleGroup = OCTPT_SAMPLE_GROUP_DEFAULT;
@@ -1096,8 +1096,9 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         // the item order's sample group (item_split): a power of four that divides the chunk's samples, so that every
         // wave's G samples exist; a branch schedule keeps one sample per wave
         // Without OCTPT_SAMPLE_GROUP the order is grouped only where it was measured to pay: scenes of
-        // spheres and cuboids alone, in chunks of at least kGroupMinItems items.  Elsewhere resolve's dearer read of
-        // the grouped colour records outweighs what extend gains (C2's 59 M-item frame -4.6 %, block-value C5b -1.2 %)
+        // spheres and cuboids alone, in chunks of at least kGroupMinItems items.  Elsewhere the grouped order loses at
+        // every G although resolve now reads its records once (resolve_pixel_wide): at G = 4 / 16 / 64 C2's 59 M-item
+        // frame -2.6 / -27 / -77 %, block-value C5b -0.5 / -4 / -38 %, block-model C5 -1.8 / -7 / -33 %
         const bool grouped = ctx->sample_group_set ||
                              (!ctx->S.has_blocks && !ctx->S.has_models && (uint64_t)Rc.spp_count * n_px >= kGroupMinItems);
         Rc.group_shift = (R.subs || !grouped) ? 0u : group_shift_of(ctx->sample_group, Rc.spp_count);

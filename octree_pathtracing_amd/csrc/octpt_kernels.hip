@@ -18,6 +18,7 @@
 #include "octpt_internal.h"
 #include "octpt_rcp.h"
 #include "octpt_reproject.h"
+#include "octpt_resolve_map.h"
 
 #ifndef OCTPT_RCP_FAST
 #define OCTPT_RCP_FAST 1  // esvo_begin's t_coef by rcp_rn (A/B: -DOCTPT_RCP_FAST=0, the division: extend +0.2..0.6 %)
@@ -1988,12 +1989,8 @@ __device__ __forceinline__ void load_path(const WaveBuffers &B, uint32_t slot, f
 // bit fields swapped: w = [by py bx px] -> q = [by bx py px], block coordinates of g / 2 bits over pixel-in-block
 // coordinates of 3 - g / 2.  With pq = tile * 64 + q
 //     item = ((sample_group * total_items + pq) << g) + s_in_group
-// group_swap swaps the two fields of the three middle bits, which start at bit pos = 3 - g / 2 either way; low is the
-// width of the lower one: 3 - g / 2 for q -> w, g / 2 for w -> q.
-__device__ __forceinline__ uint32_t group_swap(uint32_t v, uint32_t pos, uint32_t low) {
-    const uint32_t mid = (v >> pos) & 7u;
-    return (v & ~(7u << pos)) | ((((mid & ((1u << low) - 1u)) << (3u - low)) | (mid >> low)) << pos);
-}
+// group_swap (octpt_resolve_map.h) swaps the two fields of the three middle bits, which start at bit pos = 3 - g / 2
+// either way; low is the width of the lower one: 3 - g / 2 for q -> w, g / 2 for w -> q.
 // item -> (s_local, px_item); px_item is item_pixel's tile-major pixel index
 template <bool kFastDiv = true>
 __device__ __forceinline__ void item_split(const DevRender &R, uint32_t item, uint32_t &s_local, uint32_t &px_item) {
@@ -2659,6 +2656,91 @@ __device__ __forceinline__ void resolve_pixel(const DevRender &R, const WaveBuff
     accum[acc_idx] = fb;
     if constexpr (kMoments) moments[acc_idx] = mo;
     if (segcount) segcount[acc_idx] += segs;
+}
+
+// resolve_pixel for a grouped chunk (R.group_shift != 0, hence no branch schedule): the same fold, the records read a
+// wave at a time.  The wave's 64 pixels are one tile, whose records of one sample group are one contiguous span of
+// 64 * G records; the wave loads it in batches of K samples per pixel with whole-line loads, stages a batch in its own
+// LDS region and hands each lane its pixel's K samples in sample order (the mapping: octpt_resolve_map.h).  Every lane
+// of a wave that has items loads and stages, its pixel in the image or not (the records of pixels outside it are never
+// written and never folded); a wave past total_items (a multiple of 64) has nothing to read and leaves whole.  The
+// regions are per wave, so a workgroup-scope fence around a wave barrier orders a batch's staging writes, its reads
+// and the next batch's writes; there is no block barrier for the waves that left to miss.
+template <bool kMoments, bool kClamp, uint32_t K>
+__device__ __forceinline__ void resolve_pixel_wide(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp,
+                                                   float4 *__restrict__ accum, uint32_t *__restrict__ segcount,
+                                                   float2 *__restrict__ moments, float clamp, float4 *stage) {
+    const uint32_t px_item = blockIdx.x * kBlock + threadIdx.x;
+    if (px_item >= R.total_items) return;  // whole waves
+    const uint32_t lane = threadIdx.x & 63u;
+    float4 *st = stage + (threadIdx.x >> 6) * resolve_wave_slots(K);
+    uint32_t x, y;
+    item_pixel(R, px_item, x, y);
+    const bool live = x < R.W && y < R.H;
+    const uint32_t acc_idx = R.compact ? px_item : y * R.W + x;
+    float4 fb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float2 mo = make_float2(0.0f, 0.0f);
+    if (live) {
+        fb = accum[acc_idx];
+        if constexpr (kMoments) mo = moments[acc_idx];
+    }
+    uint32_t segs = 0u;
+    const uint32_t g = R.group_shift, gh = g >> 1;
+    const uint32_t q = group_swap(px_item, 3u - gh, gh) & 63u;  // the pixel's group key in its tile
+    uint32_t src[K], dst[K];
+#pragma unroll
+    for (uint32_t i = 0; i < K; ++i) {
+        src[i] = resolve_load_record(i, lane, K, g);
+        dst[i] = resolve_load_slot(i, lane, K);
+    }
+    const uint32_t n_groups = chunk_spp >> g;
+    for (uint32_t sg = 0; sg < n_groups; ++sg) {
+        // the tile's records of this sample group (item_of with the group key 0 and sample 0 of the group)
+        const float4 *span = B.color + (((size_t)sg * R.total_items + (px_item & ~63u)) << g);
+        for (uint32_t j0 = 0; j0 < (1u << g); j0 += K) {
+            float4 c[K];
+#pragma unroll
+            for (uint32_t i = 0; i < K; ++i) c[i] = span[src[i] + j0];
+#pragma unroll
+            for (uint32_t i = 0; i < K; ++i) st[dst[i]] = c[i];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+            for (uint32_t k = 0; k < K; ++k) c[k] = st[resolve_read_slot(q, k, K)];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (!live) continue;
+#pragma unroll
+            for (uint32_t k = 0; k < K; ++k) {
+                const uint32_t s = (sg << g) + j0 + k;
+                segs += __float_as_uint(c[k].w) & 0x7FFFFFFFu;
+                v3 cs = V(c[k].x, c[k].y, c[k].z);
+                if constexpr (kClamp) cs = clamp_sample(cs, clamp);
+                running_mean(fb, cs, R.spp_start + s, 1u);
+                if constexpr (kMoments) running_moments(mo, cs, R.spp_start + s, 1u);
+            }
+        }
+    }
+    if (!live) return;
+    accum[acc_idx] = fb;
+    if constexpr (kMoments) moments[acc_idx] = mo;
+    if (segcount) segcount[acc_idx] += segs;
+}
+
+// the grouped chunks' resolve: the four instances of resolve_pixel_wide (launch_wf_resolve); a chunk of G = 4 takes
+// its whole runs (K = 4), the larger groups kResolveBatch samples at a time
+template <bool kMoments, bool kClamp>
+__global__ __launch_bounds__(kBlock) void wf_resolve_wide_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
+                                                                 float4 *__restrict__ accum,
+                                                                 uint32_t *__restrict__ segcount,
+                                                                 float2 *__restrict__ moments, float clamp) {
+    __shared__ float4 stage[(kBlock / 64u) * resolve_wave_slots(kResolveBatch)];
+    if (R.group_shift == 2u)
+        resolve_pixel_wide<kMoments, kClamp, 4u>(R, B, chunk_spp, accum, segcount, moments, clamp, stage);
+    else
+        resolve_pixel_wide<kMoments, kClamp, kResolveBatch>(R, B, chunk_spp, accum, segcount, moments, clamp, stage);
 }
 
 __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(DevRender R, WaveBuffers B, uint32_t chunk_spp,
@@ -3723,6 +3805,22 @@ hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_o
 hipError_t launch_wf_resolve(const DevRender &R, const WaveBuffers &B, uint32_t chunk_spp, float4 *accum,
                              uint32_t *segcount, float2 *moments, float clamp, hipStream_t stream) {
     const dim3 grid((R.total_items + kBlock - 1u) / kBlock);
+    if (R.group_shift != 0u) {  // a grouped chunk: the instances that read the records a wave at a time
+        if (clamp != 0.0f) {
+            if (moments)
+                hipLaunchKernelGGL((wf_resolve_wide_kernel<true, true>), grid, dim3(kBlock), 0, stream, R, B, chunk_spp,
+                                   accum, segcount, moments, clamp);
+            else
+                hipLaunchKernelGGL((wf_resolve_wide_kernel<false, true>), grid, dim3(kBlock), 0, stream, R, B, chunk_spp,
+                                   accum, segcount, moments, clamp);
+        } else if (moments)
+            hipLaunchKernelGGL((wf_resolve_wide_kernel<true, false>), grid, dim3(kBlock), 0, stream, R, B, chunk_spp,
+                               accum, segcount, moments, clamp);
+        else
+            hipLaunchKernelGGL((wf_resolve_wide_kernel<false, false>), grid, dim3(kBlock), 0, stream, R, B, chunk_spp,
+                               accum, segcount, moments, clamp);
+        return hipGetLastError();
+    }
     if (clamp != 0.0f) {  // C33: the clamp instances; off, the two kernels as they always were
         if (moments)
             hipLaunchKernelGGL(wf_resolve_moments_clamp_kernel, grid, dim3(kBlock), 0, stream, R, B, chunk_spp, accum,

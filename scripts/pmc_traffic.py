@@ -16,7 +16,7 @@ import json
 import re
 import sys
 
-KERNELS = ("wf_extend_kernel", "wf_shade_kernel", "wf_seed_kernel", "wf_resolve_kernel")
+KERNELS = ("wf_extend_kernel", "wf_shade_kernel", "wf_seed_kernel", "wf_resolve_kernel", "wf_resolve_wide_kernel")
 
 
 def per_kernel(d, counter):

@@ -13,7 +13,7 @@ from collections import defaultdict
 
 def kind_of(name: str) -> str:
     for k in ("beam_kernel", "wf_seed_kernel", "wf_extend_kernel", "wf_issued_extend_kernel", "wf_shade_kernel",
-              "wf_drain_kernel", "wf_resolve_kernel", "multi_stage_kernel", "unshard_kernel", "tonemap_kernel"):
+              "wf_drain_kernel", "wf_resolve_kernel", "wf_resolve_wide_kernel", "multi_stage_kernel", "unshard_kernel", "tonemap_kernel"):
         if k in name:
             return k
     return re.sub(r"\(.*", "", name)[-40:]
