@@ -48,6 +48,16 @@ constexpr uint32_t kDefaultDrainRays = 4096;         // drain the chunk in one l
 // a pixel's samples per wave of the chunk's item order, at most (1, 4, 16 or 64; OCTPT_SAMPLE_GROUP)
 constexpr uint32_t kDefaultSampleGroup = OCTPT_SAMPLE_GROUP_DEFAULT;
 constexpr uint64_t kGroupMinItems = 1ull << 27;       // chunks below this many items keep G = 1 unless OCTPT_SAMPLE_GROUP is set
+// extend's refill threshold in the first launch of a grouped chunk whose queue holds the seed's camera records
+// (OCTPT_REFILL_FIRST), per extend instance; 0: the adaptive rule, as in every other launch
+#ifndef OCTPT_REFILL_FIRST_SPHERES
+#define OCTPT_REFILL_FIRST_SPHERES 64  // C3 -6.6 % of its step; 32 / 60 give -1.3 %, 48 / 56 under 1 %
+#endif
+#ifndef OCTPT_REFILL_FIRST_BOXES
+#define OCTPT_REFILL_FIRST_BOXES 64  // C4 -5.6 %; 60 gives -1.3 %, 48 -0.9 %
+#endif
+constexpr uint32_t kRefillFirstSpheres = OCTPT_REFILL_FIRST_SPHERES;
+constexpr uint32_t kRefillFirstBoxes = OCTPT_REFILL_FIRST_BOXES;  // scenes with cuboids, without blocks or models
 
 // log2 of the largest G in {1, 4, 16, 64} that is at most `most` and divides the chunk's sample count
 uint32_t group_shift_of(uint32_t most, uint32_t chunk_spp) {
@@ -136,6 +146,7 @@ struct octpt_ctx {
     uint32_t *d_count = nullptr;  // its device address (wf_snapshot_kernel)
     hipEvent_t count_ev[kLookahead + 1] = {};
     uint32_t pool_cap = kDefaultPool, refill = kDefaultRefill;
+    int32_t refill_first = -1;  // OCTPT_REFILL_FIRST (0..64); -1: unset, the extend instance's compiled default
     bool beam = true;  // camera rays start at their tile's beam (OCTPT_BEAM=0: off)
     uint32_t drain_rays = kDefaultDrainRays;  // queue length at which the drain takes over (OCTPT_DRAIN_RAYS, 0 = off)
     bool drain_models = false;                // the drain in block-model scenes too (OCTPT_DRAIN_MODELS=1, A/B)
@@ -1102,8 +1113,6 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         const bool grouped = ctx->sample_group_set ||
                              (!ctx->S.has_blocks && !ctx->S.has_models && (uint64_t)Rc.spp_count * n_px >= kGroupMinItems);
         Rc.group_shift = (R.subs || !grouped) ? 0u : group_shift_of(ctx->sample_group, Rc.spp_count);
-        if (std::getenv("OCTPT_DEBUG"))  // (tests/test_gpu_sample_group.py reads the G a chunk ran at from this line)
-            std::fprintf(stderr, "octpt: chunk of %u samples, sample group %u\n", Rc.spp_count, 1u << Rc.group_shift);
         Rc.beam = beam;
         const uint32_t chunk_items = (uint32_t)((uint64_t)Rc.spp_count * n_px);
         HIP_TRY(ctx, hipMemsetAsync(B.ctrl, 0, kCtrlWords * sizeof(uint32_t), s));
@@ -1116,13 +1125,27 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         // the seed writes its camera rays as 16-B records (store_cam_ray) when every item has its pixel: the first
         // extend (cam) and shade (first = 2) decode them
         const bool cam_rec = !regen &&((Rc.W | Rc.H) & (kTile - 1u)) == 0u;
+        // the first extend of a grouped chunk over camera records refills by a threshold of its own (OCTPT_REFILL_FIRST,
+        // else the instance's default; 0 and every other launch: ctx->refill, the adaptive rule unless OCTPT_REFILL
+        // is set).  The seed left each wave's 64 positions one pixel's samples (G = 64), which walk in step: a wave
+        // that waits for (nearly) all of them keeps its lanes in one iteration kind, where the adaptive rule's 16
+        // mixes the next pixel's rays in within one ray length
+        uint32_t refill_first = 0u;
+        if (Rc.group_shift != 0u && cam_rec)
+            refill_first = ctx->refill_first >= 0 ? (uint32_t)ctx->refill_first
+                           : (ctx->S.has_blocks || ctx->S.has_models) ? 0u
+                           : ctx->S.has_cuboids ? kRefillFirstBoxes : kRefillFirstSpheres;
+        if (std::getenv("OCTPT_DEBUG"))  // (tests/test_gpu_sample_group.py and test_gpu_group_refill.py read this line)
+            std::fprintf(stderr, "octpt: chunk of %u samples, sample group %u, first-launch refill %u\n", Rc.spp_count,
+                         1u << Rc.group_shift, refill_first);
         HIP_TRY(ctx, launch_wf_seed(ctx->C, Rc, B, n_seed, chunk_items, ctx->d_stats, s));
         for (uint32_t it = 0;; ++it) {
             if (cancel && cancel->load()) return fail(ctx, OCTPT_CANCELLED, "render cancelled");
             const uint32_t q = it & 1u;
             EventPair ev{};
             if ((st = ktimer_begin(ctx, s, ev)) != OCTPT_OK) return st;
-            HIP_TRY(ctx, launch_wf_extend(ctx->S, B, q, it == 0u && cam_rec, ctx->refill, grid_extend,
+            HIP_TRY(ctx, launch_wf_extend(ctx->S, B, q, it == 0u && cam_rec,
+                                          it == 0u && refill_first ? refill_first : ctx->refill, grid_extend,
                                           ctx->d_stats, s));
             if ((st = ktimer_end(ctx, s, 0, ev)) != OCTPT_OK) return st;
             if ((st = ktimer_begin(ctx, s, ev)) != OCTPT_OK) return st;
@@ -1570,6 +1593,9 @@ octpt_status octpt_create(int32_t device, octpt_ctx **out) {
     ctx->sample_group = std::min(env_u32("OCTPT_SAMPLE_GROUP", kDefaultSampleGroup), 64u);
     const char *group_env = std::getenv("OCTPT_SAMPLE_GROUP");
     ctx->sample_group_set = group_env && *group_env;  // set: that G at most in every chunk (A/B, tests)
+    // OCTPT_REFILL_FIRST=n: the first-launch threshold of a grouped chunk (clamped to 64); 0: the adaptive rule
+    const char *first_env = std::getenv("OCTPT_REFILL_FIRST");
+    if (first_env && *first_env) ctx->refill_first = (int32_t)std::min<unsigned long>(std::strtoul(first_env, nullptr, 10), 64ul);
     ctx->drain_models = env_u32("OCTPT_DRAIN_MODELS", 0u) != 0u;
     ctx->mem_limit = (size_t)env_u32("OCTPT_DEVICE_MEM_LIMIT", 0u) << 20;  // MiB, test hook (ensure_wave)
     if (hipSetDevice(device) != hipSuccess) return bail(OCTPT_ERR_DEVICE);
