@@ -197,7 +197,14 @@ typedef struct octpt_camera {
     float direction[3];
     float up[3];
     float fov; /* radians */
-    float aperture, focal_distance; /* must be 0: thin lens is unused by the reference path */
+    /* The thin lens (Camera::focus, camera.rs:68-73): aperture is the lens radius in world units,
+     * >= 0 and finite, 0 = pinhole; focal_distance is the distance along `direction` of the plane in focus, > 0
+     * and finite whenever aperture > 0 and not read at all when aperture is 0.  Path-traced renders start each
+     * path on a point of the lens drawn from a stream of its own, so the path's other draws are what they are
+     * without a lens.  OCTPT_RENDER_PREVIEW and the guide buffers (octpt_render_aov*) keep tracing the ray through
+     * the lens centre, bit for bit unchanged by the aperture (sharp guides for the filters).  octpt_temporal* and
+     * octpt_reproject_coords refuse a camera with an aperture (UNSUPPORTED): pass them the camera with aperture 0. */
+    float aperture, focal_distance;
 } octpt_camera;
 
 /* One progressive render call = spp_count passes of TileRenderer::render_tile_average
@@ -292,7 +299,9 @@ octpt_status octpt_scene_upload(octpt_ctx *ctx, const octpt_scene_desc *scene);
  * the one octpt_scene_upload makes from octpt_build_octree_ex's octree, with no round trip through
  * host memory. */
 octpt_status octpt_scene_build_device(octpt_ctx *ctx, const octpt_scene_desc *scene, uint32_t flags);
-/* set_camera / get_camera (renderer_trait.rs:20-21) */
+/* set_camera / get_camera (renderer_trait.rs:20-21).  INVALID_ARG, the camera staying as it was: fov outside
+ * (0, pi), an aperture that is negative or not finite, aperture > 0 with a focal_distance that is not finite
+ * and > 0.  With an aperture the camera rays' beam starts are not used (they assume rays from the eye). */
 octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *camera);
 octpt_status octpt_get_camera(const octpt_ctx *ctx, octpt_camera *camera);
 
@@ -378,6 +387,13 @@ octpt_status octpt_reset_stats(octpt_ctx *ctx);
  * ray from here is bit-identical to the ray the device traces for that pixel: what a host needs to turn a
  * mouse click into an octpt_intersect ray.  Host-only, no context. */
 octpt_status octpt_camera_rays(const octpt_camera *camera, uint32_t width, uint32_t height, float *rays);
+/* The first ray of a path-traced sample: rays[6 * (y * width + x)] = (origin xyz, unit direction
+ * xyz) of the ray that a render of this size and seed traces for sample `sample` (spp_start + the sample's index in
+ * the call) of pixel (x, y) -- jittered, and with an aperture leaving its point of the lens -- bit for bit: the
+ * kernels and this entry compile one text (csrc/octpt_lens.h).  octpt_camera_rays' argument rules and
+ * octpt_set_camera's for aperture and focal_distance; a failed call writes nothing.  Host-only, no context. */
+octpt_status octpt_lens_rays(const octpt_camera *camera, uint32_t width, uint32_t height, uint32_t seed,
+                             uint32_t sample, float *rays);
 
 /* First-hit guide buffers (AOVs) of the preview's camera ray (C24): one un-jittered ray per pixel, continued
  * through material-0 and alpha-0 hits exactly as RendererMode::Preview continues it (preview_render,

@@ -328,6 +328,7 @@ SIGNATURES = {
     "octpt_intersect": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "octpt_traversal_data": (_i32, [_vp, _u32, _u32, _u32, _vp, _f, _vp, _vp, _vp, _vp]),
     "octpt_camera_rays": (_i32, [C.POINTER(Camera), _u32, _u32, _vp]),
+    "octpt_lens_rays": (_i32, [C.POINTER(Camera), _u32, _u32, _u32, _u32, _vp]),
     "octpt_render_aov": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers)]),
     "octpt_render_aov_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers), _vp]),
     "octpt_denoise_device": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp, _vp]),

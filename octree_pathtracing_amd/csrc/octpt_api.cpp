@@ -22,6 +22,7 @@
 
 #include "../../include/octpt.h"
 #include "octpt_internal.h"
+#include "octpt_lens.h"
 #include "octpt_mask.h"
 #include "octpt_reproject.h"
 
@@ -1043,8 +1044,11 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     const WaveBuffers &B = ctx->wb;
     // the camera rays' beam starts, once per render call: every chunk's camera rays
     // share them (OCTPT_BEAM=0 switches them off; results are identical, ESVO iterations fewer)
+    // A camera with an aperture (C37) renders without them: behind the focal plane a lens ray leaves the tile's
+    // pyramid from the eye without bound, so the table is not conservative for it
+    const bool lens = ctx->C.aperture > 0.0f;
     const float *beam = nullptr;
-    if (ctx->beam) {
+    if (ctx->beam && !lens) {
         const size_t n_tiles = (size_t)R.beam_tx * ((R.H + kBeamTile - 1) / kBeamTile);
         octpt_ctx::BeamKey key;
         key.scene = ctx->scene_gen;
@@ -1120,11 +1124,13 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         const bool regen = n_seed < chunk_items;  // else the seed claimed every item of the chunk
         // the lean 24-B path state: L stays 0 until the path ends, item = slot
         // (and no branch schedule: the lean shade instances carry no first-reflection split)
-        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs) ? 1u : 0u;
+        // (nor a lens: its shade instances are the general ones' twins, C37)
+        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs && !lens) ? 1u : 0u;
         const int grid_shade = grid_shade_of(shade_mode(regen, ctx->wb.lean != 0u));
         // the seed writes its camera rays as 16-B records (store_cam_ray) when every item has its pixel: the first
         // extend (cam) and shade (first = 2) decode them
-        const bool cam_rec = !regen &&((Rc.W | Rc.H) & (kTile - 1u)) == 0u;
+        // (lens rays have origins of their own: the lens seed writes full records, first = 1)
+        const bool cam_rec = !regen && !lens && ((Rc.W | Rc.H) & (kTile - 1u)) == 0u;
         // the first extend of a grouped chunk over camera records refills by a threshold of its own (OCTPT_REFILL_FIRST,
         // else the instance's default; 0 and every other launch: ctx->refill, the adaptive rule unless OCTPT_REFILL
         // is set).  The seed left each wave's 64 positions one pixel's samples (G = 64), which walk in step: a wave
@@ -1848,7 +1854,9 @@ octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     if (!c) return fail(ctx, OCTPT_ERR_INVALID_ARG, "camera NULL");
     if (!(c->fov > 0.0f && c->fov < 3.14159265f)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "fov must be in (0, pi)");
-    if (c->aperture != 0.0f) return fail(ctx, OCTPT_ERR_UNSUPPORTED, "thin-lens aperture is not used by the reference path");
+    if (!lens_fields_valid(c->aperture, c->focal_distance))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "aperture must be finite and >= 0, and focal_distance finite and > 0 when aperture > 0");
     ctx->cam = *c;
     DevCamera C{};
     std::memcpy(C.eye, c->eye, 12);
@@ -1856,6 +1864,9 @@ octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
     std::memcpy(C.up, c->up, 12);
     cross3(c->direction, c->up, C.right);            // camera.rs:80
     C.d_factor = 1.0f / tanf(c->fov / 2.0f);         // camera.rs:79
+    // the thin lens (C37): focal_distance is read with an aperture alone, and divided here once
+    C.aperture = c->aperture;
+    C.focal_scale = c->aperture > 0.0f ? c->focal_distance / C.d_factor : 0.0f;
     ctx->C = C;
     ctx->has_camera = true;
     ++ctx->camera_gen;

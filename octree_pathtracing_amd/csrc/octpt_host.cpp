@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "../../include/octpt.h"
+#include "octpt_lens.h"
 #include "octpt_mask.h"
 #include "octpt_reproject.h"
 
@@ -163,6 +164,39 @@ extern "C" octpt_status octpt_camera_rays(const octpt_camera *camera, uint32_t w
             o[5] = nd[2] * r;
         }
     }
+    return OCTPT_OK;
+}
+
+// The first ray of sample `sample` of every pixel as a render of this size and seed forms it:
+// csrc/octpt_lens.h's lens_ray, the text new_path compiles, over the whole frame; the direction guard of
+// begin_segment after it, as every traced ray passes it.  Every check comes before the first write.
+extern "C" octpt_status octpt_lens_rays(const octpt_camera *camera, uint32_t width, uint32_t height, uint32_t seed,
+                                        uint32_t sample, float *rays) {
+    if (!camera || !rays || width == 0u || height == 0u) return OCTPT_ERR_INVALID_ARG;
+    if ((uint64_t)width * height >= (1ull << 31)) return OCTPT_ERR_INVALID_ARG;
+    if (!(camera->fov > 0.0f && camera->fov < 3.14159265f)) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::lens_fields_valid(camera->aperture, camera->focal_distance)) return OCTPT_ERR_INVALID_ARG;
+    const octpt::LensCamera L = octpt::lens_camera(camera->eye, camera->direction, camera->up, camera->fov,
+                                                   camera->aperture, camera->focal_distance);
+    octpt::LensFrame F;
+    F.W = width;
+    F.H = height;
+    F.seed = seed;
+    F.dim = (float)(width > height ? width : height);  // make_render's dim, jlo and jhi
+    F.jlo = -1.0f / F.dim;
+    F.jhi = 1.0f / F.dim;
+    const bool lens = L.aperture > 0.0f;
+    for (uint32_t y = 0; y < height; ++y)
+        for (uint32_t x = 0; x < width; ++x) {
+            float *o = rays + 6u * ((size_t)y * width + x), *d = o + 3;
+            if (lens) (void)octpt::lens_ray<true>(L, F, x, y, sample, o, d);
+            else (void)octpt::lens_ray<false>(L, F, x, y, sample, o, d);
+            if ((d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) || std::isnan(d[0]) || std::isnan(d[1]) || std::isnan(d[2])) {
+                d[0] = 0.0f;  // Scene::hit's direction guard (scene/mod.rs:175-179)
+                d[1] = 1.0f;
+                d[2] = 0.0f;
+            }
+        }
     return OCTPT_OK;
 }
 

@@ -124,6 +124,9 @@ struct DevScene {
 struct DevCamera {
     float eye[3], dir[3], right[3], up[3];
     float d_factor;  // 1 / tan(fov / 2)  (camera.rs:79)
+    // the thin lens, read by the lens instances of seed, shade and the megakernel alone
+    float aperture;     // lens radius, 0 = pinhole
+    float focal_scale;  // focal_distance / d_factor, divided once on the host (0 with aperture 0)
 };
 
 // n / d for a divisor d fixed per launch (Lemire, Kaser & Kurz 2019, "Faster remainder by direct computation"):
@@ -343,6 +346,11 @@ hipError_t launch_preview(const DevScene &S, const DevCamera &C, const DevRender
 hipError_t launch_render(const DevScene &S, const DevCamera &C, const DevRender &R, float4 *accum,
                          uint32_t *segcount, uint32_t *counter, unsigned long long *stats, int grid,
                          hipStream_t stream);
+// the lens instances (C37; octpt_kernels_lens.hip, a module of its own), which the launchers here take for a camera
+// with an aperture: the megakernel's, the seed's and the general shade's (mode: shade_mode, 0 or 1)
+const void *lens_render_kernel(bool nee, bool blocks);
+const void *lens_seed_kernel();
+const void *lens_shade_kernel(bool nee, bool lds, int mode);
 hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t n_seed,
                           uint32_t chunk_items, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q, bool cam, uint32_t refill, int grid,

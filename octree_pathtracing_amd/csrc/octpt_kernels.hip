@@ -16,6 +16,7 @@
 // (forward throughput instead of the reference's recursion), which the oracle also
 // implements as `forward_accumulation`.
 #include "octpt_internal.h"
+#include "octpt_lens.h"
 #include "octpt_rcp.h"
 #include "octpt_reproject.h"
 #include "octpt_resolve_map.h"
@@ -87,21 +88,7 @@ __device__ __forceinline__ float signum_(float f) { return (__float_as_uint(f) >
 // ---------------------------------------------------------------------------
 // portable f32 math -- identical constants and order to the oracle
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void dm_sincos(float x, float &s, float &c) {
-    const float kf = floorf(x * 0.636619772367581343f + 0.5f);
-    const int k = (int)kf;
-    const float r = ((x - kf * 1.5703125f) - kf * 4.837512969970703125e-4f) - kf * 7.54978995489188216e-8f;
-    const float z = r * r;
-    const float sp = r + r * z * (-1.6666654611e-1f + z * (8.3321608736e-3f + z * -1.9515295891e-4f));
-    const float cp = (1.0f - 0.5f * z) +
-                     z * z * (4.166664568298827e-2f + z * (-1.388731625493765e-3f + z * 2.443315711809948e-5f));
-    switch (k & 3) {
-    case 0: s = sp; c = cp; break;
-    case 1: s = cp; c = -sp; break;
-    case 2: s = -sp; c = -cp; break;
-    default: s = -cp; c = sp; break;
-    }
-}
+// (dm_sincos: csrc/octpt_lens.h, the text the host's lens rays compile too)
 __device__ __forceinline__ float dm_cos(float x) { float s, c; dm_sincos(x, s, c); return c; }
 
 __device__ inline float dm_asin(float x) {
@@ -170,22 +157,7 @@ __device__ __forceinline__ float dm_hypot(float x, float y) { return sqrtf(x * x
 // ---------------------------------------------------------------------------
 // counter-based RNG
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t path_state(uint32_t seed, uint32_t pixel, uint32_t sample) {
-    uint32_t h = lowbias32(seed ^ 0xA511E9B3u);
-    h = lowbias32(h ^ pixel);
-    return lowbias32(h ^ (sample * 0x9E3779B9u));
-}
-__device__ __forceinline__ float rng_next(uint32_t &st) {
-    const uint32_t s = st * 747796405u + 2891336453u;
-    st = s;
-    uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
-    w = (w >> 22u) ^ w;
-    return (float)(w >> 8) * (1.0f / 16777216.0f);
-}
+// (lowbias32, path_state, rng_next: csrc/octpt_lens.h, the text the host's lens rays compile too)
 
 // RNG stream of branch b > 0 of a split first reflection
 __device__ __forceinline__ uint32_t branch_state(uint32_t state, uint32_t b) {
@@ -1417,20 +1389,15 @@ __device__ inline v3 random_sun_direction(const DevSun &K, uint32_t &rng) {
 // ---------------------------------------------------------------------------
 // path logic shared by the megakernel and the wavefront shade kernel
 // ---------------------------------------------------------------------------
-// camera ray + fresh path (camera.rs:77-86, tile_renderer.rs:695-703)
+// camera ray + fresh path (camera.rs:77-86, tile_renderer.rs:695-703; lens_ray).  kLens: the
+// camera has an aperture, the ray leaves its point of the lens (the instances without it never read the lens)
+template <bool kLens = false>
 __device__ inline void new_path(const DevCamera &C, const DevRender &R, uint32_t x, uint32_t y, uint32_t sample,
                                 PathState &ps) {
-    ps.rng = path_state(R.seed, y * R.W + x, sample);
-    const float jlo = R.jlo, jhi = R.jhi;  // -1 / dim, 1 / dim (make_render)
-    const float xn = ((float)(2u * x + 1u) - (float)R.W) / R.dim;
-    const float yn = ((float)(2u * (R.H - y) - 1u) - (float)R.H) / R.dim;
-    const float dx = jlo + (jhi - jlo) * rng_next(ps.rng);
-    const float dy = jlo + (jhi - jlo) * rng_next(ps.rng);
-    const v3 nd = vadd(vadd(vscale(V(C.dir[0], C.dir[1], C.dir[2]), C.d_factor),
-                            vscale(V(C.right[0], C.right[1], C.right[2]), xn + dx)),
-                       vscale(V(C.up[0], C.up[1], C.up[2]), yn + dy));
-    ps.o = V(C.eye[0], C.eye[1], C.eye[2]);
-    ps.d = vnorm(nd);
+    float o[3], d[3];
+    ps.rng = lens_ray<kLens>(C, R, x, y, sample, o, d);
+    ps.o = V(o[0], o[1], o[2]);
+    ps.d = V(d[0], d[1], d[2]);
     ps.n = V(0.0f, 0.0f, 0.0f);
     ps.col[0] = ps.col[1] = ps.col[2] = ps.col[3] = 0.0f;
     ps.T = V(1.0f, 1.0f, 1.0f);
@@ -1687,7 +1654,7 @@ __device__ __forceinline__ uint32_t wave_ticket(uint32_t *ctr, bool want) {
 // ===========================================================================
 enum : uint32_t { ST_IDLE = 0, ST_NEWPATH, ST_BEGIN, ST_TRAV, ST_HIT, ST_MISS, ST_FINISH, ST_DONE };
 
-template <bool kNee, int kPrims>
+template <bool kNee, int kPrims, bool kLens = false>
 __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C, DevRender R, float4 *__restrict__ accum,
                                                         uint32_t *__restrict__ segcount, uint32_t *__restrict__ counter,
                                                         unsigned long long *__restrict__ stats) {
@@ -1726,7 +1693,7 @@ __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C,
         }
         if (__ballot(state != ST_DONE) == 0ull) break;
         if (state == ST_NEWPATH) {
-            new_path(C, R, pix % R.W, pix / R.W, R.spp_start + k, ray);
+            new_path<kLens>(C, R, pix % R.W, pix / R.W, R.spp_start + k, ray);
             cnt.paths++;
             state = ST_BEGIN;
         }
@@ -2008,7 +1975,7 @@ __device__ __forceinline__ size_t item_of(const DevRender &R, uint32_t s_local, 
 }
 
 // the path of chunk item `item`, its first segment begun; false when the pixel lies outside the image
-template <bool kFastDiv = true>
+template <bool kFastDiv = true, bool kLens = false>
 __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R, uint32_t item, PathState &ps,
                                           uint32_t &x, uint32_t &y) {
     uint32_t s_local, px_item;
@@ -2021,7 +1988,7 @@ __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R
         sample = sb.x;
         branch = sb.y >> 16;
     }
-    new_path(C, R, x, y, sample, ps);
+    new_path<kLens>(C, R, x, y, sample, ps);
     ps.branch = branch;
     begin_segment(ps);  // first segment: never capped
     return true;
@@ -2030,11 +1997,11 @@ __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R
 // generate the path of chunk item `item` into `slot`; false when the pixel lies outside the image.
 // kSeed (wf_seed_kernel): only the item is stored (item0); the chunk's first shade rebuilds the path
 // state from it (shade_lane) instead of reading 40 B per slot that the seed would have written.
-template <bool kSeed = false>
+template <bool kSeed = false, bool kLens = false>
 __device__ inline bool seed_item(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t slot,
                                  uint32_t item, PathState &ps, Counters &cnt) {
     uint32_t x, y;
-    if (!item_path(C, R, item, ps, x, y)) {
+    if (!item_path<true, kLens>(C, R, item, ps, x, y)) {
         B.color[item] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return false;
     }
@@ -2076,7 +2043,7 @@ struct ItemCursor {
 // with items left.  Items whose pixel lies outside the image are consumed (zero colour) and the
 // lane draws again, so a slot only goes idle once every shard is exhausted.  Every lane of the
 // wave must call this.
-template <bool kSeed = false>
+template <bool kSeed = false, bool kLens = false>
 __device__ inline bool regen(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t slot, bool want,
                              uint32_t chunk_items, ItemCursor &cur, PathState &ps, Counters &cnt) {
     bool need = want, ok = false;
@@ -2086,7 +2053,7 @@ __device__ inline bool regen(const DevCamera &C, const DevRender &R, const WaveB
         bool dry = false;
         if (need) {
             if (t >= n) dry = true;
-            else if (seed_item<kSeed>(C, R, B, slot, lo + t, ps, cnt)) { ok = true; need = false; }
+            else if (seed_item<kSeed, kLens>(C, R, B, slot, lo + t, ps, cnt)) { ok = true; need = false; }
         }
         if (__ballot(dry) != 0ull) {
             const uint32_t j = threadIdx.x & 63u;
@@ -2107,6 +2074,9 @@ __device__ inline bool regen(const DevCamera &C, const DevRender &R, const WaveB
 // order, so the extend waves draining the 64 segments side by side trace the same image tile for
 // 64 sample groups (the item-claim path's order, whose L2 locality this keeps).  Otherwise slot i
 // claims items from the shards (regen).
+// kLens (C37): a camera with an aperture, whose rays have origins of their own: full ray records at the direct
+// positions (store_ray, slot = item) in place of the 16-B camera records, for the ordinary extend and first shade
+template <bool kLens = false>
 __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender R, WaveBuffers B, uint32_t n_seed,
                                                          uint32_t chunk_items, unsigned long long *__restrict__ stats) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -2121,7 +2091,7 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         const uint32_t lo = shard_lo(seg, chunk_items), hi = shard_lo(seg + 1u, chunk_items);
         const uint32_t item = lo + (i >> 6) / kSegs * 64u + (i & 63u);
         slot = item;
-        if (item < hi) ok = seed_item<true>(C, R, B, slot, item, ps, cnt);
+        if (item < hi) ok = seed_item<true, kLens>(C, R, B, slot, item, ps, cnt);
         // Every tile inside the image (W and H multiples of the 8x8 tile: C3's 1080p, the 4K frames): no
         // item is dropped, so shard k's items fill segment k in item order -- position item - lo, the
         // count set by block 0 -- without a queue ticket per wave (8.3 M atomics per C3 frame on 64
@@ -2129,8 +2099,12 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         if (((R.W | R.H) & (kTile - 1u)) == 0u) {
             if (blockIdx.x == 0u && threadIdx.x < kSegs)
                 B.ctrl[ctr_count(0u, threadIdx.x)] = shard_lo(threadIdx.x + 1u, chunk_items) - shard_lo(threadIdx.x, chunk_items);
-            if (ok) store_cam_ray(B, seg * B.seg_cap + (item - lo), ps);
-            if (blockIdx.x == 0u && threadIdx.x == 0u) B.ray0[0][0] = B.eye;  // the camera records' origin record
+            if constexpr (kLens) {
+                if (ok) store_ray(B, 0u, seg * B.seg_cap + (item - lo), slot, ps);
+            } else {
+                if (ok) store_cam_ray(B, seg * B.seg_cap + (item - lo), ps);
+                if (blockIdx.x == 0u && threadIdx.x == 0u) B.ray0[0][0] = B.eye;  // the camera records' origin record
+            }
             // every item has its pixel (no tile overhangs the image), so the chunk starts chunk_items paths: one
             // add by block 0 instead of a counter flush per wave (8.3 M per C3 frame)
             if (blockIdx.x == 0u && threadIdx.x == 0u) atomicAdd(&stats[kStatPaths], (unsigned long long)chunk_items);
@@ -2138,7 +2112,7 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         }
     } else {
         ItemCursor cur = {seg, true};
-        ok = regen<true>(C, R, B, i, i < n_seed, chunk_items, cur, ps, cnt);
+        ok = regen<true, kLens>(C, R, B, i, i < n_seed, chunk_items, cur, ps, cnt);
     }
     const uint32_t t = wave_ticket(B.ctrl + ctr_count(0u, seg), ok);
     if (ok) store_ray(B, 0u, seg * B.seg_cap + t, slot, ps);
@@ -2334,7 +2308,7 @@ __global__ __launch_bounds__(kBlock, OCTPT_EXTEND_WAVES_OF(kPrims)) void wf_exte
 // through the same pack / unpack as a stored path, instead of being read.
 // kLean: the state is read at (q, pos) and a continuing path's is not stored here: the caller
 // stores it at the position its next ray takes (store_lean_at).
-template <bool kNee, bool kLean = false, int kSP = kPrimsModels>
+template <bool kNee, bool kLean = false, int kSP = kPrimsModels, bool kLens = false>
 __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C, const DevRender &R,
                                            const WaveBuffers &B, bool first, float4 r0, float4 r1, const uint2 *hit_rec,
                                            const uint4 *hit4_rec, PathState &ps, uint32_t &slot, uint32_t &item,
@@ -2344,11 +2318,12 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
         item = kLean ? slot : B.item0[slot];
         PathState s0;
         uint32_t x, y;
-        item_path<false>(C, R, item, s0, x, y);  // the seed only queued items inside the image
+        item_path<false, kLens>(C, R, item, s0, x, y);  // the seed only queued items inside the image
         float4 a, b;
         uint2 c;
         pack_path(s0, item, a, b, c);
-        unpack_path(a, b, c, B.eye, r1, ps, item);  // a camera ray's ray0 is (eye, kPrimNone): not re-read
+        // a camera ray's ray0 is (eye, kPrimNone), or with a lens (its origin as just rebuilt, kPrimNone): not re-read
+        unpack_path(a, b, c, kLens ? make_float4(s0.o.x, s0.o.y, s0.o.z, B.eye.w) : B.eye, r1, ps, item);
     } else if constexpr (kLean) {  // L = +0 as the path started, item = slot (store_lean_at)
         const float4 a = (q ? B.pb : B.pa)[pos];
         unpack_path(make_float4(a.x, a.y, a.z, 0.0f), make_float4(0.0f, 0.0f, a.w, __uint_as_float(slot)),
@@ -2438,7 +2413,9 @@ constexpr uint32_t kShadeLdsBlocks = OCTPT_SHADE_LDS_BLOCKS;
 // regeneration, no sun sampling, kLean above)
 // kNoFirst: an instance for the chunk's later launches, compiled without the first
 // launch's path-state rebuild (first is 0)
-template <bool kNee, bool kLdsMats, int kMode, bool kNoFirst = false, int kSP = kPrimsModels>
+// kLens (C37): the camera has an aperture (the first launch's rebuild and the regeneration form lens rays); the
+// general instances (kMode 0 and 1) alone, a lens camera's chunks do not take the lean state
+template <bool kNee, bool kLdsMats, int kMode, bool kNoFirst = false, int kSP = kPrimsModels, bool kLens = false>
 __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT_SHADE_WAVES) void wf_shade_kernel(DevScene Sg, DevCamera C, DevRender R, WaveBuffers B,
                                                           uint32_t q, uint32_t chunk_items, uint32_t first_arg,
                                                           unsigned long long *__restrict__ stats) {
@@ -2488,13 +2465,13 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT
                 cam_ray(B.eye, shard_lo(seg, chunk_items) + base + lane, r0c, r1);
             }
             const float4 r0 = first ? B.eye : B.ray0[q][i];  // (the chunk's first shade: the seed's camera rays)
-            append = shade_lane<kNee, kMode == 2, kSP>(S, C, R, B, first != 0u, r0, r1, B.hit + i,
+            append = shade_lane<kNee, kMode == 2, kSP, kLens>(S, C, R, B, first != 0u, r0, r1, B.hit + i,
                                                   S.has_blocks ? B.hit4 + i : nullptr, ps, slot, item, cnt, q, i);
             finished = !append;
         }
         // regenerate: finished lanes take the next chunk items (path regeneration)
         if constexpr (kMode == 1) {
-            if (regen(C, R, B, slot, finished, chunk_items, cur, ps, cnt)) append = true;
+            if (regen<false, kLens>(C, R, B, slot, finished, chunk_items, cur, ps, cnt)) append = true;
         }
         const uint32_t t = wave_ticket(B.ctrl + ctr_count(q ^ 1u, seg), append);
         if (append) {
@@ -3583,6 +3560,29 @@ __global__ __launch_bounds__(256) void atrous_var_kernel(DevDenoiseVar D, uint32
 
 }  // namespace
 
+#if defined(OCTPT_LENS_TU)  // (set by octpt_kernels_lens.hip alone: not a build switch)
+// The lens instances (C37) of the megakernel, the seed and the general shade, for octpt_kernels_lens.hip, which
+// compiles this text for them alone.  A module of their own: in one module with the others they change how the
+// compiler inlines the functions they share, and with it the registers of the instances without a lens (the
+// general shade without sun sampling 105 -> 90 VGPRs, its drain 136 -> 109).
+const void *lens_render_kernel(bool nee, bool blocks) {
+    return nee ? (blocks ? reinterpret_cast<const void *>(render_kernel<true, kPrimsBlocks, true>)
+                         : reinterpret_cast<const void *>(render_kernel<true, kPrimsModels, true>))
+               : (blocks ? reinterpret_cast<const void *>(render_kernel<false, kPrimsBlocks, true>)
+                         : reinterpret_cast<const void *>(render_kernel<false, kPrimsModels, true>));
+}
+const void *lens_seed_kernel() { return reinterpret_cast<const void *>(wf_seed_kernel<true>); }
+template <bool kNee, bool kLds>
+static const void *lens_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, true>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, true>);
+}
+const void *lens_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? lens_shade_of<true, true>(mode) : lens_shade_of<true, false>(mode))
+               : (lds ? lens_shade_of<false, true>(mode) : lens_shade_of<false, false>(mode));
+}
+#else
+
 // ESVO stack levels 1..depth-1 (level 0 is never used, see esvo_step)
 size_t render_lds_bytes(uint32_t depth) { return (size_t)(depth - 1u) * kBlock * (sizeof(uint2) + sizeof(uint16_t)); }
 
@@ -3690,6 +3690,14 @@ hipError_t launch_render(const DevScene &S0, const DevCamera &C, const DevRender
     // the general instance (spheres, cuboids, cuboid models) or the block-value one (C23)
     auto kern = S.sun.sun_sampling ? (S.has_blocks ? render_kernel<true, kPrimsBlocks> : render_kernel<true, kPrimsModels>)
                                    : (S.has_blocks ? render_kernel<false, kPrimsBlocks> : render_kernel<false, kPrimsModels>);
+    if (C.aperture > 0.0f) {  // the lens instance (C37)
+        void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), &accum,
+                        &segcount, &counter, &stats};
+        const hipError_t e = hipLaunchKernel(lens_render_kernel(S.sun.sun_sampling != 0, S.has_blocks != 0u), dim3(grid),
+                                             dim3(kBlock), args, render_lds_bytes(S.depth), stream);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), render_lds_bytes(S.depth), stream, S, C, R, accum, segcount,
                        counter, stats);
     return hipGetLastError();
@@ -3701,8 +3709,15 @@ hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuff
     const uint64_t threads = n_seed == chunk_items
                                  ? (uint64_t)kSegs * ((((uint64_t)chunk_items + kSegs - 1u) / kSegs + 63u) / 64u) * 64u
                                  : (uint64_t)n_seed;
-    hipLaunchKernelGGL(wf_seed_kernel, dim3((uint32_t)((threads + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, C, R, B, n_seed,
-                       chunk_items, stats);
+    const dim3 grid((uint32_t)((threads + kBlock - 1u) / kBlock));
+    if (C.aperture > 0.0f) {  // the lens instance (C37)
+        void *args[] = {const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), const_cast<WaveBuffers *>(&B), &n_seed,
+                        &chunk_items, &stats};
+        const hipError_t e = hipLaunchKernel(lens_seed_kernel(), grid, dim3(kBlock), args, 0, stream);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(wf_seed_kernel<false>, grid, dim3(kBlock), 0, stream, C, R, B, n_seed, chunk_items, stats);
     return hipGetLastError();
 }
 
@@ -3740,8 +3755,10 @@ static const void *shade_instance_of(int mode, bool first, int prims) {
                      : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0>);
 }
 bool shade_lds_tables(const DevScene &S) { return S.n_mats <= kShadeLdsMats && S.n_texs <= kShadeLdsMats; }
-static const void *shade_instance(const DevScene &S, int mode, bool first = false) {
+static const void *shade_instance(const DevScene &S, int mode, bool first = false, bool lens = false) {
     const bool lds = shade_lds_tables(S);
+    // a lens camera (C37): the general instances' lens twins (enqueue_wavefront keeps such chunks off the lean state)
+    if (lens) return lens_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
     const int prims = S.has_blocks    ? kPrimsBlocks
                       : S.has_models  ? kPrimsModels
                       : S.has_cuboids ? kPrimsBoxes
@@ -3765,8 +3782,8 @@ hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRende
     uint32_t first_u = first;
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
                     const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
-    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u), dim3(grid),
-                                         dim3(kBlock), args, 0, stream);
+    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, C.aperture > 0.0f),
+                                         dim3(grid), dim3(kBlock), args, 0, stream);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
@@ -3900,5 +3917,7 @@ hipError_t launch_unshard(uint32_t W, uint32_t H, uint32_t shard_count, const ui
                        shards, stride, frame);
     return hipGetLastError();
 }
+
+#endif  // OCTPT_LENS_TU
 
 }  // namespace octpt

@@ -146,7 +146,7 @@ class HipRenderer:
 
     def set_camera(self, camera: Camera) -> None:
         c = _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction),
-                        (C.c_float * 3)(*camera.up), camera.fov, 0.0, 0.0)
+                        (C.c_float * 3)(*camera.up), camera.fov, camera.aperture, camera.focal_distance)
         self._check(self._lib.octpt_set_camera(self._ctx, C.byref(c)))
         self._camera = camera
         self.reset_render()
@@ -342,6 +342,11 @@ class HipRenderer:
         """octpt_camera_rays of the current camera: [H, W, 6] (origin, unit direction), the rays the device
         traces for the pixel centres, bit for bit."""
         return camera_rays(self._camera, W, H)
+
+    def lens_rays(self, W: int, H: int, seed: int, sample: int) -> np.ndarray:
+        """octpt_lens_rays of the current camera: [H, W, 6], the first ray a W x H render with this seed traces
+        for sample `sample` of each pixel, bit for bit."""
+        return lens_rays(self._camera, W, H, seed, sample)
 
     def render_aov(self, settings: RenderSettings, which=_lib.AOV_NAMES, shard=(0, 1), compact: bool = False,
                    out: dict | None = None) -> dict:
@@ -798,7 +803,20 @@ def camera_rays(camera: Camera, W: int, H: int) -> np.ndarray:
     return rays
 
 
+def lens_rays(camera: Camera, W: int, H: int, seed: int, sample: int) -> np.ndarray:
+    """octpt_lens_rays: the first ray of sample `sample` of every pixel as a W x H render with this seed traces it
+    (jittered; from its point of the lens when the camera has an aperture), [H, W, 6] f32 (host-only, no context)."""
+    c = _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction), (C.c_float * 3)(*camera.up),
+                    camera.fov, camera.aperture, camera.focal_distance)
+    rays = np.zeros((H, W, 6), np.float32)
+    st = _lib.load().octpt_lens_rays(C.byref(c), W, H, seed, sample, rays.ctypes.data_as(C.c_void_p))
+    if st != 0:
+        raise _lib.OctptError(st, "octpt_lens_rays")
+    return rays
+
+
 def _c_camera(camera: Camera) -> "_lib.Camera":
+    # (the temporal entries take the camera without its lens: they refuse an aperture, DESIGN.md C37)
     return _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction), (C.c_float * 3)(*camera.up),
                        camera.fov, 0.0, 0.0)
 

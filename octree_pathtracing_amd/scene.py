@@ -122,6 +122,17 @@ class Camera:
     direction: tuple = (0.0, 0.0, 1.0)
     up: tuple = (0.0, 1.0, 0.0)
     fov: float = float(F32(70.0) * (PI / F32(180.0)))  # 70f32.to_radians()
+    # the thin lens: lens radius (0 = pinhole) and the distance along `direction` of the plane in
+    # focus, read only with an aperture
+    aperture: float = 0.0
+    focal_distance: float = 0.0
+
+    def focus(self, focal_point, aperture: float) -> "Camera":
+        """Camera::focus (camera.rs:69-73), evaluated in f32: a copy focused on focal_point with this aperture."""
+        v = np.asarray(focal_point, F32) - np.asarray(self.eye, F32)
+        d = np.asarray(self.direction, F32)
+        fd = (v[0] * d[0] + v[1] * d[1]) + v[2] * d[2]
+        return dataclasses_replace(self, focal_distance=float(fd), aperture=float(F32(aperture)))
 
     @staticmethod
     def look_at(eye, center, up=(0.0, 1.0, 0.0), fov=None) -> "Camera":
