@@ -864,6 +864,88 @@ octpt_status octpt_build_block_octree_sections_device(octpt_ctx *ctx, const octp
  * every entry builds its own replica. */
 octpt_status octpt_scene_build_sections_device(octpt_ctx *ctx, const octpt_scene_desc *scene,
                                                const octpt_section_world *world, uint32_t flags);
+/* --- the emitter grid: what next-event estimation toward emissive blocks samples from ---
+ * Block-value worlds only.  An emitter is a leaf of the block octree, at any level, whose block has
+ * model == OCTPT_MODEL_NONE and at least one face material with emittance > EPSILON (5e-8); a leaf of side
+ * s = 2^k (a LOD or compacted leaf) is one emitter (x, y, z, s): its minimum corner and its side.  Block-model
+ * leaves are not listed.  The grid has cells of grid_size voxels per side (a power of two, 1 .. 2^depth),
+ * cells_per_axis = 2^depth / grid_size per axis, cell (cx, cy, cz) at index cx + cells_per_axis * (cy +
+ * cells_per_axis * cz).  An emitter's home cell is (x, y, z) / grid_size; the list of cell c holds every emitter
+ * whose home cell is within Chebyshev distance 1 of c, in ascending Morton code of (x, y, z) (x bit 0, y bit 1,
+ * z bit 2 per level) -- Chunky's Grid.  CSR form: cell c's list is cell_emitters[cell_first[c] .. cell_first[c + 1]),
+ * indices into emitters[], which is in ascending Morton code itself. */
+typedef struct octpt_emitter {
+    uint32_t x, y, z, s;
+} octpt_emitter;
+/* Count-then-fill, as octpt_sections_to_cells: the three counts and cells_per_axis are always received (0 on an
+ * error).  With the three pointers NULL the call only counts.  Otherwise all three must be set and each capacity
+ * (in elements) must hold its array -- cell_count + 1, entry_count, emitter_count -- else nothing is written and
+ * the call is INVALID_ARG. */
+typedef struct octpt_emitter_grid_arrays {
+    uint32_t *cell_first;
+    uint32_t cell_first_capacity;
+    uint32_t *cell_emitters;
+    uint32_t cell_emitters_capacity;
+    octpt_emitter *emitters;
+    uint32_t emitters_capacity;
+    uint32_t cell_count, entry_count, emitter_count, cells_per_axis;
+} octpt_emitter_grid_arrays;
+/* The definition of the grid.  Host-only, no context.  cells are the rows (x, y, z, block) of
+ * octpt_build_block_octree, whose octree (with OCTPT_BUILD_COMPACT: the compacted one) provides the leaves.
+ * INVALID_ARG: what octpt_build_block_octree refuses, a block id >= block_count, a face material >=
+ * material_count, grid_size 0, not a power of two or above 2^depth, count-then-fill misuse.  OOM: more than 2^24
+ * emitters, more than 2^28 list entries, or more than 2^28 cells. */
+octpt_status octpt_build_emitter_grid(const uint32_t *cells, uint32_t cell_count, const octpt_block *blocks,
+                                      uint32_t block_count, const octpt_material *materials, uint32_t material_count,
+                                      uint32_t depth, uint32_t flags, uint32_t grid_size,
+                                      octpt_emitter_grid_arrays *out);
+/* Emitter sampling (Scene::emitter_sampling_strategy and emmitter_intensity, scene/mod.rs:5-58).  The default is
+ * NONE, with which every render is what it is without this call.  ONE_BLOCK and ALL have their values reserved and
+ * are UNSUPPORTED, as is every other strategy value.  grid_size: a power of two, 1 .. 2^21, and with ONE on a
+ * context that holds a scene at most 2^depth; intensity finite and >= 0; reserved words 0: else INVALID_ARG and
+ * the setting stays.  ONE on a context whose scene has primitive leaves is UNSUPPORTED.  Like
+ * octpt_set_sample_clamp the call joins a frame in flight, holds for later renders and is read when a render call
+ * is made.  It may come before or after the scene: with ONE and a block-value scene both known, the context's
+ * device builds the grid from the octree resident there (after octpt_scene_upload, octpt_scene_build_blocks_device
+ * or octpt_scene_build_sections_device alike; no host round trip), equal to octpt_build_emitter_grid's array for
+ * array; a new scene or grid_size rebuilds it, NONE drops it.  A scene set while ONE holds a grid_size above its
+ * 2^depth is INVALID_ARG; the grid's budgets are OOM as above.  On a multi-device context every entry builds its
+ * own replica.
+ * Renders: the preview and the guide buffers ignore the setting.  ONE with OCTPT_RENDER_MEGAKERNEL is UNSUPPORTED,
+ * as is ONE on a scene of primitive leaves.  With ONE and an empty grid (no emitter to sample) a render runs the
+ * ordinary kernel instances and equals NONE bit for bit.
+ * The estimator (csrc/octpt_emitter.h), at a diffuse reflection in a scene with emitters_enabled: own
+ * emittance is added at depth 1 as ever and dropped at depth > 1 exactly on a full-cell block leaf; unless it was just
+ * added at depth 1, one emitter of the hit point's cell list (K entries) is picked from an RNG stream of its own, one
+ * target in its cube, and one shadow segment is traced (counted like the sun's); when it hits a full-cell block leaf
+ * whose entered face emits and is not transparent there, L += T * albedo * col_e^2 * (|dir.n| / max(dist^2, 1) *
+ * emittance_e * intensity * K).  The factor K makes ONE an unbiased pick over the list: a deliberate choice.  With sun
+ * sampling the emitter segment runs first, then the sun's, then the bounce. */
+#define OCTPT_EMITTERS_NONE 0u
+#define OCTPT_EMITTERS_ONE 1u
+#define OCTPT_EMITTERS_ONE_BLOCK 2u /* reserved */
+#define OCTPT_EMITTERS_ALL 3u       /* reserved */
+typedef struct octpt_emitter_params {
+    uint32_t strategy;
+    uint32_t grid_size;
+    float intensity;
+    uint32_t reserved[5];
+} octpt_emitter_params;
+octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_params *params);
+/* The context's device grid, copied back in count-then-fill form (the rules of octpt_emitter_grid_arrays).  With
+ * NONE, or no block-value scene, the context holds no grid: INVALID_ARG.  On a multi-device context the first
+ * entry's replica. */
+octpt_status octpt_emitter_grid(octpt_ctx *ctx, octpt_emitter_grid_arrays *out);
+
+/* The emitter sample of one diffuse hit as the emitter instances take it (csrc/octpt_emitter.h, the text they compile):
+ * host-only.  grid: filled arrays of a grid of this depth and grid_size; rng_state: the path's RNG state before any
+ * draw of the hit.  out = (p.xyz, dir.xyz, dist, |dir.n| / max(dist^2, 1)), *list_length = K of the hit's cell,
+ * *emitter the picked index into emitters[], or 0xFFFFFFFF with dir, dist and the factor 0 when no segment is traced
+ * (K == 0, or a target at distance 0). */
+octpt_status octpt_emitter_sample(const octpt_emitter_grid_arrays *grid, uint32_t depth, uint32_t grid_size,
+                                  const float hit[3], const float normal[3], uint32_t rng_state, float out[8],
+                                  uint32_t *emitter, uint32_t *list_length);
+
 octpt_status octpt_octree_get_view(const octpt_octree *tree, octpt_octree_view *view);
 void octpt_octree_free(octpt_octree *tree);
 

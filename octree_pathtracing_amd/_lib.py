@@ -103,6 +103,23 @@ class SectionWorld(C.Structure):
                 ("palette_size", C.c_uint32), ("indices", C.c_void_p), ("index_count", C.c_uint32)]
 
 
+class EmitterGridArrays(C.Structure):
+    """octpt_emitter_grid_arrays: the emitter grid's three arrays, count-then-fill."""
+    _fields_ = [("cell_first", C.c_void_p), ("cell_first_capacity", C.c_uint32), ("cell_emitters", C.c_void_p),
+                ("cell_emitters_capacity", C.c_uint32), ("emitters", C.c_void_p), ("emitters_capacity", C.c_uint32),
+                ("cell_count", C.c_uint32), ("entry_count", C.c_uint32), ("emitter_count", C.c_uint32),
+                ("cells_per_axis", C.c_uint32)]
+
+
+class EmitterParams(C.Structure):
+    """octpt_emitter_params (octpt_set_emitter_sampling)."""
+    _fields_ = [("strategy", C.c_uint32), ("grid_size", C.c_uint32), ("intensity", C.c_float),
+                ("reserved", C.c_uint32 * 5)]
+
+
+EMITTERS_NONE, EMITTERS_ONE, EMITTERS_ONE_BLOCK, EMITTERS_ALL = 0, 1, 2, 3
+
+
 # numpy view of octpt_section rows (scene.SectionWorld.sections)
 SECTION_DTYPE = [("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("palette_first", "<u4"), ("palette_count", "<u4"),
                  ("index_first", "<u4")]
@@ -378,6 +395,12 @@ SIGNATURES = {
     "octpt_build_block_octree": (_i32, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "octpt_build_block_octree_device": (_i32, [_vp, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
     "octpt_scene_build_blocks_device": (_i32, [_vp, C.POINTER(SceneDesc), _vp, _u32, _u32]),
+    "octpt_build_emitter_grid": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32,
+                                        C.POINTER(EmitterGridArrays)]),
+    "octpt_set_emitter_sampling": (_i32, [_vp, C.POINTER(EmitterParams)]),
+    "octpt_emitter_sample": (_i32, [C.POINTER(EmitterGridArrays), _u32, _u32, _vp, _vp, _u32, _vp, C.POINTER(_u32),
+                                    C.POINTER(_u32)]),
+    "octpt_emitter_grid": (_i32, [_vp, C.POINTER(EmitterGridArrays)]),
     "octpt_sections_to_cells": (_i32, [C.POINTER(SectionWorld), _u32, _vp, _u32, C.POINTER(_u32)]),
     "octpt_build_block_octree_sections_device": (_i32, [_vp, C.POINTER(SectionWorld), _u32, _u32, C.POINTER(_vp)]),
     "octpt_scene_build_sections_device": (_i32, [_vp, C.POINTER(SceneDesc), C.POINTER(SectionWorld), _u32]),

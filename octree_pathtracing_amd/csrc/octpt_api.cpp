@@ -23,6 +23,7 @@
 #include "../../include/octpt.h"
 #include "octpt_internal.h"
 #include "octpt_lens.h"
+#include "octpt_emitter.h"
 #include "octpt_mask.h"
 #include "octpt_reproject.h"
 
@@ -197,6 +198,18 @@ struct octpt_ctx {
     size_t tile_spp_cap = 0, tile_err_cap = 0;
     // the sample clamp of resolve (C33, octpt_set_sample_clamp): 0 = off
     float sample_clamp = 0.0f;
+    // emitter sampling (C38, octpt_set_emitter_sampling): the setting, the scene's emissive flag per block (empty
+    // for a scene of primitive leaves), and the device grid built when strategy ONE and a block-value scene are
+    // both known (grid_valid; its three arrays are allocations of their own)
+    uint32_t emit_strategy = OCTPT_EMITTERS_NONE, emit_grid_size = 8u;
+    float emit_intensity = 1.0f;
+    std::vector<uint32_t> block_emissive;
+    DeviceEmitterGrid emit_grid;
+    bool grid_valid = false;
+    EmitGrid *d_emit_hdr = nullptr;  // the render's EmitGrid on the device (the emitter instances' S.leaf_sph)
+    EmitGrid emit_hdr_host{};        // ... and what it holds (uploaded again only when the grid or the intensity changed)
+    bool emit_hdr_valid = false;
+    size_t nee_planes = 0;           // planes of wb.pd per slot: 4 (sun sampling) or 6 (emitter sampling)
     // the seam rule's spread error plane (C34, the _ex driver) and the finished frame's guide and variance planes
     // (C36, octpt_render_final_device), grow-only
     float *d_tile_spread = nullptr;
@@ -309,7 +322,17 @@ void make_sun(const octpt_sun &p, const float lut_float[256], DevSun &k) {
     k.radius_cos = cosf(p.radius);                          // Sun::new (scene/mod.rs:331)
 }
 
+// the emitter grid of the scene (C38)
+void drop_emitter_grid(octpt_ctx *ctx) {
+    if (ctx->emit_grid.cell_first) (void)hipFree(ctx->emit_grid.cell_first);
+    if (ctx->emit_grid.cell_emitters) (void)hipFree(ctx->emit_grid.cell_emitters);
+    if (ctx->emit_grid.emitters) (void)hipFree(ctx->emit_grid.emitters);
+    ctx->emit_grid = DeviceEmitterGrid{};
+    ctx->grid_valid = false;
+}
+
 void free_scene(octpt_ctx *ctx) {
+    drop_emitter_grid(ctx);
     for (void *p : ctx->scene_allocs) (void)hipFree(p);
     ctx->scene_allocs.clear();
     ctx->has_scene = false;
@@ -661,6 +684,8 @@ octpt_status upload_tables(octpt_ctx *ctx, const octpt_scene_desc *d, bool host_
     for (uint32_t i = 0; i < d->material_count && d->emitters_enabled; ++i)
         emissive = emissive || d->materials[i].emittance > 5e-8f;  // RAY_EPSILON
     ctx->lean_scene = !emissive && !d->sun.sun_sampling;
+    ctx->block_emissive.clear();  // (validate_tables checked every face material)
+    if (d->blocks) block_emissive_flags(d->blocks, d->block_count, d->materials, d->material_count, ctx->block_emissive);
     return OCTPT_OK;
 }
 
@@ -708,6 +733,14 @@ octpt_status make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender
     if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
     if (p->max_depth == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "max_depth must be >= 1");
+    if (ctx->emit_strategy == OCTPT_EMITTERS_ONE && !(p->flags & OCTPT_RENDER_PREVIEW)) {  // C38
+        const octpt_ctx *gc = ctx->sub.empty() ? ctx : ctx->sub[0];  // a multi-device context: its entries hold the scene
+        if (!gc->S.has_blocks)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "emitter sampling needs a block-value scene (octpt_scene_desc.blocks)");
+        if (p->flags & OCTPT_RENDER_MEGAKERNEL)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "emitter sampling runs on the wavefront path only");
+        if (!gc->grid_valid) return fail(ctx, OCTPT_ERR_INTERNAL, "emitter sampling is on and the context holds no grid");
+    }
     if (ctx->sample_clamp != 0.0f && (p->flags & OCTPT_RENDER_MEGAKERNEL) && !(p->flags & OCTPT_RENDER_PREVIEW))
         return fail(ctx, OCTPT_ERR_UNSUPPORTED,
                     "a sample clamp is set (octpt_set_sample_clamp): the megakernel accumulates inside the kernel");
@@ -849,7 +882,8 @@ enum OomPart { kOomNone = 0, kOomQueues, kOomColor, kOomNee };
 // and the pool obtained becomes the context's cap (pool_cap), so later renders neither retry the larger
 // pool nor re-allocate.  A colour or sun-sampling allocation that fails returns OOM with *part set; the
 // caller shrinks the chunk or the pool and calls again (enqueue_wavefront).
-octpt_status ensure_wave(octpt_ctx *ctx, size_t pool, size_t color_items, bool nee, bool blocks, OomPart *part) {
+octpt_status ensure_wave(octpt_ctx *ctx, size_t pool, size_t color_items, bool nee, bool blocks, OomPart *part,
+                         bool emit = false) {
     *part = kOomNone;
     if (!ctx->h_count) {
         // coherent (fine-grained) pinned memory: wf_snapshot_kernel's stores reach the host directly
@@ -907,17 +941,21 @@ octpt_status ensure_wave(octpt_ctx *ctx, size_t pool, size_t color_items, bool n
         }
     }
     // sun-sampling planes (4 x 16 B per slot) only for scenes that sample the sun (C18)
-    if (nee && ctx->nee_pool < ctx->pool) {
+    // ... six with emitter sampling (C38): the emitter segment rides the same state, a waiting sun sample takes two more
+    const size_t planes = emit ? 6u : 4u;
+    if ((nee || emit) && (ctx->nee_pool < ctx->pool || ctx->nee_planes < planes)) {
         HIP_TRY(ctx, hipDeviceSynchronize());
         wave_free(ctx, ctx->nee_alloc);
         ctx->nee_pool = 0;
-        const hipError_t e = wave_malloc(ctx, &ctx->nee_alloc, 4 * ctx->pool * sizeof(float4));
+        ctx->nee_planes = 0;
+        const hipError_t e = wave_malloc(ctx, &ctx->nee_alloc, planes * ctx->pool * sizeof(float4));
         if (e != hipSuccess) {
             (void)hipGetLastError();
             *part = kOomNee;
             return hip_fail(ctx, e, "sun-sampling planes");
         }
         ctx->nee_pool = ctx->pool;
+        ctx->nee_planes = planes;
     }
     ctx->wb.pd = static_cast<float4 *>(ctx->nee_alloc);
     if (color_items > ctx->color_cap) {
@@ -980,6 +1018,29 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     const uint64_t n_px = R.total_items;
     // the sample clamp (C33) as set when the render call was made: octpt_set_sample_clamp joins a frame in flight
     const float clamp = ctx->sample_clamp;
+    // emitter sampling (C38): strategy ONE over a grid that holds emitters, in a scene whose emitters are enabled,
+    // takes the emitter instances of shade and the drain; an empty grid has nothing to sample and renders through
+    // the ordinary ones
+    const bool emit = ctx->emit_strategy == OCTPT_EMITTERS_ONE && ctx->grid_valid && ctx->emit_grid.n_emitters != 0u &&
+                      ctx->S.emitters != 0 && ctx->S.has_blocks != 0u;
+    DevScene Se = ctx->S;  // what shade and the drain take
+    if (emit) {
+        const DeviceEmitterGrid &g = ctx->emit_grid;
+        uint32_t axis_bits = 0;
+        while ((1u << axis_bits) < g.cells_axis) ++axis_bits;
+        const EmitGrid hdr{g.cell_first, g.cell_emitters, g.emitters, g.grid_shift, axis_bits, 1u << ctx->S.depth,
+                           ctx->emit_intensity};
+        if (!ctx->d_emit_hdr) HIP_TRY(ctx, hipMalloc(&ctx->d_emit_hdr, sizeof(EmitGrid)));
+        if (!ctx->emit_hdr_valid || std::memcmp(&ctx->emit_hdr_host, &hdr, sizeof hdr) != 0) {
+            // a new grid or intensity: an earlier render (on any stream) may still read the old header
+            ctx->emit_hdr_valid = false;
+            HIP_TRY(ctx, hipDeviceSynchronize());
+            HIP_TRY(ctx, hipMemcpy(ctx->d_emit_hdr, &hdr, sizeof hdr, hipMemcpyHostToDevice));
+            ctx->emit_hdr_host = hdr;
+            ctx->emit_hdr_valid = true;
+        }
+        Se.leaf_sph = reinterpret_cast<const float4 *>(ctx->d_emit_hdr);
+    }
     uint32_t chunk_spp = 1;
     uint64_t chunk_max = 0;
     octpt_status st = OCTPT_OK;
@@ -992,7 +1053,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a branch-schedule pass exceeds the 2^31-item chunk limit");
         OomPart part = kOomNone;
         st = ensure_wave(ctx, (size_t)std::min<uint64_t>(ctx->pool_cap, chunk_max), chunk_max,
-                         ctx->S.sun.sun_sampling != 0, ctx->S.has_blocks != 0, &part);
+                         ctx->S.sun.sun_sampling != 0, ctx->S.has_blocks != 0, &part, emit);
         if (st == OCTPT_OK) break;
         if (st != OCTPT_ERR_OOM) return st;
         // out of device memory past the queues: a smaller chunk (colour records) or pool (planes), kept
@@ -1028,6 +1089,8 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     const int seg_blocks = (int)(kSegs * 64u / kBlock);
     // blocks per CU: what the instance's registers allow (4 with regeneration, 5 without), or OCTPT_SHADE_BPC
     const uint32_t shade_bpc_env = std::min<uint32_t>(env_u32("OCTPT_SHADE_BPC", 0u), 8u);
+    // (sized by the ordinary instance's occupancy also when the emitter instances run, C38: they hold more registers,
+    // so their grid is oversubscribed; shade's grid-stride loop makes the grid size a matter of speed alone: accepted)
     auto grid_shade_of = [&](int mode) {
         int &cached = ctx->shade_bpc_cache[ctx->S.sun.sun_sampling ? 1 : 0]
                                           [shade_lds_tables(ctx->S) ? 1 : 0]
@@ -1125,7 +1188,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         // the lean 24-B path state: L stays 0 until the path ends, item = slot
         // (and no branch schedule: the lean shade instances carry no first-reflection split)
         // (nor a lens: its shade instances are the general ones' twins, C37)
-        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs && !lens) ? 1u : 0u;
+        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs && !lens && !emit) ? 1u : 0u;
         const int grid_shade = grid_shade_of(shade_mode(regen, ctx->wb.lean != 0u));
         // the seed writes its camera rays as 16-B records (store_cam_ray) when every item has its pixel: the first
         // extend (cam) and shade (first = 2) decode them
@@ -1155,8 +1218,8 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                                           ctx->d_stats, s));
             if ((st = ktimer_end(ctx, s, 0, ev)) != OCTPT_OK) return st;
             if ((st = ktimer_begin(ctx, s, ev)) != OCTPT_OK) return st;
-            HIP_TRY(ctx, launch_wf_shade(ctx->S, ctx->C, Rc, B, q, chunk_items, it == 0u ? (cam_rec ? 2u : 1u) : 0u,
-                                         regen, grid_shade, ctx->d_stats, s));
+            HIP_TRY(ctx, launch_wf_shade(Se, ctx->C, Rc, B, q, chunk_items, it == 0u ? (cam_rec ? 2u : 1u) : 0u,
+                                         regen, grid_shade, ctx->d_stats, s, emit));
             if ((st = ktimer_end(ctx, s, 1, ev)) != OCTPT_OK) return st;
             // snapshot of the queue iteration `it` produced; the host checks the snapshot of
             // iteration it - kLookahead, so the GPU always has kLookahead iterations queued (an
@@ -1188,7 +1251,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                     if (exhausted) {
                         // one path per wave (wf_drain_kernel), four waves per block
                         const int grid = (int)std::min<uint64_t>((queued + 3) / 4 + 1, (uint64_t)ctx->num_cu * 16u);
-                        HIP_TRY(ctx, launch_wf_drain(ctx->S, Rc, B, q ^ 1u, grid, ctx->d_stats, s));
+                        HIP_TRY(ctx, launch_wf_drain(Se, Rc, B, q ^ 1u, grid, ctx->d_stats, s, emit));
                         break;
                     }
                 }
@@ -1448,10 +1511,41 @@ octpt_status build_octree_handle(octpt_ctx *ctx, octpt_octree **out, const char 
     }
 }
 
-void commit_scene(octpt_ctx *ctx, const DevScene &S) {
+// The emitter grid of the context's scene and setting (C38): built on the device when strategy ONE and a block-value
+// scene are both known, dropped else.  A single-device context's, with its device current and its stream idle.
+octpt_status refresh_emitter_grid(octpt_ctx *ctx) {
+    drop_emitter_grid(ctx);
+    if (ctx->emit_strategy != OCTPT_EMITTERS_ONE || !ctx->has_scene || !ctx->S.has_blocks) return OCTPT_OK;
+    if (ctx->emit_grid_size > (1u << ctx->S.depth))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "the emitter grid's grid_size exceeds the world's 2^depth");
+    uint32_t shift = 0;
+    while ((1u << shift) < ctx->emit_grid_size) ++shift;
+    octpt_status refusal = OCTPT_OK;
+    const hipError_t e = build_emitter_grid_gpu(ctx->stream, ctx->build_scratch, ctx->S, ctx->block_emissive.data(), shift,
+                                                ctx->emit_grid, refusal);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hip_fail(ctx, e, "emitter grid build");
+    }
+    if (refusal == OCTPT_ERR_OOM)
+        return fail(ctx, OCTPT_ERR_OOM, "the emitter grid exceeds its budget (2^24 emitters, 2^28 list entries, 2^28 cells)");
+    if (refusal != OCTPT_OK) return fail(ctx, refusal, "emitter grid build: the scene holds more octants than it counts");
+    ctx->grid_valid = true;
+    return OCTPT_OK;
+}
+
+// a scene is set: its grid with it; a scene whose grid cannot be built is not kept
+octpt_status commit_scene(octpt_ctx *ctx, const DevScene &S) {
     ctx->S = S;
     ctx->has_scene = true;
     ++ctx->scene_gen;
+    const octpt_status st = refresh_emitter_grid(ctx);
+    if (st != OCTPT_OK) {
+        const std::string msg = ctx->err;
+        free_scene(ctx);
+        ctx->err = msg;
+    }
+    return st;
 }
 
 // a scene entry on a multi-device context: entry(child) makes a replica on every device entry
@@ -1511,8 +1605,7 @@ octpt_status pack_device_scene(octpt_ctx *ctx, const octpt_scene_desc *d, const 
     S.n_octants = t.n_octants;
     const octpt_status st = upload_tables(ctx, d, false, S);
     if (st != OCTPT_OK) return st;
-    commit_scene(ctx, S);
-    return OCTPT_OK;
+    return commit_scene(ctx, S);
 }
 
 // The three octpt_scene_build_*_device entries after their argument checks.  blocks: the entry builds a block-value
@@ -1698,6 +1791,7 @@ void octpt_destroy(octpt_ctx *ctx) {
     }
     free_scene(ctx);
     free_wave(ctx);
+    if (ctx->d_emit_hdr) (void)hipFree(ctx->d_emit_hdr);
     ctx->build_scratch.release();
     if (ctx->h_count) (void)hipHostFree(ctx->h_count);
     for (auto &ev : ctx->count_ev)
@@ -1803,8 +1897,7 @@ octpt_status octpt_scene_upload(octpt_ctx *ctx, const octpt_scene_desc *d) {
         S.n_octants = d->octant_count;
         st = upload_tables(ctx, d, true, S);
         if (st != OCTPT_OK) return st;
-        commit_scene(ctx, S);
-        return OCTPT_OK;
+        return commit_scene(ctx, S);
     } catch (const std::bad_alloc &) {
         free_scene(ctx);
         return fail(ctx, OCTPT_ERR_OOM, "host allocation failed");
@@ -3188,6 +3281,94 @@ octpt_status octpt_set_sample_clamp(octpt_ctx *ctx, float max_luminance) {
         const octpt_status st = octpt_set_sample_clamp(sc, max_luminance);
         if (st != OCTPT_OK) return fail(ctx, st, sc->err);
     }
+    return OCTPT_OK;
+}
+
+// ---------------- emitter sampling: the setting and the grid ----------------
+octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_params *p) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter params NULL");
+    if (p->strategy == OCTPT_EMITTERS_ONE_BLOCK || p->strategy == OCTPT_EMITTERS_ALL)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "emitter sampling strategies ONE_BLOCK and ALL are reserved (DESIGN.md C38)");
+    if (p->strategy > OCTPT_EMITTERS_ALL) return fail(ctx, OCTPT_ERR_UNSUPPORTED, "unknown emitter sampling strategy");
+    for (uint32_t r : p->reserved)
+        if (r) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter params: reserved words must be 0");
+    if (!(p->intensity >= 0.0f) || !std::isfinite(p->intensity))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter intensity must be finite and >= 0");
+    if (p->grid_size == 0u || (p->grid_size & (p->grid_size - 1u)) || p->grid_size > (1u << kMaxDepth))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter grid_size must be a power of two, 1 .. 2^21");
+    join_inflight(ctx);  // a frame in flight keeps the setting its call was made with
+    if (p->strategy == OCTPT_EMITTERS_ONE && ctx->has_scene) {
+        const octpt_ctx *sc = is_multi(ctx) ? ctx->sub[0] : ctx;
+        if (!sc->S.has_blocks)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "emitter sampling needs a block-value scene (octpt_scene_desc.blocks)");
+        if (p->grid_size > (1u << sc->S.depth))
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter grid_size exceeds the world's 2^depth");
+    }
+    const uint32_t old_strategy = ctx->emit_strategy, old_size = ctx->emit_grid_size;
+    const float old_intensity = ctx->emit_intensity;
+    ctx->emit_strategy = p->strategy;
+    ctx->emit_grid_size = p->grid_size;
+    ctx->emit_intensity = p->intensity;
+    octpt_status st = OCTPT_OK;
+    if (is_multi(ctx)) {
+        for (octpt_ctx *sc : ctx->sub) {
+            st = octpt_set_emitter_sampling(sc, p);
+            if (st != OCTPT_OK) {
+                fail(ctx, st, sc->err);
+                break;
+            }
+        }
+    } else if (old_strategy != p->strategy || old_size != p->grid_size) {
+        const hipError_t e = hipSetDevice(ctx->device);
+        st = e != hipSuccess ? hip_fail(ctx, e, "hipSetDevice") : OCTPT_OK;
+        if (st == OCTPT_OK && ctx->has_scene) {
+            const hipError_t es = hipStreamSynchronize(ctx->stream);
+            st = es != hipSuccess ? hip_fail(ctx, es, "hipStreamSynchronize") : refresh_emitter_grid(ctx);
+        }
+    }
+    if (st != OCTPT_OK) {  // the setting stays what it was (a grid budget refusal: the old grid is built again)
+        const std::string msg = ctx->err;
+        ctx->emit_strategy = old_strategy;
+        ctx->emit_grid_size = old_size;
+        ctx->emit_intensity = old_intensity;
+        if (is_multi(ctx)) {  // every entry back to the old setting, those that had taken the new one included
+            octpt_emitter_params old{};
+            old.strategy = old_strategy;
+            old.grid_size = old_size;
+            old.intensity = old_intensity;
+            for (octpt_ctx *sc : ctx->sub) (void)octpt_set_emitter_sampling(sc, &old);
+        } else if (ctx->has_scene) {
+            (void)refresh_emitter_grid(ctx);
+        }
+        ctx->err = msg;
+    }
+    return st;
+}
+
+octpt_status octpt_emitter_grid(octpt_ctx *ctx, octpt_emitter_grid_arrays *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter grid arrays NULL");
+    out->cell_count = out->entry_count = out->emitter_count = out->cells_per_axis = 0u;
+    join_inflight(ctx);
+    if (is_multi(ctx)) {
+        const octpt_status st = octpt_emitter_grid(ctx->sub[0], out);
+        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+    }
+    if (!ctx->grid_valid)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "the context holds no emitter grid (strategy OCTPT_EMITTERS_ONE and a block-value scene build it)");
+    const DeviceEmitterGrid &g = ctx->emit_grid;
+    bool fill = false;
+    const octpt_status st = emitter_grid_receive(out, g.n_cells, g.n_entries, g.n_emitters, g.cells_axis, fill);
+    if (st != OCTPT_OK) return fail(ctx, st, "emitter grid: set all three arrays, each with the capacity of its count");
+    if (!fill) return OCTPT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(out->cell_first, g.cell_first, ((size_t)g.n_cells + 1u) * 4, hipMemcpyDeviceToHost));
+    if (g.n_entries)
+        HIP_TRY(ctx, hipMemcpy(out->cell_emitters, g.cell_emitters, (size_t)g.n_entries * 4, hipMemcpyDeviceToHost));
+    if (g.n_emitters)
+        HIP_TRY(ctx, hipMemcpy(out->emitters, g.emitters, (size_t)g.n_emitters * sizeof(octpt_emitter), hipMemcpyDeviceToHost));
     return OCTPT_OK;
 }
 

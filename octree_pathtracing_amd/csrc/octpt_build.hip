@@ -519,6 +519,9 @@ inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + kBuildBlock - 1) / k
 // The slot map of the context's grow-only scratch (BuildScratch): a region is slots [first, end), and a cursor takes
 // its region's slots in a fixed order per build, so a rebuild finds every buffer where the last one left it.
 //   kBuildSlots    a builder's own buffers; its result (DeviceOctree) points into them until the next build.
+//                  The emitter grid's builder (build_emitter_grid_gpu, C38) counts as a build: it takes these slots
+//                  for its temporaries, so a scene entry's or octpt_set_emitter_sampling's grid build ends the
+//                  lifetime of an earlier DeviceOctree (the scene entries have packed theirs by then).
 //                  build_octree_gpu takes up to 0..25.
 //   kCellSlots     the block-value builds' part of it: 0 the uploaded input, 1 the error word, 2..5 the (Morton code,
 //                  block) streams and their sorted copies, 6..8 the tail's scan, 9..16 the octants.  The section
@@ -1137,6 +1140,319 @@ hipError_t fill_block_scene_gpu(hipStream_t stream, BuildScratch &scratch, const
                        t.n_octants, d_base, d_bflags, node_child);
     BTRY(hipGetLastError());
     return hipStreamSynchronize(stream);
+}
+
+// ---------------------------------------------------------------------------
+// The emitter grid from a resident block-value scene's node slots.  An octant is (base, mask):
+// mask bit i = child i present, bit i + 8 = it is a leaf, its slot node_child[base + rank of i] = (block, flags)
+// for a leaf and the child octant's own (base, mask) else.  Every store is a plain vector store, and positions
+// come from exclusive scans: no atomics.
+// ---------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ uint32_t compact_by_2(uint64_t v) {  // part_by_2's inverse, 21 bits
+    uint64_t x = v & 0x1249249249249249ULL;
+    x = (x | x >> 2) & 0x10c30c30c30c30c3ULL;
+    x = (x | x >> 4) & 0x100f00f00f00f00fULL;
+    x = (x | x >> 8) & 0x1f0000ff0000ffULL;
+    x = (x | x >> 16) & 0x1f00000000ffffULL;
+    x = (x | x >> 32) & 0x1fffffULL;
+    return (uint32_t)x;
+}
+
+// The walk's octant table: entry k = (base, mask | level << 16, Morton code of its corner); the root is entry 0 at
+// level 0.  Level l's entries are [lo, hi); cnt[k - lo] = its octant children (cnt[hi - lo] = 0: the scan's total).
+__global__ __launch_bounds__(kBuildBlock) void walk_count_kernel(const uint32_t *__restrict__ oc_mask, uint32_t lo,
+                                                                 uint32_t hi, uint32_t *__restrict__ cnt) {
+    const uint32_t k = lo + blockIdx.x * kBuildBlock + threadIdx.x;
+    if (k > hi) return;
+    const uint32_t m = k < hi ? oc_mask[k] : 0u;
+    cnt[k - lo] = (uint32_t)__popc(m & ~(m >> 8) & 0xFFu);
+}
+
+// ... and its octant children, in child order, to entries hi + offs[k - lo] ..; cap = the table's size (never
+// exceeded: the host compared hi + total with it)
+__global__ __launch_bounds__(kBuildBlock) void walk_fill_kernel(const uint2 *__restrict__ node_child,
+                                                                uint32_t *__restrict__ oc_base,
+                                                                uint32_t *__restrict__ oc_mask,
+                                                                uint64_t *__restrict__ oc_code, uint32_t lo, uint32_t hi,
+                                                                const uint32_t *__restrict__ offs, uint32_t depth,
+                                                                uint32_t cap) {
+    const uint32_t k = lo + blockIdx.x * kBuildBlock + threadIdx.x;
+    if (k >= hi) return;
+    const uint32_t mw = oc_mask[k], m = mw & 0xFFFFu, lv = mw >> 16, base = oc_base[k];
+    const uint64_t code = oc_code[k];
+    const uint32_t shift = 3u * (depth - 1u - lv);
+    uint32_t dst = hi + offs[k - lo], rank = 0u;
+    for (uint32_t i = 0; i < 8u; ++i) {
+        if (!((m >> i) & 1u)) continue;
+        const uint32_t r = rank++;
+        if ((m >> (i + 8u)) & 1u) continue;
+        const uint2 slot = node_child[base + r];
+        if (dst < cap) {
+            oc_base[dst] = slot.x;
+            oc_mask[dst] = (slot.y & 0xFFFFu) | ((lv + 1u) << 16);
+            oc_code[dst] = code | ((uint64_t)i << shift);
+        }
+        ++dst;
+    }
+}
+
+// emissive leaf children of table entry k (cnt[n] = 0), or with kFill their (Morton code, level) from offs[k]
+template <bool kFill>
+__global__ __launch_bounds__(kBuildBlock) void leaf_emitters_kernel(const uint2 *__restrict__ node_child,
+                                                                    const uint32_t *__restrict__ oc_base,
+                                                                    const uint32_t *__restrict__ oc_mask,
+                                                                    const uint64_t *__restrict__ oc_code, uint32_t n,
+                                                                    const uint32_t *__restrict__ emissive,
+                                                                    uint32_t n_blocks, uint32_t depth,
+                                                                    uint32_t *__restrict__ cnt,
+                                                                    const uint32_t *__restrict__ offs,
+                                                                    uint64_t *__restrict__ keys,
+                                                                    uint32_t *__restrict__ levels, uint32_t n_keys) {
+    const uint32_t k = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (k > n || (kFill && k == n)) return;
+    uint32_t found = 0u;
+    if (k < n) {
+        const uint32_t mw = oc_mask[k], m = mw & 0xFFFFu, lv = mw >> 16, base = oc_base[k];
+        const uint32_t shift = 3u * (depth - 1u - lv);
+        uint32_t rank = 0u;
+        for (uint32_t i = 0; i < 8u; ++i) {
+            if (!((m >> i) & 1u)) continue;
+            const uint32_t r = rank++;
+            if (!((m >> (i + 8u)) & 1u)) continue;
+            const uint32_t block = node_child[base + r].x;
+            if (block >= n_blocks || !emissive[block]) continue;
+            if (kFill) {
+                const uint32_t dst = offs[k] + found;
+                if (dst < n_keys) {
+                    keys[dst] = oc_code[k] | ((uint64_t)i << shift);
+                    levels[dst] = lv + 1u;
+                }
+            }
+            ++found;
+        }
+    }
+    if (!kFill) cnt[k] = found;
+}
+
+__global__ __launch_bounds__(kBuildBlock) void emitter_records_kernel(const uint64_t *__restrict__ keys,
+                                                                      const uint32_t *__restrict__ levels, uint32_t n,
+                                                                      uint32_t depth, octpt_emitter *__restrict__ out) {
+    const uint32_t k = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (k >= n) return;
+    const uint64_t c = keys[k];
+    octpt_emitter e;
+    e.x = compact_by_2(c);
+    e.y = compact_by_2(c >> 1);
+    e.z = compact_by_2(c >> 2);
+    e.s = 1u << (depth - levels[k]);
+    out[k] = e;
+}
+
+// first sorted key >= code
+__device__ inline uint32_t key_lower_bound(const uint64_t *__restrict__ keys, uint32_t n, uint64_t code) {
+    uint32_t lo = 0u, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < code) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+
+// The emitters of a home cell are one run of the sorted keys: those with the cell's Morton code above bit
+// 3 * gshift.  Cell c's list is the runs of its 27-neighbourhood in ascending cell code.  kFill false: cnt[c] = the
+// list's length (cnt[n_cells] = 0); true: the list from first[c].
+template <bool kFill>
+__global__ __launch_bounds__(kBuildBlock) void grid_cells_kernel(const uint64_t *__restrict__ keys, uint32_t n_keys,
+                                                                 uint32_t axis_bits, uint32_t gshift, uint32_t n_cells,
+                                                                 uint32_t *__restrict__ cnt,
+                                                                 const uint32_t *__restrict__ first,
+                                                                 uint32_t *__restrict__ list, uint32_t n_entries) {
+    const uint32_t c = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (c > n_cells || (kFill && c == n_cells)) return;
+    if (c == n_cells) {
+        cnt[c] = 0u;
+        return;
+    }
+    const uint32_t G = 1u << axis_bits, am = G - 1u;
+    const int32_t cx = (int32_t)(c & am), cy = (int32_t)((c >> axis_bits) & am), cz = (int32_t)(c >> (2u * axis_bits));
+    uint32_t run_lo[27], run_n[27];
+    uint32_t runs = 0u, total = 0u;
+    for (int32_t dz = -1; dz <= 1; ++dz)
+        for (int32_t dy = -1; dy <= 1; ++dy)
+            for (int32_t dx = -1; dx <= 1; ++dx) {
+                const int32_t x = cx + dx, y = cy + dy, z = cz + dz;
+                if (x < 0 || y < 0 || z < 0 || x >= (int32_t)G || y >= (int32_t)G || z >= (int32_t)G) continue;
+                const uint64_t mc = morton((uint32_t)x, (uint32_t)y, (uint32_t)z);
+                const uint32_t lo = key_lower_bound(keys, n_keys, mc << (3u * gshift));
+                const uint32_t hi = key_lower_bound(keys, n_keys, (mc + 1ull) << (3u * gshift));
+                if (hi == lo) continue;
+                total += hi - lo;
+                if (kFill) {  // insertion by run start: the non-empty runs are disjoint, so their starts ascend with the cell code
+                    uint32_t j = runs;
+                    while (j > 0u && run_lo[j - 1u] > lo) {
+                        run_lo[j] = run_lo[j - 1u];
+                        run_n[j] = run_n[j - 1u];
+                        --j;
+                    }
+                    run_lo[j] = lo;
+                    run_n[j] = hi - lo;
+                }
+                ++runs;
+            }
+    if (!kFill) {
+        cnt[c] = total;
+        return;
+    }
+    uint32_t dst = first[c];
+    for (uint32_t j = 0; j < runs; ++j)
+        for (uint32_t k = 0; k < run_n[j]; ++k, ++dst)
+            if (dst < n_entries) list[dst] = run_lo[j] + k;
+}
+
+hipError_t scan_u32(hipStream_t stream, char *d_tmp, size_t tmp_bytes, const uint32_t *in, uint32_t *out, uint32_t n) {
+    size_t bytes = tmp_bytes;
+    return hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, in, out, n, stream);
+}
+
+}  // namespace
+
+hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, const DevScene &S,
+                                  const uint32_t *emissive, uint32_t grid_shift, DeviceEmitterGrid &out,
+                                  octpt_status &refusal) {
+    out = DeviceEmitterGrid{};
+    refusal = OCTPT_OK;
+    const uint32_t depth = S.depth, axis_bits = depth - grid_shift;
+    if (3ull * axis_bits > 28ull) {  // more than kMaxEmitterCells cells
+        refusal = OCTPT_ERR_OOM;
+        return hipSuccess;
+    }
+    const uint32_t n_cells = 1u << (3u * axis_bits);
+    const uint32_t cap = std::max(S.n_octants, 1u);  // the walk's table: every octant once
+    ScratchCursor pool{scratch, kBuildSlots};
+    uint32_t *d_emissive, *oc_base, *oc_mask, *d_cnt, *d_offs;
+    uint64_t *oc_code;
+    const size_t n_scan = (size_t)std::max(cap, n_cells) + 1u;
+    BTRY(pool.get(&d_emissive, S.n_blocks));
+    BTRY(pool.get(&oc_base, cap));
+    BTRY(pool.get(&oc_mask, cap));
+    BTRY(pool.get(&oc_code, cap));
+    BTRY(pool.get(&d_cnt, n_scan));
+    BTRY(pool.get(&d_offs, n_scan));
+    size_t scan_bytes = 0;
+    BTRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_cnt, d_offs, (int)n_scan, stream));
+    char *d_tmp;
+    BTRY(pool.get(&d_tmp, scan_bytes));
+    if (S.n_blocks)
+        BTRY(hipMemcpyAsync(d_emissive, emissive, (size_t)S.n_blocks * 4, hipMemcpyHostToDevice, stream));
+    // the root, then level after level
+    const uint32_t root_mask = S.root_mask & 0xFFFFu;
+    const uint64_t zero = 0ull;
+    BTRY(hipMemcpyAsync(oc_base, &S.root, 4, hipMemcpyHostToDevice, stream));
+    BTRY(hipMemcpyAsync(oc_mask, &root_mask, 4, hipMemcpyHostToDevice, stream));
+    BTRY(hipMemcpyAsync(oc_code, &zero, 8, hipMemcpyHostToDevice, stream));
+    BTRY(hipStreamSynchronize(stream));  // the three words above are read from this frame
+    uint32_t lo = 0u, hi = 1u;
+    for (uint32_t lv = 0; lv + 1u < depth && hi > lo; ++lv) {  // an octant at level depth - 1 has leaf children only
+        const uint32_t n = hi - lo;
+        hipLaunchKernelGGL(walk_count_kernel, dim3(blocks((uint64_t)n + 1)), dim3(kBuildBlock), 0, stream, oc_mask, lo, hi,
+                           d_cnt);
+        BTRY(hipGetLastError());
+        BTRY(scan_u32(stream, d_tmp, scan_bytes, d_cnt, d_offs, n + 1u));
+        uint32_t total = 0u;
+        BTRY(hipMemcpyAsync(&total, d_offs + n, 4, hipMemcpyDeviceToHost, stream));
+        BTRY(hipStreamSynchronize(stream));
+        if ((uint64_t)hi + total > cap) {
+            refusal = OCTPT_ERR_INTERNAL;
+            return hipSuccess;
+        }
+        if (total) {
+            hipLaunchKernelGGL(walk_fill_kernel, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, S.node_child, oc_base,
+                               oc_mask, oc_code, lo, hi, d_offs, depth, cap);
+            BTRY(hipGetLastError());
+        }
+        lo = hi;
+        hi += total;
+    }
+    const uint32_t n_oct = hi;
+    // the emissive leaves: mark and scan, emit (Morton code, level), sort
+    hipLaunchKernelGGL(leaf_emitters_kernel<false>, dim3(blocks((uint64_t)n_oct + 1)), dim3(kBuildBlock), 0, stream,
+                       S.node_child, oc_base, oc_mask, oc_code, n_oct, d_emissive, S.n_blocks, depth, d_cnt,
+                       (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, 0u);
+    BTRY(hipGetLastError());
+    BTRY(scan_u32(stream, d_tmp, scan_bytes, d_cnt, d_offs, n_oct + 1u));
+    uint32_t n_em = 0u;
+    BTRY(hipMemcpyAsync(&n_em, d_offs + n_oct, 4, hipMemcpyDeviceToHost, stream));
+    BTRY(hipStreamSynchronize(stream));
+    if (n_em > kMaxEmitters) {
+        refusal = OCTPT_ERR_OOM;
+        return hipSuccess;
+    }
+    uint64_t *d_keys, *d_keys_s;
+    uint32_t *d_lv, *d_lv_s;
+    BTRY(pool.get(&d_keys, n_em));
+    BTRY(pool.get(&d_keys_s, n_em));
+    BTRY(pool.get(&d_lv, n_em));
+    BTRY(pool.get(&d_lv_s, n_em));
+    if (n_em) {
+        hipLaunchKernelGGL(leaf_emitters_kernel<true>, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, S.node_child,
+                           oc_base, oc_mask, oc_code, n_oct, d_emissive, S.n_blocks, depth, (uint32_t *)nullptr, d_offs,
+                           d_keys, d_lv, n_em);
+        BTRY(hipGetLastError());
+        size_t sort_bytes = 0;
+        BTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys, d_keys_s, d_lv, d_lv_s, n_em, 0,
+                                                (int)(3u * depth), stream));
+        char *d_sort;
+        BTRY(pool.get(&d_sort, sort_bytes));
+        BTRY(hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_keys, d_keys_s, d_lv, d_lv_s, n_em, 0,
+                                                (int)(3u * depth), stream));
+    }
+    // count the 27-neighbourhood per cell, scan into cell_first, fill
+    DeviceEmitterGrid g;
+    auto drop = [&](hipError_t e) {
+        if (g.cell_first) (void)hipFree(g.cell_first);
+        if (g.cell_emitters) (void)hipFree(g.cell_emitters);
+        if (g.emitters) (void)hipFree(g.emitters);
+        return e;
+    };
+#define GTRY(expr)                                   \
+    do {                                             \
+        const hipError_t _e = (expr);                \
+        if (_e != hipSuccess) return drop(_e);       \
+    } while (0)
+    GTRY(hipMalloc(&g.cell_first, ((size_t)n_cells + 1u) * 4));
+    GTRY(hipMalloc(&g.emitters, std::max<size_t>(n_em, 1) * sizeof(octpt_emitter)));
+    hipLaunchKernelGGL(grid_cells_kernel<false>, dim3(blocks((uint64_t)n_cells + 1)), dim3(kBuildBlock), 0, stream,
+                       d_keys_s, n_em, axis_bits, grid_shift, n_cells, d_cnt, (const uint32_t *)nullptr,
+                       (uint32_t *)nullptr, 0u);
+    GTRY(hipGetLastError());
+    GTRY(scan_u32(stream, d_tmp, scan_bytes, d_cnt, g.cell_first, n_cells + 1u));
+    uint32_t n_entries = 0u;
+    GTRY(hipMemcpyAsync(&n_entries, g.cell_first + n_cells, 4, hipMemcpyDeviceToHost, stream));
+    GTRY(hipStreamSynchronize(stream));
+    if (n_entries > kMaxEmitterEntries) {
+        refusal = OCTPT_ERR_OOM;
+        return drop(hipSuccess);
+    }
+    GTRY(hipMalloc(&g.cell_emitters, std::max<size_t>(n_entries, 1) * 4));
+    if (n_em) {
+        hipLaunchKernelGGL(emitter_records_kernel, dim3(blocks(n_em)), dim3(kBuildBlock), 0, stream, d_keys_s, d_lv_s, n_em,
+                           depth, g.emitters);
+        GTRY(hipGetLastError());
+        hipLaunchKernelGGL(grid_cells_kernel<true>, dim3(blocks(n_cells)), dim3(kBuildBlock), 0, stream, d_keys_s, n_em,
+                           axis_bits, grid_shift, n_cells, (uint32_t *)nullptr, g.cell_first, g.cell_emitters, n_entries);
+        GTRY(hipGetLastError());
+    }
+    GTRY(hipStreamSynchronize(stream));
+#undef GTRY
+    g.n_cells = n_cells;
+    g.n_entries = n_entries;
+    g.n_emitters = n_em;
+    g.cells_axis = 1u << axis_bits;
+    g.grid_shift = grid_shift;
+    out = g;
+    return hipSuccess;
 }
 
 }  // namespace octpt

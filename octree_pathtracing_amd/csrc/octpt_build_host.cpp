@@ -179,9 +179,130 @@ octpt_status section_world_status(const octpt_section_world *w, uint32_t depth) 
     return OCTPT_OK;
 }
 
+// the emissive flag of every block (C38): 1 for a block that fills its cell (no model) and has a face material
+// with emittance > EPSILON; false: a face material index outside the table
+bool block_emissive_flags(const octpt_block *blocks, uint32_t nb, const octpt_material *mats, uint32_t nm,
+                          std::vector<uint32_t> &out) {
+    out.assign(nb, 0u);
+    for (uint32_t b = 0; b < nb; ++b) {
+        if (blocks[b].model != OCTPT_MODEL_NONE) continue;
+        for (int f = 0; f < 6; ++f) {
+            const uint32_t m = blocks[b].face_material[f];
+            if (m >= nm) return false;
+            if (mats[m].emittance > kEmitterEpsilon) out[b] = 1u;
+        }
+    }
+    return true;
+}
+
+// count-then-fill of octpt_emitter_grid_arrays: the counts into *out, then OK when the call only counts or the
+// arrays hold them (fill = true), INVALID_ARG (nothing may be written) else
+octpt_status emitter_grid_receive(octpt_emitter_grid_arrays *out, uint32_t n_cells, uint32_t n_entries,
+                                  uint32_t n_emitters, uint32_t cells_axis, bool &fill) {
+    fill = false;
+    out->cell_count = n_cells;
+    out->entry_count = n_entries;
+    out->emitter_count = n_emitters;
+    out->cells_per_axis = cells_axis;
+    if (!out->cell_first && !out->cell_emitters && !out->emitters) return OCTPT_OK;
+    if (!out->cell_first || !out->cell_emitters || !out->emitters) return OCTPT_ERR_INVALID_ARG;
+    if (out->cell_first_capacity < (uint64_t)n_cells + 1u || out->cell_emitters_capacity < n_entries ||
+        out->emitters_capacity < n_emitters)
+        return OCTPT_ERR_INVALID_ARG;
+    fill = true;
+    return OCTPT_OK;
+}
+
 }  // namespace octpt
 
+namespace {
+
+struct HostEmitter {
+    uint64_t code;
+    octpt_emitter e;
+    bool operator<(const HostEmitter &o) const { return code < o.code; }
+};
+
+// the emissive leaves under octant o (corner (x, y, z), side s), in any order
+bool collect_emitters(const octpt_octree &t, uint32_t o, uint32_t x, uint32_t y, uint32_t z, uint32_t s,
+                      const std::vector<uint32_t> &emissive, std::vector<HostEmitter> &out) {
+    const octpt_octant &oc = t.octants[o];
+    const uint32_t h = s >> 1;
+    for (uint32_t i = 0; i < 8u; ++i) {
+        if (!((oc.child_mask >> i) & 1u)) continue;
+        const uint32_t cx = x + ((i & 1u) ? h : 0u), cy = y + ((i & 2u) ? h : 0u), cz = z + ((i & 4u) ? h : 0u);
+        const uint32_t v = oc.children[i];
+        if ((oc.child_mask >> (i + 8u)) & 1u) {
+            if (v >= emissive.size()) return false;
+            if (emissive[v]) out.push_back({morton(cx, cy, cz), {cx, cy, cz, h}});
+        } else if (!collect_emitters(t, v, cx, cy, cz, h, emissive, out)) {
+            return false;
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
 extern "C" {
+
+octpt_status octpt_build_emitter_grid(const uint32_t *cells, uint32_t n, const octpt_block *blocks, uint32_t nb,
+                                      const octpt_material *mats, uint32_t nm, uint32_t depth, uint32_t flags,
+                                      uint32_t grid_size, octpt_emitter_grid_arrays *out) {
+    if (!out) return OCTPT_ERR_INVALID_ARG;
+    out->cell_count = out->entry_count = out->emitter_count = out->cells_per_axis = 0u;
+    if ((nb && !blocks) || (nm && !mats)) return OCTPT_ERR_INVALID_ARG;
+    if (depth < 1 || depth > kMaxDepth) return OCTPT_ERR_INVALID_ARG;
+    if (grid_size == 0u || (grid_size & (grid_size - 1u)) || grid_size > (1u << depth)) return OCTPT_ERR_INVALID_ARG;
+    octpt_octree *tree = nullptr;
+    const octpt_status bst = octpt_build_block_octree(cells, n, depth, flags, &tree);
+    if (bst != OCTPT_OK) return bst;
+    std::unique_ptr<octpt_octree> hold(tree);
+    try {
+        std::vector<uint32_t> emissive;
+        if (!block_emissive_flags(blocks, nb, mats, nm, emissive)) return OCTPT_ERR_INVALID_ARG;
+        std::vector<HostEmitter> em;
+        if (!collect_emitters(*tree, tree->root, 0u, 0u, 0u, 1u << depth, emissive, em)) return OCTPT_ERR_INVALID_ARG;
+        if (em.size() > kMaxEmitters) return OCTPT_ERR_OOM;
+        std::sort(em.begin(), em.end());
+        uint32_t shift = 0;
+        while ((1u << shift) < grid_size) ++shift;
+        const uint64_t G = (uint64_t)1u << (depth - shift);
+        if (G * G * G > kMaxEmitterCells) return OCTPT_ERR_OOM;
+        const uint32_t n_cells = (uint32_t)(G * G * G);
+        // every emitter into the lists of its home cell's 27-neighbourhood: count, scan, fill in Morton order
+        std::vector<uint64_t> first((size_t)n_cells + 1u, 0u);
+        auto each_cell = [&](const octpt_emitter &e, auto fn) {
+            const int64_t hx = e.x >> shift, hy = e.y >> shift, hz = e.z >> shift;
+            for (int64_t dz = -1; dz <= 1; ++dz)
+                for (int64_t dy = -1; dy <= 1; ++dy)
+                    for (int64_t dx = -1; dx <= 1; ++dx) {
+                        const int64_t cx = hx + dx, cy = hy + dy, cz = hz + dz;
+                        if (cx < 0 || cy < 0 || cz < 0 || cx >= (int64_t)G || cy >= (int64_t)G || cz >= (int64_t)G)
+                            continue;
+                        fn((size_t)(cx + (int64_t)G * (cy + (int64_t)G * cz)));
+                    }
+        };
+        for (const HostEmitter &h : em) each_cell(h.e, [&](size_t c) { first[c + 1]++; });
+        for (size_t c = 0; c < n_cells; ++c) first[c + 1] += first[c];
+        if (first[n_cells] > kMaxEmitterEntries) return OCTPT_ERR_OOM;
+        bool fill = false;
+        const octpt_status st =
+            emitter_grid_receive(out, n_cells, (uint32_t)first[n_cells], (uint32_t)em.size(), (uint32_t)G, fill);
+        if (st != OCTPT_OK || !fill) return st;
+        std::vector<uint32_t> next(first.begin(), first.end() - 1);
+        for (size_t k = 0; k < em.size(); ++k) {
+            out->emitters[k] = em[k].e;
+            each_cell(em[k].e, [&](size_t c) { out->cell_emitters[next[c]++] = (uint32_t)k; });
+        }
+        for (size_t c = 0; c <= n_cells; ++c) out->cell_first[c] = (uint32_t)first[c];
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return OCTPT_ERR_OOM;
+    } catch (...) {
+        return OCTPT_ERR_INTERNAL;
+    }
+}
 
 octpt_status octpt_build_octree(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid *cuboids, uint32_t nc,
                                 uint32_t depth, octpt_octree **out) {

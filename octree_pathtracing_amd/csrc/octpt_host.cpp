@@ -14,6 +14,7 @@
 
 #include "../../include/octpt.h"
 #include "octpt_lens.h"
+#include "octpt_emitter.h"
 #include "octpt_mask.h"
 #include "octpt_reproject.h"
 
@@ -223,5 +224,30 @@ extern "C" octpt_status octpt_reproject_coords(const octpt_camera *camera, const
             prev_xy[2u * p + 1u] = fy;
             prev_depth[p] = zp;
         }
+    return OCTPT_OK;
+}
+
+// csrc/octpt_emitter.h's emitter_sample, the text shade_segment's emitter instances compile, for one hit
+extern "C" octpt_status octpt_emitter_sample(const octpt_emitter_grid_arrays *grid, uint32_t depth, uint32_t grid_size,
+                                             const float hit[3], const float normal[3], uint32_t rng_state,
+                                             float out[8], uint32_t *emitter, uint32_t *list_length) {
+    if (!grid || !hit || !normal || !out || !emitter || !list_length) return OCTPT_ERR_INVALID_ARG;
+    if (!grid->cell_first || !grid->cell_emitters || !grid->emitters) return OCTPT_ERR_INVALID_ARG;
+    if (depth < 1 || depth > 21 || grid_size == 0u || (grid_size & (grid_size - 1u)) || grid_size > (1u << depth))
+        return OCTPT_ERR_INVALID_ARG;
+    uint32_t shift = 0;
+    while ((1u << shift) < grid_size) ++shift;
+    if (grid->cells_per_axis != (1u << (depth - shift))) return OCTPT_ERR_INVALID_ARG;
+    const octpt::EmitGrid G{grid->cell_first, grid->cell_emitters, grid->emitters, shift, depth - shift, 1u << depth, 1.0f};
+    octpt::EmitShot s{};
+    const bool traced = octpt::emitter_sample(G, hit, normal, rng_state, s);
+    *list_length = s.K;
+    *emitter = traced ? s.emitter : 0xFFFFFFFFu;
+    for (int i = 0; i < 3; ++i) {
+        out[i] = s.p[i];
+        out[3 + i] = traced ? s.dir[i] : 0.0f;
+    }
+    out[6] = traced ? s.dist : 0.0f;
+    out[7] = traced ? s.geom : 0.0f;
     return OCTPT_OK;
 }

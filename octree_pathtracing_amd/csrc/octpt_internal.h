@@ -90,7 +90,11 @@ struct DevScene {
     // its base; octant child = (its base, its child_mask), leaf child = (prim id, 1) or
     // (first leaf prim, prim count)
     const uint2 *node_child;
-    const float4 *leaf_sph;         // parallel to node_child: the sphere of a single-sphere leaf slot
+    // parallel to node_child: the sphere of a single-sphere leaf slot (sphere-only scenes; read by their extend alone).
+    // OVERLOADED: the emitter instances of shade and the drain (C38) are launched with a copy of a block-value
+    // scene whose leaf_sph holds the device address of the render's EmitGrid (csrc/octpt_emitter.h) instead, so
+    // that no kernel argument changes its layout; code that reads leaf_sph in a block scene must not be added
+    const float4 *leaf_sph;
     uint32_t root, root_mask, depth, n_octants;  // root = the root octant's base
     uint32_t has_cuboids;
     float octree_scale;             // 2^-depth
@@ -359,14 +363,19 @@ hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q,
 // smaller than the chunk, finished paths regenerate their slots (the instance with regeneration)
 hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t q,
                            uint32_t chunk_items, uint32_t first, bool regen, int grid, unsigned long long *stats,
-                           hipStream_t stream);
+                           hipStream_t stream, bool emit = false);
+// the emitter instances (C38; octpt_kernels_emit.hip, a module of its own), which launch_wf_shade and launch_wf_drain
+// take with `emit`: S is then a block-value scene whose leaf_sph holds the device address of the render's EmitGrid
+// (csrc/octpt_emitter.h), and the pd planes number six
+const void *emit_shade_kernel(bool nee, bool lds, int mode, bool lens);
+const void *emit_drain_kernel(bool nee);
 // blocks per CU of the shade instance (shade_mode; registers bound it, shade uses no dynamic LDS)
 int shade_blocks_per_cu(const DevScene &S, int mode);
 // whether the scene's shade instance copies the material / texture tables into LDS
 bool shade_lds_tables(const DevScene &S);
 // the drain of a chunk's last queued rays (every chunk item claimed): one launch, paths finished in-lane
 hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuffers &B, uint32_t q, int grid,
-                           unsigned long long *stats, hipStream_t stream);
+                           unsigned long long *stats, hipStream_t stream, bool emit = false);
 // the host's snapshot of an iteration's counters: queue q's kSegs segment counts, then the kSegs item
 // counters, written by one 128-thread block into pinned host memory (enqueue_wavefront's steering)
 hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_out, hipStream_t stream);
@@ -460,6 +469,16 @@ uint64_t pair_bound(const octpt_sphere *spheres, uint32_t ns, const octpt_cuboid
                     uint32_t depth);
 octpt_status section_world_status(const octpt_section_world *w, uint32_t depth);
 
+// The emitter grid (octpt_build_emitter_grid in include/octpt.h): its budgets, the emissive flag of
+// every block (false: a face material outside the table) and the count-then-fill rule of its arrays, which the host
+// builder (octpt_build_host.cpp) and the context's query (octpt_api.cpp) share
+constexpr float kEmitterEpsilon = 5e-8f;  // Ray::EPSILON
+constexpr uint64_t kMaxEmitters = 1ull << 24, kMaxEmitterEntries = 1ull << 28, kMaxEmitterCells = 1ull << 28;
+bool block_emissive_flags(const octpt_block *blocks, uint32_t nb, const octpt_material *mats, uint32_t nm,
+                          std::vector<uint32_t> &out);
+octpt_status emitter_grid_receive(octpt_emitter_grid_arrays *out, uint32_t n_cells, uint32_t n_entries,
+                                  uint32_t n_emitters, uint32_t cells_axis, bool &fill);
+
 // grow-only device scratch of the GPU octree builder, owned by the context: repeated builds
 // (scene edits) reuse it instead of paying hipMalloc / hipFree per buffer
 struct BuildScratch {
@@ -539,6 +558,21 @@ hipError_t fill_scene_gpu(hipStream_t stream, const DeviceOctree &t, const uint3
 // into the scratch.  node_child: n_slots + 8 (the tail zeroed by the caller).
 hipError_t fill_block_scene_gpu(hipStream_t stream, BuildScratch &scratch, const DeviceOctree &t,
                                 const uint32_t *d_base, const uint32_t *bflags, uint32_t n_blocks, uint2 *node_child);
+
+// The emitter grid on the device (octpt_build.hip, C38), from the node slots of a resident block-value scene:
+// a level-by-level walk of the octants (count, scan, fill), the emissive leaves marked and scanned, (Morton code,
+// level) emitted and sorted, the 27-neighbourhood counted per cell, scanned and filled.  The three arrays are
+// device allocations of their own (hipMalloc; the caller frees them), the temporaries the scratch's build slots.
+// d_emissive: block_emissive_flags on the device.  refusal: OCTPT_OK, or OOM (a budget above) / INTERNAL (more
+// octants reached than the scene counts) with nothing allocated.
+struct DeviceEmitterGrid {
+    uint32_t *cell_first = nullptr, *cell_emitters = nullptr;
+    octpt_emitter *emitters = nullptr;
+    uint32_t n_cells = 0, n_entries = 0, n_emitters = 0, cells_axis = 0, grid_shift = 0;
+};
+hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, const DevScene &S,
+                                  const uint32_t *emissive, uint32_t grid_shift, DeviceEmitterGrid &out,
+                                  octpt_status &refusal);
 
 }  // namespace octpt
 

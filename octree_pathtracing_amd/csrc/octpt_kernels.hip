@@ -17,6 +17,7 @@
 // implements as `forward_accumulation`.
 #include "octpt_internal.h"
 #include "octpt_lens.h"
+#include "octpt_emitter.h"
 #include "octpt_rcp.h"
 #include "octpt_reproject.h"
 #include "octpt_resolve_map.h"
@@ -216,6 +217,15 @@ struct PathState {
     float mult;
     v3 co, cd, cn;
     uint32_t clast, ccur;
+#if defined(OCTPT_EMIT_TU)
+    // emitter sampling (C38), the emitter instances' module only (the struct stays what it is everywhere else): a shadow segment with att[3] < 0 is the emitter
+    // segment (att[0..2] = T_before * albedo, mult = the shot's geometric factor, -att[3] = the cell list's length);
+    // a sun sample drawn at the same hit waits behind it in (sd, so, smult) while sun_pend is set; emit_to_sun
+    // marks the shade step that turned the one into the other (its waiting state is stored again)
+    bool sun_pend, emit_to_sun;
+    v3 sd, so;  // the waiting sun sample's direction and origin (the hit point, or OFFSET behind the surface)
+    float smult;
+#endif
 };
 
 struct Esvo {
@@ -1458,6 +1468,98 @@ __device__ inline void shadow_segment_done(const DevScene &S, PathState &ray, bo
     ray.cur = ray.ccur;
 }
 
+// Emitter sampling (strategy ONE): OCTPT_EMIT_TU is defined by octpt_kernels_emit.hip alone, which
+// compiles this text for the emitter instances of the general shade (with its regeneration) and the drain, as a module
+// of its own (see emit_shade_kernel below); everywhere else every line under it is absent and the text is what it was.
+// Such an instance is launched for a block-value scene only, whose DevScene::leaf_sph (the single-sphere leaf table:
+// sphere scenes' alone, never read by shade or a block scene's walk) carries the device address of the render's
+// EmitGrid instead: no struct that a kernel takes changes its layout for the feature.
+#if defined(OCTPT_EMIT_TU)
+__device__ __forceinline__ const EmitGrid &emit_grid_of(const DevScene &S) {
+    return *reinterpret_cast<const EmitGrid *>(S.leaf_sph);
+}
+
+// The emitter sample of a diffuse hit (csrc/octpt_emitter.h), taken before the bounce: false when nothing is to be
+// traced (the caller goes on as without sampling).  Else the bounce -- and with sun sampling the sun sample, drawn in
+// the reference's order: sun direction, subsurface chance, bounce -- is drawn now and waits, and the ray becomes the
+// emitter's shadow segment: one next_intersection from p along dir with the surface's self-hit key.
+template <bool kNee>
+__device__ inline bool emitter_shot(const DevScene &S, const DevMaterial &m, PathState &ray, uint32_t emit_rng) {
+    const EmitGrid &G = emit_grid_of(S);
+    const v3 n = ray.n;
+    const float o[3] = {ray.o.x, ray.o.y, ray.o.z}, nn[3] = {n.x, n.y, n.z};
+    EmitShot sh;
+    if (!emitter_sample(G, o, nn, emit_rng, sh)) return false;
+    v3 &T = ray.T;
+    const float c0 = ray.col[0], c1 = ray.col[1], c2 = ray.col[2];
+    ray.att[0] = T.x * c0;  // T_before * albedo
+    ray.att[1] = T.y * c1;
+    ray.att[2] = T.z * c2;
+    ray.att[3] = -(float)sh.K;
+    ray.sun_pend = false;
+    const uint32_t scur = ray.prev;
+    if (kNee && S.sun.sun_sampling) {
+        const v3 sd = random_sun_direction(S.sun, ray.rng);
+        const bool front = vdot(sd, n) > 0.0f;
+        ray.sun_pend = front || ((m.flags & MAT_FLAG_SUBSURFACE) && rng_next(ray.rng) < S.sun.f_sub_surface);
+        ray.so = front ? ray.o : vadd(ray.o, vscale(n, -RAY_OFFSET));
+        ray.sd = sd;
+        ray.smult = fabsf(vdot(sd, n)) * S.sun.lum_a;
+        const float w = diffuse_reflection(S.sun, ray);
+        T = V(T.x * (c0 * w), T.y * (c1 * w), T.z * (c2 * w));
+    } else {
+        T = V(T.x * c0, T.y * c1, T.z * c2);
+        diffuse_reflection(S.sun, ray);
+    }
+    ray.co = ray.o;
+    ray.cd = ray.d;
+    ray.cn = n;
+    ray.clast = ray.last_prim;
+    ray.ccur = ray.cur;
+    ray.mult = sh.geom;
+    ray.shadow = true;
+    ray.o = V(sh.p[0], sh.p[1], sh.p[2]);
+    ray.d = V(sh.dir[0], sh.dir[1], sh.dir[2]);
+    ray.n = n;
+    ray.cur = scur;
+    return true;
+}
+
+// ... and after that segment: it contributes when it hit a full-cell block leaf (key kPrimNone) whose entered face's
+// material emits and whose texel is not transparent -- any listed emitter, as in Chunky.  Then the waiting sun sample's
+// shadow segments start, or the waiting bounce resumes.
+template <bool kNee>
+__device__ inline void emitter_segment_done(const DevScene &S, PathState &ray, bool hit) {
+    if (hit && ray.last_prim == kPrimNone) {
+        const float emittance = S.mats[ray.cur].emittance;
+        if (emittance > RAY_EPSILON && ray.col[3] > RAY_EPSILON) {
+            const float e = emitter_scale(ray.mult, emittance, emit_grid_of(S).intensity, (uint32_t)(-ray.att[3]));
+            ray.L = V(ray.L.x + ray.att[0] * ((ray.col[0] * ray.col[0]) * e),
+                      ray.L.y + ray.att[1] * ((ray.col[1] * ray.col[1]) * e),
+                      ray.L.z + ray.att[2] * ((ray.col[2] * ray.col[2]) * e));
+        }
+    }
+    if (kNee && ray.sun_pend) {  // the sun sample drawn at the same hit: shade_segment's sun branch from `cast` on
+        ray.mult = ray.smult;
+        ray.att[0] = ray.att[1] = ray.att[2] = ray.att[3] = 1.0f;
+        ray.o = vadd(ray.so, vscale(ray.sd, RAY_OFFSET));
+        ray.d = ray.sd;
+        ray.n = ray.cn;
+        ray.last_prim = ray.clast;
+        ray.cur = ray.prev;
+        ray.sun_pend = false;
+        ray.emit_to_sun = true;
+        return;
+    }
+    ray.shadow = false;
+    ray.o = ray.co;
+    ray.d = ray.cd;
+    ray.n = ray.cn;
+    ray.last_prim = ray.clast;
+    ray.cur = ray.ccur;
+}
+#endif
+
 // path_tracer.rs:15-135 in forward-throughput form, from a finished segment to either the
 // next segment's ray (returns true) or the end of the path (returns false).  kNee: the scene may
 // sample the sun; shadow segments run between a diffuse hit and its bounce.
@@ -1466,10 +1568,18 @@ __device__ inline void shadow_segment_done(const DevScene &S, PathState &ray, bo
 template <bool kNee, bool kLean = false>
 __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, PathState &ray, bool hit,
                                      Counters &cnt) {
+#if defined(OCTPT_EMIT_TU)
+    if (ray.shadow) {
+        if (ray.att[3] < 0.0f) emitter_segment_done<kNee>(S, ray, hit);
+        else shadow_segment_done(S, ray, hit);
+        return true;
+    }
+#else
     if (kNee && ray.shadow) {
         shadow_segment_done(S, ray, hit);
         return true;
     }
+#endif
     if (!hit) {
         float sky[3];
         sky_color(S.sun, ray, sky);
@@ -1492,17 +1602,31 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
     }
     cnt.shade++;
     v3 &T = ray.T;
+#if defined(OCTPT_EMIT_TU)
+    const uint32_t emit_rng = ray.rng;  // the emitter stream's key: the state before any draw of this hit (C38)
+#endif
     const float metal = m.metalness;
     const bool do_metal = metal > RAY_EPSILON && rng_next(ray.rng) < metal;
     if (do_metal || (specular > RAY_EPSILON && rng_next(ray.rng) < specular)) {
         if (do_metal) T = V(T.x * ray.col[0], T.y * ray.col[1], T.z * ray.col[2]);
         specular_reflection(ray, m.roughness);
     } else if (rng_next(ray.rng) < diffuse) {
+        // emitter sampling (C38): own emittance at depth 1 as ever, and dropped at depth > 1 exactly on a full-cell
+        // block leaf (a listed emitter, which the sample reaches; its key is kPrimNone, a quad's is not)
+#if defined(OCTPT_EMIT_TU)
+        if (!kLean && S.emitters && m.emittance > RAY_EPSILON && (ray.depth == 1u || ray.last_prim != kPrimNone)) {
+#else
         if (!kLean && S.emitters && m.emittance > RAY_EPSILON) {
+#endif
             const v3 e = V(ray.col[0] * ray.col[0] * m.emittance, ray.col[1] * ray.col[1] * m.emittance,
                            ray.col[2] * ray.col[2] * m.emittance);
             ray.L = V(ray.L.x + T.x * e.x, ray.L.y + T.y * e.y, ray.L.z + T.z * e.z);
         }
+#if defined(OCTPT_EMIT_TU)
+        if (S.emitters && !(ray.depth == 1u && m.emittance > RAY_EPSILON)) {  // the reference's `else if`
+            if (emitter_shot<kNee>(S, m, ray, emit_rng)) return true;
+        }
+#endif
         if (kNee && S.sun.sun_sampling) {
             // do_diffuse_reflection's sun-sampling branch (path_tracer.rs:225-291).  Draw order:
             // sun direction, subsurface chance, then the bounce; the shadow loop draws nothing,
@@ -1923,6 +2047,21 @@ __device__ __forceinline__ void load_nee(const WaveBuffers &B, uint32_t slot, Pa
     ps.mult = c.w;
     ps.att[0] = d.x; ps.att[1] = d.y; ps.att[2] = d.z; ps.att[3] = d.w;
 }
+
+#if defined(OCTPT_EMIT_TU)
+// a sun sample waiting behind an emitter segment (C38; planes 4 and 5 of pd, allocated for the emitter instances)
+__device__ __forceinline__ void store_sun_pend(const WaveBuffers &B, uint32_t slot, const PathState &ps) {
+    B.pd[4u * B.pool + slot] = make_float4(ps.sd.x, ps.sd.y, ps.sd.z, ps.smult);
+    B.pd[5u * B.pool + slot] = make_float4(ps.so.x, ps.so.y, ps.so.z, ps.sun_pend ? 1.0f : 0.0f);
+}
+__device__ __forceinline__ void load_sun_pend(const WaveBuffers &B, uint32_t slot, PathState &ps) {
+    const float4 a = B.pd[4u * B.pool + slot], b = B.pd[5u * B.pool + slot];
+    ps.sd = V(a.x, a.y, a.z);
+    ps.smult = a.w;
+    ps.so = V(b.x, b.y, b.z);
+    ps.sun_pend = b.w != 0.0f;
+}
+#endif
 
 __device__ __forceinline__ void unpack_path(float4 a, float4 b, uint2 c, float4 r0, float4 r1, PathState &ps,
                                             uint32_t &item) {
@@ -2352,8 +2491,15 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
         cnt.redo++;
         return true;
     }
+#if defined(OCTPT_EMIT_TU)
+    const bool was_shadow = ps.shadow;
+    if (was_shadow) load_nee(B, slot, ps);
+    ps.sun_pend = ps.emit_to_sun = false;
+    if (kNee && was_shadow && ps.att[3] < 0.0f) load_sun_pend(B, slot, ps);
+#else
     const bool was_shadow = kNee && ps.shadow;
     if (was_shadow) load_nee(B, slot, ps);
+#endif
     const bool hit = hr.x != kPrimNone;
     if (hit && (kSP == kPrimsBlocks || (kMayBlocks && S.has_blocks))) {  // block-value leaf (C23): (u, v) beside it
         ps.n = V(0.0f, 0.0f, 0.0f);
@@ -2373,10 +2519,18 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
     if (cont) cont = begin_segment(ps);
     if (cont) {
         if (!kLean) store_path(B, slot, ps, item);
+#if defined(OCTPT_EMIT_TU)
+        if (ps.shadow) {  // a shadow segment follows: a new emitter or sun sample, or the next one
+            if (!was_shadow || ps.emit_to_sun) store_nee(B, slot, ps);
+            store_att(B, slot, ps);
+            if (kNee && !was_shadow && ps.att[3] < 0.0f) store_sun_pend(B, slot, ps);  // (waiting or not)
+        }
+#else
         if (kNee && ps.shadow) {  // a shadow segment follows: new sun sample or the next one
             if (!was_shadow) store_nee(B, slot, ps);
             store_att(B, slot, ps);
         }
+#endif
         return true;
     }
     // segments this item reports (a branch > 0 reports none of the replayed prefix) and whether the
@@ -3581,6 +3735,27 @@ const void *lens_shade_kernel(bool nee, bool lds, int mode) {
     return nee ? (lds ? lens_shade_of<true, true>(mode) : lens_shade_of<true, false>(mode))
                : (lds ? lens_shade_of<false, true>(mode) : lens_shade_of<false, false>(mode));
 }
+#elif defined(OCTPT_EMIT_TU)  // (set by octpt_kernels_emit.hip alone: not a build switch)
+// The emitter instances (C38) of the general shade, with and without regeneration and a lens, and of the block
+// scene's drain, for octpt_kernels_emit.hip, which compiles this text with OCTPT_EMIT_TU for them alone: the instances
+// without emitter sampling stay the code they are.
+template <bool kNee, bool kLds, bool kLens>
+static const void *emit_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kLens>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kLens>);
+}
+template <bool kNee, bool kLds>
+static const void *emit_shade_lens(int mode, bool lens) {
+    return lens ? emit_shade_of<kNee, kLds, true>(mode) : emit_shade_of<kNee, kLds, false>(mode);
+}
+const void *emit_shade_kernel(bool nee, bool lds, int mode, bool lens) {
+    return nee ? (lds ? emit_shade_lens<true, true>(mode, lens) : emit_shade_lens<true, false>(mode, lens))
+               : (lds ? emit_shade_lens<false, true>(mode, lens) : emit_shade_lens<false, false>(mode, lens));
+}
+const void *emit_drain_kernel(bool nee) {
+    return nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
+               : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, false>);
+}
 #else
 
 // ESVO stack levels 1..depth-1 (level 0 is never used, see esvo_step)
@@ -3755,8 +3930,11 @@ static const void *shade_instance_of(int mode, bool first, int prims) {
                      : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0>);
 }
 bool shade_lds_tables(const DevScene &S) { return S.n_mats <= kShadeLdsMats && S.n_texs <= kShadeLdsMats; }
-static const void *shade_instance(const DevScene &S, int mode, bool first = false, bool lens = false) {
+static const void *shade_instance(const DevScene &S, int mode, bool first = false, bool lens = false,
+                                  bool emit = false) {
     const bool lds = shade_lds_tables(S);
+    // emitter sampling (C38): the general instances' emitter twins (such chunks never take the lean state)
+    if (emit) return emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode, lens);
     // a lens camera (C37): the general instances' lens twins (enqueue_wavefront keeps such chunks off the lean state)
     if (lens) return lens_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
     const int prims = S.has_blocks    ? kPrimsBlocks
@@ -3778,20 +3956,20 @@ int shade_blocks_per_cu(const DevScene &S, int mode) {
 
 hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t q,
                            uint32_t chunk_items, uint32_t first, bool regen, int grid, unsigned long long *stats,
-                           hipStream_t stream) {
+                           hipStream_t stream, bool emit) {
     uint32_t first_u = first;
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
                     const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
-    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, C.aperture > 0.0f),
+    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, C.aperture > 0.0f, emit),
                                          dim3(grid), dim3(kBlock), args, 0, stream);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
 hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuffers &B, uint32_t q, int grid,
-                           unsigned long long *stats, hipStream_t stream) {
+                           unsigned long long *stats, hipStream_t stream, bool emit) {
     const bool nee = S.sun.sun_sampling != 0;
-    const void *fn = S.has_blocks ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
+    const void *fn = emit ? emit_drain_kernel(nee) : S.has_blocks ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
                                          : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, false>))
                      : S.has_models ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsModels, true>)
                                          : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsModels, false>))

@@ -114,6 +114,7 @@ class HipRenderer:
         self.max_depth = max_depth
         self.branch_count = 1  # TileRenderer branch count; 1 = one path per sample
         self._scene_keep = None
+        self._scene_emitters = False  # the last set_scene's Scene had emitter sampling on
         self._accum = None
         self._spp = 0
         self._in_flight = None
@@ -178,6 +179,10 @@ class HipRenderer:
     def set_scene(self, scene: Scene) -> None:
         desc, keep = scene.to_desc()
         self._check(self._lib.octpt_scene_upload(self._ctx, C.byref(desc)))
+        # the scene's emitter sampling (C38) is the renderer's from here on: a scene with NONE switches it off
+        if scene.emitter_sampling != _lib.EMITTERS_NONE or self._scene_emitters:
+            self.set_emitter_sampling(scene.emitter_sampling, scene.emitter_grid_size, scene.emitter_intensity)
+        self._scene_emitters = scene.emitter_sampling != _lib.EMITTERS_NONE
         self._scene_keep = keep
         self.reset_render()
 
@@ -664,6 +669,20 @@ class HipRenderer:
             C.c_void_p(d_seg_count) if d_seg_count else None, tile_spp.ctypes.data_as(C.c_void_p), C.byref(res),
             C.c_void_p(stream) if stream else None))
         return tile_spp, res.as_dict()
+
+    # ------------------------------------------------------------ emitter sampling (C38)
+    def set_emitter_sampling(self, strategy: int, grid_size: int = 8, intensity: float = 1.0) -> None:
+        """Scene::emitter_sampling_strategy and emmitter_intensity (octpt_set_emitter_sampling): _lib.EMITTERS_NONE or
+        _lib.EMITTERS_ONE, the emitter grid's cell side in voxels and the intensity, for every later render.  With
+        ONE and a block-value scene this GPU builds the emitter grid (emitter_grid)."""
+        self._check(self._lib.octpt_set_emitter_sampling(
+            self._ctx, C.byref(_lib.EmitterParams(int(strategy), int(grid_size), float(intensity)))))
+
+    def emitter_grid(self) -> dict:
+        """The emitter grid this GPU built (octpt_emitter_grid), as scene.build_emitter_grid returns the host's."""
+        from .scene import take_emitter_grid
+
+        return take_emitter_grid(lambda g: self._check(self._lib.octpt_emitter_grid(self._ctx, C.byref(g))))
 
     # ------------------------------------------------------------ final-quality adaptive frames (C33-C36)
     def set_sample_clamp(self, max_luminance: float) -> None:

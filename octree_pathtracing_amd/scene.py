@@ -304,6 +304,11 @@ class Scene:
     blocks: np.ndarray | None = None
     block_model: np.ndarray | None = None
     cells: np.ndarray | None = None
+    # emitter sampling (Scene::emitter_sampling_strategy and emmitter_intensity, scene/mod.rs:5-58):
+    # _lib.EMITTERS_NONE leaves every render as it is; HipRenderer.set_scene applies the three
+    emitter_sampling: int = _lib.EMITTERS_NONE
+    emitter_grid_size: int = 8
+    emitter_intensity: float = 1.0
 
     # ---------------------------------------------------------------- octree
     def build_octree(self, depth: int, renderer=None, compact: bool = False, device_cells=None,
@@ -420,6 +425,12 @@ class Scene:
             out._depth = self._depth
         return out
 
+    def material_structs(self):
+        """octpt_material rows of `materials`."""
+        return (_lib.Material * len(self.materials))(*[
+            _lib.Material(m.ior, m.specular, m.emittance, m.roughness, m.metalness, m.texture_index, m.tint_index, m.flags)
+            for m in self.materials])
+
     def block_structs(self):
         """octpt_block rows of `blocks` / `block_model` (C23)."""
         n = len(self.blocks)
@@ -534,6 +545,64 @@ class Scene:
             desc.block_count = len(self.blocks)
         keep.extend([mats, texs])
         return desc, keep
+
+
+def take_emitter_grid(call) -> dict:
+    """The emitter grid of a count-then-fill entry (call(arrays) -> status checked by the caller): counts first,
+    then the arrays.  Returns cell_first, cell_emitters, emitters (n, 4: x, y, z, s) and cells_per_axis."""
+    g = _lib.EmitterGridArrays()
+    call(g)
+    first = np.zeros(g.cell_count + 1, np.uint32)
+    entries = np.zeros(max(g.entry_count, 1), np.uint32)
+    emitters = np.zeros((max(g.emitter_count, 1), 4), np.uint32)
+    g.cell_first, g.cell_first_capacity = first.ctypes.data, len(first)
+    g.cell_emitters, g.cell_emitters_capacity = entries.ctypes.data, len(entries)
+    g.emitters, g.emitters_capacity = emitters.ctypes.data, len(emitters)
+    call(g)
+    return {"cell_first": first, "cell_emitters": entries[: g.entry_count], "emitters": emitters[: g.emitter_count],
+            "cells_per_axis": int(g.cells_per_axis)}
+
+
+def build_emitter_grid(scene: Scene, depth: int, grid_size: int, compact: bool = False) -> dict:
+    """The emitter grid of a block-value scene's cells on the host (octpt_build_emitter_grid, the grid's definition,
+    DESIGN.md C38): see take_emitter_grid for the result."""
+    if scene.blocks is None:
+        raise ValueError("build_emitter_grid: a block-value scene (scene.blocks) is needed")
+    lib = _lib.load()
+    cells, blocks, mats = scene.cells_array(), scene.block_structs(), scene.material_structs()
+
+    def call(g):
+        _lib.check(lib, None, lib.octpt_build_emitter_grid(
+            cells.ctypes.data_as(C.c_void_p) if len(cells) else None, len(cells), C.cast(blocks, C.c_void_p),
+            len(scene.blocks), C.cast(mats, C.c_void_p), len(scene.materials), depth,
+            _lib.BUILD_COMPACT if compact else 0, grid_size, C.byref(g)))
+
+    return take_emitter_grid(call)
+
+
+def emitter_sample(grid: dict, depth: int, grid_size: int, hit, normal, rng_state: int) -> dict:
+    """octpt_emitter_sample: the emitter sample of one diffuse hit as the emitter instances of shade take it
+    (csrc/octpt_emitter.h; host-only).  grid: a build_emitter_grid / HipRenderer.emitter_grid result.  Returns p, dir
+    (f32 [3]), dist, geom, K (the hit's cell list's length) and emitter (index into grid["emitters"], None when no
+    segment is traced)."""
+    lib = _lib.load()
+    first = np.ascontiguousarray(grid["cell_first"], np.uint32)
+    entries = np.ascontiguousarray(grid["cell_emitters"], np.uint32)
+    emitters = np.ascontiguousarray(grid["emitters"], np.uint32).reshape(-1, 4)
+    pad = np.zeros(4, np.uint32)  # an empty array still needs an address
+    g = _lib.EmitterGridArrays()
+    g.cell_first, g.cell_first_capacity = first.ctypes.data, len(first)
+    g.cell_emitters, g.cell_emitters_capacity = (entries if len(entries) else pad).ctypes.data, len(entries)
+    g.emitters, g.emitters_capacity = (emitters if len(emitters) else pad).ctypes.data, len(emitters)
+    g.cell_count, g.entry_count, g.emitter_count = len(first) - 1, len(entries), len(emitters)
+    g.cells_per_axis = int(grid["cells_per_axis"])
+    h, n = np.ascontiguousarray(hit, F32), np.ascontiguousarray(normal, F32)
+    out, em, K = np.zeros(8, F32), C.c_uint32(), C.c_uint32()
+    _lib.check(lib, None, lib.octpt_emitter_sample(C.byref(g), depth, grid_size, h.ctypes.data_as(C.c_void_p),
+                                                   n.ctypes.data_as(C.c_void_p), int(rng_state) & 0xFFFFFFFF,
+                                                   out.ctypes.data_as(C.c_void_p), C.byref(em), C.byref(K)))
+    return {"p": out[:3].copy(), "dir": out[3:6].copy(), "dist": float(out[6]), "geom": float(out[7]),
+            "K": int(K.value), "emitter": None if em.value == 0xFFFFFFFF else int(em.value)}
 
 
 @dataclass
