@@ -868,7 +868,8 @@ octpt_status octpt_scene_build_sections_device(octpt_ctx *ctx, const octpt_scene
  * Block-value worlds only.  An emitter is a leaf of the block octree, at any level, whose block has
  * model == OCTPT_MODEL_NONE and at least one face material with emittance > EPSILON (5e-8); a leaf of side
  * s = 2^k (a LOD or compacted leaf) is one emitter (x, y, z, s): its minimum corner and its side.  Block-model
- * leaves are not listed.  The grid has cells of grid_size voxels per side (a power of two, 1 .. 2^depth),
+ * leaves are listed only with OCTPT_EMITTERS_MODELS (C39, below).  The grid has cells of grid_size voxels per side
+ * (a power of two, 1 .. 2^depth),
  * cells_per_axis = 2^depth / grid_size per axis, cell (cx, cy, cz) at index cx + cells_per_axis * (cy +
  * cells_per_axis * cz).  An emitter's home cell is (x, y, z) / grid_size; the list of cell c holds every emitter
  * whose home cell is within Chebyshev distance 1 of c, in ascending Morton code of (x, y, z) (x bit 0, y bit 1,
@@ -899,11 +900,51 @@ octpt_status octpt_build_emitter_grid(const uint32_t *cells, uint32_t cell_count
                                       uint32_t block_count, const octpt_material *materials, uint32_t material_count,
                                       uint32_t depth, uint32_t flags, uint32_t grid_size,
                                       octpt_emitter_grid_arrays *out);
+/* --- emissive block models as emitters: torches, lanterns, candles ---
+ * The emissive-model table.  The emissive quads of model m are the quads of [first_quad, first_quad + quad_count)
+ * whose material has emittance > EPSILON (5e-8) and whose area a = |u x v| is finite and > 0, in table order; the
+ * area in plain f32 without contraction, each cross component a * b - c * d, the length sqrtf((x^2 + y^2) + z^2).
+ * model m's entries are [model_first[m], model_first[m + 1]): quad_index[] the quad, cum_area[] the running f32 sum
+ * of the areas within the model, in order; A_m, the model's emissive area, is its last cum_area, and a model is
+ * emissive when it has an entry.  Count-then-fill as octpt_emitter_grid_arrays: the two counts are always received
+ * (0 on an error); the three pointers NULL: the call only counts; else all three set with capacities (in elements)
+ * of model_count + 1, entry_count, entry_count, or nothing is written and the call is INVALID_ARG. */
+typedef struct octpt_emitter_model_arrays {
+    uint32_t *model_first;
+    uint32_t model_first_capacity;
+    uint32_t *quad_index;
+    uint32_t quad_index_capacity;
+    float *cum_area;
+    uint32_t cum_area_capacity;
+    uint32_t model_count, entry_count;
+} octpt_emitter_model_arrays;
+/* The definition of the table.  Host-only, no context.  INVALID_ARG: a model whose quad range leaves the quad table,
+ * a quad of a model with material >= material_count, count-then-fill misuse. */
+octpt_status octpt_emitter_model_table(const octpt_block_model *models, uint32_t model_count, const octpt_quad *quads,
+                                       uint32_t quad_count, const octpt_material *materials, uint32_t material_count,
+                                       octpt_emitter_model_arrays *out);
+/* Flags of emitter sampling (octpt_emitter_params.flags, octpt_build_emitter_grid_models' emitter_flags).
+ * OCTPT_EMITTERS_MODELS: a leaf at any level whose block has model != OCTPT_MODEL_NONE and an emissive model is an
+ * emitter too, with the record (x, y, z, 0x80000000 | model): the leaf's minimum corner, where C23 draws the model in
+ * unit-voxel coordinates whatever the leaf's level.  A cube emitter keeps s = 2^k, so the top bit of the fourth word
+ * tells the two kinds apart. */
+#define OCTPT_EMITTERS_MODELS 0x1u
+/* octpt_build_emitter_grid with the model and quad tables and the flags above: with emitter_flags 0 it equals
+ * octpt_build_emitter_grid array for array (the two tables are not read).  INVALID_ARG besides: an emitter flag
+ * other than OCTPT_EMITTERS_MODELS, and with it what octpt_emitter_model_table refuses, a block's model >=
+ * model_count, model_count above 2^31 - 1. */
+octpt_status octpt_build_emitter_grid_models(const uint32_t *cells, uint32_t cell_count, const octpt_block *blocks,
+                                             uint32_t block_count, const octpt_material *materials,
+                                             uint32_t material_count, const octpt_block_model *models,
+                                             uint32_t model_count, const octpt_quad *quads, uint32_t quad_count,
+                                             uint32_t depth, uint32_t flags, uint32_t grid_size, uint32_t emitter_flags,
+                                             octpt_emitter_grid_arrays *out);
 /* Emitter sampling (Scene::emitter_sampling_strategy and emmitter_intensity, scene/mod.rs:5-58).  The default is
  * NONE, with which every render is what it is without this call.  ONE_BLOCK and ALL have their values reserved and
  * are UNSUPPORTED, as is every other strategy value.  grid_size: a power of two, 1 .. 2^21, and with ONE on a
- * context that holds a scene at most 2^depth; intensity finite and >= 0; reserved words 0: else INVALID_ARG and
- * the setting stays.  ONE on a context whose scene has primitive leaves is UNSUPPORTED.  Like
+ * context that holds a scene at most 2^depth; intensity finite and >= 0; flags 0 or OCTPT_EMITTERS_MODELS (C39;
+ * accepted and without meaning under NONE; under ONE a change of it rebuilds the grid, and with it a scene of more
+ * than 2^31 - 1 models is INVALID_ARG); reserved words 0: else INVALID_ARG and the setting stays.  ONE on a context whose scene has primitive leaves is UNSUPPORTED.  Like
  * octpt_set_sample_clamp the call joins a frame in flight, holds for later renders and is read when a render call
  * is made.  It may come before or after the scene: with ONE and a block-value scene both known, the context's
  * device builds the grid from the octree resident there (after octpt_scene_upload, octpt_scene_build_blocks_device
@@ -920,7 +961,13 @@ octpt_status octpt_build_emitter_grid(const uint32_t *cells, uint32_t cell_count
  * target in its cube, and one shadow segment is traced (counted like the sun's); when it hits a full-cell block leaf
  * whose entered face emits and is not transparent there, L += T * albedo * col_e^2 * (|dir.n| / max(dist^2, 1) *
  * emittance_e * intensity * K).  The factor K makes ONE an unbiased pick over the list: a deliberate choice.  With sun
- * sampling the emitter segment runs first, then the sun's, then the bounce. */
+ * sampling the emitter segment runs first, then the sun's, then the bounce.
+ * With OCTPT_EMITTERS_MODELS (C39) a picked model emitter's target is a point of one of its model's emissive quads,
+ * the quad picked in proportion to its area -- the first i of the model's entries with u1 * A_m < cum_area[i], the
+ * last one else -- and t = ((origin + u * u2) + v * u3) + corner per component; the factor is (|dir.n| / max(dist^2,
+ * 1)) * A_m, Chunky's face-area form.  The segment then also contributes when it hits a block-model quad whose
+ * material emits and whose texel's alpha is above EPSILON, and own emittance at depth > 1 is dropped on every
+ * emissive hit, quads included: every emissive surface of the scene is listed. */
 #define OCTPT_EMITTERS_NONE 0u
 #define OCTPT_EMITTERS_ONE 1u
 #define OCTPT_EMITTERS_ONE_BLOCK 2u /* reserved */
@@ -929,13 +976,19 @@ typedef struct octpt_emitter_params {
     uint32_t strategy;
     uint32_t grid_size;
     float intensity;
-    uint32_t reserved[5];
+    uint32_t flags; /* OCTPT_EMITTERS_MODELS or 0 */
+    uint32_t reserved[4];
 } octpt_emitter_params;
 octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_params *params);
 /* The context's device grid, copied back in count-then-fill form (the rules of octpt_emitter_grid_arrays).  With
  * NONE, or no block-value scene, the context holds no grid: INVALID_ARG.  On a multi-device context the first
  * entry's replica. */
 octpt_status octpt_emitter_grid(octpt_ctx *ctx, octpt_emitter_grid_arrays *out);
+/* The emissive-model table the context's device holds beside its grid (built on the host at the scene entry with
+ * octpt_emitter_model_table's arithmetic and uploaded once per scene), copied back in count-then-fill form.  The
+ * context holds it when it holds a grid built with OCTPT_EMITTERS_MODELS: INVALID_ARG else.  On a multi-device
+ * context the first entry's replica. */
+octpt_status octpt_emitter_models(octpt_ctx *ctx, octpt_emitter_model_arrays *out);
 
 /* The emitter sample of one diffuse hit as the emitter instances take it (csrc/octpt_emitter.h, the text they compile):
  * host-only.  grid: filled arrays of a grid of this depth and grid_size; rng_state: the path's RNG state before any
@@ -945,6 +998,15 @@ octpt_status octpt_emitter_grid(octpt_ctx *ctx, octpt_emitter_grid_arrays *out);
 octpt_status octpt_emitter_sample(const octpt_emitter_grid_arrays *grid, uint32_t depth, uint32_t grid_size,
                                   const float hit[3], const float normal[3], uint32_t rng_state, float out[8],
                                   uint32_t *emitter, uint32_t *list_length);
+/* ... over a grid that lists model emitters (C39): table and quads are the filled emissive-model table and the quad
+ * table it indexes (INVALID_ARG: a record's model outside the table or without entries, an entry's quad outside the
+ * quad table); *quad is the picked quad's index into quads[], or 0xFFFFFFFF for a cube emitter or no segment.  A
+ * cube emitter is sampled as octpt_emitter_sample samples it, draw for draw; out[7] carries A_m for a model. */
+octpt_status octpt_emitter_sample_models(const octpt_emitter_grid_arrays *grid, const octpt_emitter_model_arrays *table,
+                                         const octpt_quad *quads, uint32_t quad_count, uint32_t depth,
+                                         uint32_t grid_size, const float hit[3], const float normal[3],
+                                         uint32_t rng_state, float out[8], uint32_t *emitter, uint32_t *list_length,
+                                         uint32_t *quad);
 
 octpt_status octpt_octree_get_view(const octpt_octree *tree, octpt_octree_view *view);
 void octpt_octree_free(octpt_octree *tree);

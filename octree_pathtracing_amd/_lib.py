@@ -111,13 +111,29 @@ class EmitterGridArrays(C.Structure):
                 ("cells_per_axis", C.c_uint32)]
 
 
+class _EmitterParamsTail(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved_tail", C.c_uint32 * 4)]
+
+
 class EmitterParams(C.Structure):
-    """octpt_emitter_params (octpt_set_emitter_sampling)."""
+    """octpt_emitter_params (octpt_set_emitter_sampling).  `reserved` views the five words after intensity, whose
+    first is `flags` (EMITTERS_MODELS) and whose other four are reserved."""
+    _anonymous_ = ("_tail",)
     _fields_ = [("strategy", C.c_uint32), ("grid_size", C.c_uint32), ("intensity", C.c_float),
-                ("reserved", C.c_uint32 * 5)]
+                ("_tail", type("_EmitterParamsWords", (C.Union,), {
+                    "_anonymous_": ("_named",),
+                    "_fields_": [("reserved", C.c_uint32 * 5), ("_named", _EmitterParamsTail)]}))]
+
+
+class EmitterModelArrays(C.Structure):
+    """octpt_emitter_model_arrays: the emissive-model table's three arrays, count-then-fill."""
+    _fields_ = [("model_first", C.c_void_p), ("model_first_capacity", C.c_uint32), ("quad_index", C.c_void_p),
+                ("quad_index_capacity", C.c_uint32), ("cum_area", C.c_void_p), ("cum_area_capacity", C.c_uint32),
+                ("model_count", C.c_uint32), ("entry_count", C.c_uint32)]
 
 
 EMITTERS_NONE, EMITTERS_ONE, EMITTERS_ONE_BLOCK, EMITTERS_ALL = 0, 1, 2, 3
+EMITTERS_MODELS = 1  # octpt_emitter_params.flags: emissive block models are emitters too (C39)
 
 
 # numpy view of octpt_section rows (scene.SectionWorld.sections)
@@ -401,6 +417,13 @@ SIGNATURES = {
     "octpt_emitter_sample": (_i32, [C.POINTER(EmitterGridArrays), _u32, _u32, _vp, _vp, _u32, _vp, C.POINTER(_u32),
                                     C.POINTER(_u32)]),
     "octpt_emitter_grid": (_i32, [_vp, C.POINTER(EmitterGridArrays)]),
+    "octpt_emitter_model_table": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(EmitterModelArrays)]),
+    "octpt_build_emitter_grid_models": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32,
+                                               _u32, C.POINTER(EmitterGridArrays)]),
+    "octpt_emitter_models": (_i32, [_vp, C.POINTER(EmitterModelArrays)]),
+    "octpt_emitter_sample_models": (_i32, [C.POINTER(EmitterGridArrays), C.POINTER(EmitterModelArrays), _vp, _u32, _u32,
+                                           _u32, _vp, _vp, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32),
+                                           C.POINTER(_u32)]),
     "octpt_sections_to_cells": (_i32, [C.POINTER(SectionWorld), _u32, _vp, _u32, C.POINTER(_u32)]),
     "octpt_build_block_octree_sections_device": (_i32, [_vp, C.POINTER(SectionWorld), _u32, _u32, C.POINTER(_vp)]),
     "octpt_scene_build_sections_device": (_i32, [_vp, C.POINTER(SceneDesc), C.POINTER(SectionWorld), _u32]),

@@ -203,7 +203,15 @@ struct octpt_ctx {
     // both known (grid_valid; its three arrays are allocations of their own)
     uint32_t emit_strategy = OCTPT_EMITTERS_NONE, emit_grid_size = 8u;
     float emit_intensity = 1.0f;
+    uint32_t emit_flags = 0u;  // OCTPT_EMITTERS_MODELS (C39)
     std::vector<uint32_t> block_emissive;
+    // model emitters (C39): the scene's emissive-model table, built on the host at the scene entry, its emissive
+    // byte per model, and the table on the device (scene allocations, uploaded once per scene when a grid with
+    // OCTPT_EMITTERS_MODELS is first built)
+    EmissiveModelTable emit_models;
+    std::vector<uint8_t> model_emissive;
+    uint32_t *d_model_first = nullptr, *d_model_quad = nullptr;
+    float *d_model_cum = nullptr, *d_model_ouv = nullptr;
     DeviceEmitterGrid emit_grid;
     bool grid_valid = false;
     EmitGrid *d_emit_hdr = nullptr;  // the render's EmitGrid on the device (the emitter instances' S.leaf_sph)
@@ -335,6 +343,8 @@ void free_scene(octpt_ctx *ctx) {
     drop_emitter_grid(ctx);
     for (void *p : ctx->scene_allocs) (void)hipFree(p);
     ctx->scene_allocs.clear();
+    ctx->d_model_first = ctx->d_model_quad = nullptr;
+    ctx->d_model_cum = ctx->d_model_ouv = nullptr;
     ctx->has_scene = false;
 }
 
@@ -686,6 +696,15 @@ octpt_status upload_tables(octpt_ctx *ctx, const octpt_scene_desc *d, bool host_
     ctx->lean_scene = !emissive && !d->sun.sun_sampling;
     ctx->block_emissive.clear();  // (validate_tables checked every face material)
     if (d->blocks) block_emissive_flags(d->blocks, d->block_count, d->materials, d->material_count, ctx->block_emissive);
+    // ... and the emissive-model table (C39; validate_tables checked the quad ranges, the quad materials and every
+    // block's model)
+    ctx->emit_models = EmissiveModelTable{};
+    ctx->model_emissive.clear();
+    if (d->blocks && d->model_count) {
+        emissive_model_table(d->models, d->model_count, d->quads, d->quad_count, d->materials, d->material_count,
+                             ctx->emit_models);
+        ctx->model_emissive = model_emissive_bytes(ctx->emit_models);
+    }
     return OCTPT_OK;
 }
 
@@ -1028,8 +1047,11 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         const DeviceEmitterGrid &g = ctx->emit_grid;
         uint32_t axis_bits = 0;
         while ((1u << axis_bits) < g.cells_axis) ++axis_bits;
+        const bool models = (g.flags & OCTPT_EMITTERS_MODELS) != 0u;  // C39: the table beside the grid
         const EmitGrid hdr{g.cell_first, g.cell_emitters, g.emitters, g.grid_shift, axis_bits, 1u << ctx->S.depth,
-                           ctx->emit_intensity};
+                           ctx->emit_intensity, g.flags, 0u,
+                           models ? ctx->d_model_first : nullptr, models ? ctx->d_model_quad : nullptr,
+                           models ? ctx->d_model_cum : nullptr, models ? ctx->d_model_ouv : nullptr};
         if (!ctx->d_emit_hdr) HIP_TRY(ctx, hipMalloc(&ctx->d_emit_hdr, sizeof(EmitGrid)));
         if (!ctx->emit_hdr_valid || std::memcmp(&ctx->emit_hdr_host, &hdr, sizeof hdr) != 0) {
             // a new grid or intensity: an earlier render (on any stream) may still read the old header
@@ -1520,9 +1542,28 @@ octpt_status refresh_emitter_grid(octpt_ctx *ctx) {
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "the emitter grid's grid_size exceeds the world's 2^depth");
     uint32_t shift = 0;
     while ((1u << shift) < ctx->emit_grid_size) ++shift;
+    // model emitters (C39): the table goes to the device with the first such grid of the scene
+    const bool models = (ctx->emit_flags & OCTPT_EMITTERS_MODELS) != 0u;
+    if (models && ctx->model_emissive.size() > 0x7FFFFFFFull)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "OCTPT_EMITTERS_MODELS: more than 2^31 - 1 models");
+    if (models && !ctx->d_model_first) {
+        const EmissiveModelTable &t = ctx->emit_models;
+        const uint32_t none = 0u;  // a scene without models: first[] = {0}
+        hipError_t eu = t.first.empty() ? upload(ctx, &none, 1, &ctx->d_model_first)
+                                        : upload(ctx, t.first.data(), t.first.size(), &ctx->d_model_first);
+        if (eu == hipSuccess) eu = upload(ctx, t.quad.data(), t.quad.size(), &ctx->d_model_quad);
+        if (eu == hipSuccess) eu = upload(ctx, t.cum.data(), t.cum.size(), &ctx->d_model_cum);
+        if (eu == hipSuccess) eu = upload(ctx, t.ouv.data(), t.ouv.size(), &ctx->d_model_ouv);
+        if (eu != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_model_first = nullptr;  // (the allocations made stay the scene's and go with it)
+            return hip_fail(ctx, eu, "emissive-model table upload");
+        }
+    }
     octpt_status refusal = OCTPT_OK;
     const hipError_t e = build_emitter_grid_gpu(ctx->stream, ctx->build_scratch, ctx->S, ctx->block_emissive.data(), shift,
-                                                ctx->emit_grid, refusal);
+                                                ctx->emit_grid, refusal, models ? ctx->model_emissive.data() : nullptr,
+                                                models ? (uint32_t)ctx->model_emissive.size() : 0u);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return hip_fail(ctx, e, "emitter grid build");
@@ -1530,6 +1571,7 @@ octpt_status refresh_emitter_grid(octpt_ctx *ctx) {
     if (refusal == OCTPT_ERR_OOM)
         return fail(ctx, OCTPT_ERR_OOM, "the emitter grid exceeds its budget (2^24 emitters, 2^28 list entries, 2^28 cells)");
     if (refusal != OCTPT_OK) return fail(ctx, refusal, "emitter grid build: the scene holds more octants than it counts");
+    ctx->emit_grid.flags = ctx->emit_flags;
     ctx->grid_valid = true;
     return OCTPT_OK;
 }
@@ -3291,6 +3333,8 @@ octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_para
     if (p->strategy == OCTPT_EMITTERS_ONE_BLOCK || p->strategy == OCTPT_EMITTERS_ALL)
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "emitter sampling strategies ONE_BLOCK and ALL are reserved (DESIGN.md C38)");
     if (p->strategy > OCTPT_EMITTERS_ALL) return fail(ctx, OCTPT_ERR_UNSUPPORTED, "unknown emitter sampling strategy");
+    if (p->flags & ~OCTPT_EMITTERS_MODELS)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter params: unknown flag (OCTPT_EMITTERS_MODELS is the only one)");
     for (uint32_t r : p->reserved)
         if (r) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter params: reserved words must be 0");
     if (!(p->intensity >= 0.0f) || !std::isfinite(p->intensity))
@@ -3305,11 +3349,12 @@ octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_para
         if (p->grid_size > (1u << sc->S.depth))
             return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter grid_size exceeds the world's 2^depth");
     }
-    const uint32_t old_strategy = ctx->emit_strategy, old_size = ctx->emit_grid_size;
+    const uint32_t old_strategy = ctx->emit_strategy, old_size = ctx->emit_grid_size, old_flags = ctx->emit_flags;
     const float old_intensity = ctx->emit_intensity;
     ctx->emit_strategy = p->strategy;
     ctx->emit_grid_size = p->grid_size;
     ctx->emit_intensity = p->intensity;
+    ctx->emit_flags = p->flags;
     octpt_status st = OCTPT_OK;
     if (is_multi(ctx)) {
         for (octpt_ctx *sc : ctx->sub) {
@@ -3319,7 +3364,8 @@ octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_para
                 break;
             }
         }
-    } else if (old_strategy != p->strategy || old_size != p->grid_size) {
+    } else if (old_strategy != p->strategy || old_size != p->grid_size ||
+               (p->strategy == OCTPT_EMITTERS_ONE && old_flags != p->flags)) {  // (under NONE the flag means nothing)
         const hipError_t e = hipSetDevice(ctx->device);
         st = e != hipSuccess ? hip_fail(ctx, e, "hipSetDevice") : OCTPT_OK;
         if (st == OCTPT_OK && ctx->has_scene) {
@@ -3332,11 +3378,13 @@ octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_para
         ctx->emit_strategy = old_strategy;
         ctx->emit_grid_size = old_size;
         ctx->emit_intensity = old_intensity;
+        ctx->emit_flags = old_flags;
         if (is_multi(ctx)) {  // every entry back to the old setting, those that had taken the new one included
             octpt_emitter_params old{};
             old.strategy = old_strategy;
             old.grid_size = old_size;
             old.intensity = old_intensity;
+            old.flags = old_flags;
             for (octpt_ctx *sc : ctx->sub) (void)octpt_set_emitter_sampling(sc, &old);
         } else if (ctx->has_scene) {
             (void)refresh_emitter_grid(ctx);
@@ -3369,6 +3417,32 @@ octpt_status octpt_emitter_grid(octpt_ctx *ctx, octpt_emitter_grid_arrays *out) 
         HIP_TRY(ctx, hipMemcpy(out->cell_emitters, g.cell_emitters, (size_t)g.n_entries * 4, hipMemcpyDeviceToHost));
     if (g.n_emitters)
         HIP_TRY(ctx, hipMemcpy(out->emitters, g.emitters, (size_t)g.n_emitters * sizeof(octpt_emitter), hipMemcpyDeviceToHost));
+    return OCTPT_OK;
+}
+
+octpt_status octpt_emitter_models(octpt_ctx *ctx, octpt_emitter_model_arrays *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter model arrays NULL");
+    out->model_count = out->entry_count = 0u;
+    join_inflight(ctx);
+    if (is_multi(ctx)) {
+        const octpt_status st = octpt_emitter_models(ctx->sub[0], out);
+        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
+    }
+    if (!ctx->grid_valid || !(ctx->emit_grid.flags & OCTPT_EMITTERS_MODELS) || !ctx->d_model_first)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "the context holds no emissive-model table (a grid built with OCTPT_EMITTERS_MODELS holds one)");
+    const uint32_t n_models = (uint32_t)ctx->model_emissive.size(), n_entries = (uint32_t)ctx->emit_models.quad.size();
+    bool fill = false;
+    const octpt_status st = emitter_models_receive(out, n_models, n_entries, fill);
+    if (st != OCTPT_OK) return fail(ctx, st, "emitter models: set all three arrays, each with the capacity of its count");
+    if (!fill) return OCTPT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(out->model_first, ctx->d_model_first, ((size_t)n_models + 1u) * 4, hipMemcpyDeviceToHost));
+    if (n_entries) {
+        HIP_TRY(ctx, hipMemcpy(out->quad_index, ctx->d_model_quad, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->cum_area, ctx->d_model_cum, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+    }
     return OCTPT_OK;
 }
 

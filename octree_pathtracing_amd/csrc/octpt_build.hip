@@ -1198,8 +1198,11 @@ __global__ __launch_bounds__(kBuildBlock) void walk_fill_kernel(const uint2 *__r
     }
 }
 
-// emissive leaf children of table entry k (cnt[n] = 0), or with kFill their (Morton code, level) from offs[k]
-template <bool kFill>
+// emissive leaf children of table entry k (cnt[n] = 0), or with kFill their (Morton code, level) from offs[k].
+// kModels (C39, OCTPT_EMITTERS_MODELS): a leaf whose block has a model with its emissive byte set is an emitter too,
+// and carries kModelRecord | model in place of its level: the record's fourth word, through the sort.
+constexpr uint32_t kModelRecord = 0x80000000u;
+template <bool kFill, bool kModels>
 __global__ __launch_bounds__(kBuildBlock) void leaf_emitters_kernel(const uint2 *__restrict__ node_child,
                                                                     const uint32_t *__restrict__ oc_base,
                                                                     const uint32_t *__restrict__ oc_mask,
@@ -1209,7 +1212,10 @@ __global__ __launch_bounds__(kBuildBlock) void leaf_emitters_kernel(const uint2 
                                                                     uint32_t *__restrict__ cnt,
                                                                     const uint32_t *__restrict__ offs,
                                                                     uint64_t *__restrict__ keys,
-                                                                    uint32_t *__restrict__ levels, uint32_t n_keys) {
+                                                                    uint32_t *__restrict__ levels, uint32_t n_keys,
+                                                                    const uint32_t *__restrict__ blk_model,
+                                                                    const uint8_t *__restrict__ model_emissive,
+                                                                    uint32_t n_models) {
     const uint32_t k = blockIdx.x * kBuildBlock + threadIdx.x;
     if (k > n || (kFill && k == n)) return;
     uint32_t found = 0u;
@@ -1222,12 +1228,19 @@ __global__ __launch_bounds__(kBuildBlock) void leaf_emitters_kernel(const uint2 
             const uint32_t r = rank++;
             if (!((m >> (i + 8u)) & 1u)) continue;
             const uint32_t block = node_child[base + r].x;
-            if (block >= n_blocks || !emissive[block]) continue;
+            if (block >= n_blocks) continue;
+            uint32_t word = lv + 1u;
+            if (!emissive[block]) {
+                if (!kModels) continue;
+                const uint32_t mdl = blk_model[block];  // (OCTPT_MODEL_NONE is no index of the table)
+                if (mdl >= n_models || !model_emissive[mdl]) continue;
+                word = kModelRecord | mdl;
+            }
             if (kFill) {
                 const uint32_t dst = offs[k] + found;
                 if (dst < n_keys) {
                     keys[dst] = oc_code[k] | ((uint64_t)i << shift);
-                    levels[dst] = lv + 1u;
+                    levels[dst] = word;
                 }
             }
             ++found;
@@ -1236,6 +1249,7 @@ __global__ __launch_bounds__(kBuildBlock) void leaf_emitters_kernel(const uint2 
     if (!kFill) cnt[k] = found;
 }
 
+template <bool kModels>
 __global__ __launch_bounds__(kBuildBlock) void emitter_records_kernel(const uint64_t *__restrict__ keys,
                                                                       const uint32_t *__restrict__ levels, uint32_t n,
                                                                       uint32_t depth, octpt_emitter *__restrict__ out) {
@@ -1246,7 +1260,8 @@ __global__ __launch_bounds__(kBuildBlock) void emitter_records_kernel(const uint
     e.x = compact_by_2(c);
     e.y = compact_by_2(c >> 1);
     e.z = compact_by_2(c >> 2);
-    e.s = 1u << (depth - levels[k]);
+    const uint32_t word = levels[k];
+    e.s = (kModels && (word & kModelRecord)) ? word : 1u << (depth - word);
     out[k] = e;
 }
 
@@ -1320,7 +1335,7 @@ hipError_t scan_u32(hipStream_t stream, char *d_tmp, size_t tmp_bytes, const uin
 
 hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, const DevScene &S,
                                   const uint32_t *emissive, uint32_t grid_shift, DeviceEmitterGrid &out,
-                                  octpt_status &refusal) {
+                                  octpt_status &refusal, const uint8_t *model_emissive, uint32_t n_models) {
     out = DeviceEmitterGrid{};
     refusal = OCTPT_OK;
     const uint32_t depth = S.depth, axis_bits = depth - grid_shift;
@@ -1335,6 +1350,9 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
     uint64_t *oc_code;
     const size_t n_scan = (size_t)std::max(cap, n_cells) + 1u;
     BTRY(pool.get(&d_emissive, S.n_blocks));
+    const bool with_models = model_emissive != nullptr && n_models != 0u && S.blk_model != nullptr;  // C39
+    uint8_t *d_model_emissive = nullptr;
+    if (with_models) BTRY(pool.get(&d_model_emissive, n_models));
     BTRY(pool.get(&oc_base, cap));
     BTRY(pool.get(&oc_mask, cap));
     BTRY(pool.get(&oc_code, cap));
@@ -1346,6 +1364,7 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
     BTRY(pool.get(&d_tmp, scan_bytes));
     if (S.n_blocks)
         BTRY(hipMemcpyAsync(d_emissive, emissive, (size_t)S.n_blocks * 4, hipMemcpyHostToDevice, stream));
+    if (with_models) BTRY(hipMemcpyAsync(d_model_emissive, model_emissive, n_models, hipMemcpyHostToDevice, stream));
     // the root, then level after level
     const uint32_t root_mask = S.root_mask & 0xFFFFu;
     const uint64_t zero = 0ull;
@@ -1377,9 +1396,12 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
     }
     const uint32_t n_oct = hi;
     // the emissive leaves: mark and scan, emit (Morton code, level), sort
-    hipLaunchKernelGGL(leaf_emitters_kernel<false>, dim3(blocks((uint64_t)n_oct + 1)), dim3(kBuildBlock), 0, stream,
+    // (the instances without model emitters are the kernels they were)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(with_models ? leaf_emitters_kernel<false, true> : leaf_emitters_kernel<false, false>),
+                       dim3(blocks((uint64_t)n_oct + 1)), dim3(kBuildBlock), 0, stream,
                        S.node_child, oc_base, oc_mask, oc_code, n_oct, d_emissive, S.n_blocks, depth, d_cnt,
-                       (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, 0u);
+                       (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, 0u, S.blk_model,
+                       (const uint8_t *)d_model_emissive, n_models);
     BTRY(hipGetLastError());
     BTRY(scan_u32(stream, d_tmp, scan_bytes, d_cnt, d_offs, n_oct + 1u));
     uint32_t n_em = 0u;
@@ -1396,9 +1418,10 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
     BTRY(pool.get(&d_lv, n_em));
     BTRY(pool.get(&d_lv_s, n_em));
     if (n_em) {
-        hipLaunchKernelGGL(leaf_emitters_kernel<true>, dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, S.node_child,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(with_models ? leaf_emitters_kernel<true, true> : leaf_emitters_kernel<true, false>),
+                           dim3(blocks(n_oct)), dim3(kBuildBlock), 0, stream, S.node_child,
                            oc_base, oc_mask, oc_code, n_oct, d_emissive, S.n_blocks, depth, (uint32_t *)nullptr, d_offs,
-                           d_keys, d_lv, n_em);
+                           d_keys, d_lv, n_em, S.blk_model, (const uint8_t *)d_model_emissive, n_models);
         BTRY(hipGetLastError());
         size_t sort_bytes = 0;
         BTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys, d_keys_s, d_lv, d_lv_s, n_em, 0,
@@ -1437,8 +1460,8 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
     }
     GTRY(hipMalloc(&g.cell_emitters, std::max<size_t>(n_entries, 1) * 4));
     if (n_em) {
-        hipLaunchKernelGGL(emitter_records_kernel, dim3(blocks(n_em)), dim3(kBuildBlock), 0, stream, d_keys_s, d_lv_s, n_em,
-                           depth, g.emitters);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(with_models ? emitter_records_kernel<true> : emitter_records_kernel<false>),
+                           dim3(blocks(n_em)), dim3(kBuildBlock), 0, stream, d_keys_s, d_lv_s, n_em, depth, g.emitters);
         GTRY(hipGetLastError());
         hipLaunchKernelGGL(grid_cells_kernel<true>, dim3(blocks(n_cells)), dim3(kBuildBlock), 0, stream, d_keys_s, n_em,
                            axis_bits, grid_shift, n_cells, (uint32_t *)nullptr, g.cell_first, g.cell_emitters, n_entries);

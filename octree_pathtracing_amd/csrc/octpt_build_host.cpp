@@ -12,6 +12,7 @@
 
 #include "../../include/octpt.h"
 #include "octpt_internal.h"
+#include "octpt_emitter.h"
 
 using namespace octpt;
 
@@ -213,6 +214,65 @@ octpt_status emitter_grid_receive(octpt_emitter_grid_arrays *out, uint32_t n_cel
     return OCTPT_OK;
 }
 
+// ---- emissive block models (C39) ----
+bool emissive_model_table(const octpt_block_model *models, uint32_t n_models, const octpt_quad *quads, uint32_t n_quads,
+                          const octpt_material *mats, uint32_t nm, EmissiveModelTable &out) {
+    out.first.assign((size_t)n_models + 1u, 0u);
+    out.quad.clear();
+    out.cum.clear();
+    out.ouv.clear();
+    for (uint32_t m = 0; m < n_models; ++m) {
+        const uint64_t lo = models[m].first_quad, hi = lo + models[m].quad_count;
+        if (hi > n_quads) return false;
+        float sum = 0.0f;
+        for (uint64_t q = lo; q < hi; ++q) {
+            const octpt_quad &Q = quads[q];
+            if (Q.material >= nm) return false;
+            if (!(mats[Q.material].emittance > kEmitterEpsilon)) continue;
+            const float a = emit_quad_area(Q.u, Q.v);
+            if (!(a > 0.0f) || !(a < __builtin_inff())) continue;
+            sum = sum + a;
+            out.quad.push_back((uint32_t)q);
+            out.cum.push_back(sum);
+            out.ouv.insert(out.ouv.end(), Q.origin, Q.origin + 3);
+            out.ouv.insert(out.ouv.end(), Q.u, Q.u + 3);
+            out.ouv.insert(out.ouv.end(), Q.v, Q.v + 3);
+        }
+        out.first[m + 1u] = (uint32_t)out.quad.size();
+    }
+    return true;
+}
+
+octpt_status emitter_models_receive(octpt_emitter_model_arrays *out, uint32_t n_models, uint32_t n_entries, bool &fill) {
+    fill = false;
+    out->model_count = n_models;
+    out->entry_count = n_entries;
+    if (!out->model_first && !out->quad_index && !out->cum_area) return OCTPT_OK;
+    if (!out->model_first || !out->quad_index || !out->cum_area) return OCTPT_ERR_INVALID_ARG;
+    if (out->model_first_capacity < (uint64_t)n_models + 1u || out->quad_index_capacity < n_entries ||
+        out->cum_area_capacity < n_entries)
+        return OCTPT_ERR_INVALID_ARG;
+    fill = true;
+    return OCTPT_OK;
+}
+
+std::vector<uint8_t> model_emissive_bytes(const EmissiveModelTable &t) {
+    std::vector<uint8_t> e(t.first.size() - 1u);
+    for (size_t m = 0; m < e.size(); ++m) e[m] = t.first[m + 1] > t.first[m] ? 1u : 0u;
+    return e;
+}
+
+bool block_emissive_flags_models(const octpt_block *blocks, uint32_t nb, const std::vector<uint8_t> &model_emissive,
+                                 std::vector<uint32_t> &flags) {
+    for (uint32_t b = 0; b < nb; ++b) {
+        const uint32_t m = blocks[b].model;
+        if (m == OCTPT_MODEL_NONE) continue;
+        if (m >= model_emissive.size()) return false;
+        if (model_emissive[m]) flags[b] = kEmitModelBit | m;
+    }
+    return true;
+}
+
 }  // namespace octpt
 
 namespace {
@@ -234,7 +294,8 @@ bool collect_emitters(const octpt_octree &t, uint32_t o, uint32_t x, uint32_t y,
         const uint32_t v = oc.children[i];
         if ((oc.child_mask >> (i + 8u)) & 1u) {
             if (v >= emissive.size()) return false;
-            if (emissive[v]) out.push_back({morton(cx, cy, cz), {cx, cy, cz, h}});
+            // a full-cell emitter's side, or a model emitter's kEmitModelBit | model (C39)
+            if (emissive[v]) out.push_back({morton(cx, cy, cz), {cx, cy, cz, emissive[v] == 1u ? h : emissive[v]}});
         } else if (!collect_emitters(t, v, cx, cy, cz, h, emissive, out)) {
             return false;
         }
@@ -246,12 +307,46 @@ bool collect_emitters(const octpt_octree &t, uint32_t o, uint32_t x, uint32_t y,
 
 extern "C" {
 
+octpt_status octpt_emitter_model_table(const octpt_block_model *models, uint32_t n_models, const octpt_quad *quads,
+                                       uint32_t n_quads, const octpt_material *mats, uint32_t nm,
+                                       octpt_emitter_model_arrays *out) {
+    if (!out) return OCTPT_ERR_INVALID_ARG;
+    out->model_count = out->entry_count = 0u;
+    if ((n_models && !models) || (n_quads && !quads) || (nm && !mats)) return OCTPT_ERR_INVALID_ARG;
+    try {
+        EmissiveModelTable t;
+        if (!emissive_model_table(models, n_models, quads, n_quads, mats, nm, t)) return OCTPT_ERR_INVALID_ARG;
+        bool fill = false;
+        const octpt_status st = emitter_models_receive(out, n_models, (uint32_t)t.quad.size(), fill);
+        if (st != OCTPT_OK || !fill) return st;
+        std::copy(t.first.begin(), t.first.end(), out->model_first);
+        std::copy(t.quad.begin(), t.quad.end(), out->quad_index);
+        std::copy(t.cum.begin(), t.cum.end(), out->cum_area);
+        return OCTPT_OK;
+    } catch (const std::bad_alloc &) {
+        return OCTPT_ERR_OOM;
+    }
+}
+
 octpt_status octpt_build_emitter_grid(const uint32_t *cells, uint32_t n, const octpt_block *blocks, uint32_t nb,
                                       const octpt_material *mats, uint32_t nm, uint32_t depth, uint32_t flags,
                                       uint32_t grid_size, octpt_emitter_grid_arrays *out) {
+    return octpt_build_emitter_grid_models(cells, n, blocks, nb, mats, nm, nullptr, 0u, nullptr, 0u, depth, flags,
+                                           grid_size, 0u, out);
+}
+
+octpt_status octpt_build_emitter_grid_models(const uint32_t *cells, uint32_t n, const octpt_block *blocks, uint32_t nb,
+                                             const octpt_material *mats, uint32_t nm, const octpt_block_model *models,
+                                             uint32_t n_models, const octpt_quad *quads, uint32_t n_quads,
+                                             uint32_t depth, uint32_t flags, uint32_t grid_size, uint32_t emitter_flags,
+                                             octpt_emitter_grid_arrays *out) {
     if (!out) return OCTPT_ERR_INVALID_ARG;
     out->cell_count = out->entry_count = out->emitter_count = out->cells_per_axis = 0u;
     if ((nb && !blocks) || (nm && !mats)) return OCTPT_ERR_INVALID_ARG;
+    if (emitter_flags & ~OCTPT_EMITTERS_MODELS) return OCTPT_ERR_INVALID_ARG;
+    const bool with_models = (emitter_flags & OCTPT_EMITTERS_MODELS) != 0u;
+    if (with_models && ((n_models && !models) || (n_quads && !quads) || n_models > 0x7FFFFFFFu))
+        return OCTPT_ERR_INVALID_ARG;
     if (depth < 1 || depth > kMaxDepth) return OCTPT_ERR_INVALID_ARG;
     if (grid_size == 0u || (grid_size & (grid_size - 1u)) || grid_size > (1u << depth)) return OCTPT_ERR_INVALID_ARG;
     octpt_octree *tree = nullptr;
@@ -261,6 +356,11 @@ octpt_status octpt_build_emitter_grid(const uint32_t *cells, uint32_t n, const o
     try {
         std::vector<uint32_t> emissive;
         if (!block_emissive_flags(blocks, nb, mats, nm, emissive)) return OCTPT_ERR_INVALID_ARG;
+        if (with_models) {  // C39
+            EmissiveModelTable table;
+            if (!emissive_model_table(models, n_models, quads, n_quads, mats, nm, table)) return OCTPT_ERR_INVALID_ARG;
+            if (!block_emissive_flags_models(blocks, nb, model_emissive_bytes(table), emissive)) return OCTPT_ERR_INVALID_ARG;
+        }
         std::vector<HostEmitter> em;
         if (!collect_emitters(*tree, tree->root, 0u, 0u, 0u, 1u << depth, emissive, em)) return OCTPT_ERR_INVALID_ARG;
         if (em.size() > kMaxEmitters) return OCTPT_ERR_OOM;

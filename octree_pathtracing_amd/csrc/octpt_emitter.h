@@ -1,6 +1,7 @@
 // The emitter sample of a diffuse reflection, DESIGN.md C38 (strategy ONE), stated once for the device (shade_segment's
 // emitter instances) and the host (octpt_emitter_sample): which emitter of the hit point's grid cell is picked, the
 // target in its cube, the shadow segment's direction and the geometric factor, and the contribution's expression.
+// With OCTPT_EMITTERS_MODELS (C39) an emitter may be an emissive block model: the target is a point of one of its quads.
 // Plain f32 in this order, glam's dot-product order, correctly rounded division and sqrtf; both sides compile this
 // text with contraction off (octpt_lens.h is to the lens what this header is to the emitter; the RNG is its).
 #pragma once
@@ -23,16 +24,30 @@ struct EmitGrid {
     uint32_t axis_bits;   // log2 cells per axis
     uint32_t world;       // 2^depth
     float intensity;      // Scene::emmitter_intensity
+    // model emitters (C39): flags = OCTPT_EMITTERS_MODELS or 0 (then nothing below is read); the emissive-model
+    // table (octpt_emitter_model_table), and per table entry the quad's (origin, u, v), nine floats
+    uint32_t flags;
+    uint32_t pad;  // (no padding bytes: the context compares headers bytewise)
+    const uint32_t *model_first, *quad_index;
+    const float *cum_area, *quad_ouv;
 };
+constexpr uint32_t kEmitModelBit = 0x80000000u;  // an emitter record's fourth word: kEmitModelBit | model
 
 struct EmitShot {
     float p[3];    // the shadow segment's origin: hit point + n * OFFSET
     float dir[3];  // its direction, (t - p) / |t - p|
     float dist;
-    float geom;    // |dir . n| / max(dist^2, 1)
+    float geom;    // |dir . n| / max(dist^2, 1), for a model emitter times its emissive area A_m
     uint32_t K;    // the cell list's length
     uint32_t emitter;
+    uint32_t quad;  // the picked quad of a model emitter (C39), 0xFFFFFFFF for a cube
 };
+
+// the area |u x v| of a quad (C39): each cross component a * b - c * d, the length sqrtf((x^2 + y^2) + z^2)
+OCTPT_LENS_FN float emit_quad_area(const float u[3], const float v[3]) {
+    const float x = u[1] * v[2] - u[2] * v[1], y = u[2] * v[0] - u[0] * v[2], z = u[0] * v[1] - u[1] * v[0];
+    return sqrtf((x * x + y * y) + z * z);
+}
 
 // cell coordinate of floor(v), clamped to the world
 OCTPT_LENS_FN uint32_t emit_cell_axis(float v, const EmitGrid &G) {
@@ -60,8 +75,28 @@ OCTPT_LENS_FN bool emitter_sample(const EmitGrid &G, const float o[3], const flo
     if (k > K - 1u) k = K - 1u;
     s.emitter = G.cell_emitters[first + k];
     const octpt_emitter e = G.emitters[s.emitter];
-    const float side = (float)e.s;
-    const float t[3] = {(float)e.x + side * u1, (float)e.y + side * u2, (float)e.z + side * u3};
+    float t[3], area = 1.0f;
+    const bool model = (G.flags & OCTPT_EMITTERS_MODELS) != 0u && (e.s & kEmitModelBit) != 0u;
+    s.quad = 0xFFFFFFFFu;
+    if (model) {
+        // a model emitter (C39): the quad in proportion to its area, the first entry with u1 * A_m < cum_area, the
+        // last one else; the target on it, at the leaf's corner
+        const uint32_t m = e.s & ~kEmitModelBit;
+        const uint32_t hi = G.model_first[m + 1u];
+        uint32_t i = G.model_first[m];
+        area = G.cum_area[hi - 1u];
+        const float x = u1 * area;
+        while (i + 1u < hi && !(x < G.cum_area[i])) ++i;
+        const float *q = G.quad_ouv + 9u * i;
+        const float corner[3] = {(float)e.x, (float)e.y, (float)e.z};
+        for (int c = 0; c < 3; ++c) t[c] = ((q[c] + q[3 + c] * u2) + q[6 + c] * u3) + corner[c];
+        s.quad = G.quad_index[i];
+    } else {
+        const float side = (float)e.s;
+        t[0] = (float)e.x + side * u1;
+        t[1] = (float)e.y + side * u2;
+        t[2] = (float)e.z + side * u3;
+    }
     const float d[3] = {t[0] - s.p[0], t[1] - s.p[1], t[2] - s.p[2]};
     const float dist = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
     if (!(dist > 0.0f) || !(dist < __builtin_inff())) return false;
@@ -70,6 +105,7 @@ OCTPT_LENS_FN bool emitter_sample(const EmitGrid &G, const float o[3], const flo
     const float dn = (s.dir[0] * n[0] + s.dir[1] * n[1]) + s.dir[2] * n[2];
     const float d2 = dist * dist;
     s.geom = fabsf(dn) / (d2 > 1.0f ? d2 : 1.0f);
+    if (model) s.geom = s.geom * area;  // Chunky's face-area form: the area-proportional pick makes the factor A_m
     return true;
 }
 

@@ -11,6 +11,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <new>
+#include <vector>
 
 #include "../../include/octpt.h"
 #include "octpt_lens.h"
@@ -231,18 +233,66 @@ extern "C" octpt_status octpt_reproject_coords(const octpt_camera *camera, const
 extern "C" octpt_status octpt_emitter_sample(const octpt_emitter_grid_arrays *grid, uint32_t depth, uint32_t grid_size,
                                              const float hit[3], const float normal[3], uint32_t rng_state,
                                              float out[8], uint32_t *emitter, uint32_t *list_length) {
-    if (!grid || !hit || !normal || !out || !emitter || !list_length) return OCTPT_ERR_INVALID_ARG;
+    uint32_t quad = 0u;
+    return octpt_emitter_sample_models(grid, nullptr, nullptr, 0u, depth, grid_size, hit, normal, rng_state, out, emitter,
+                                       list_length, &quad);
+}
+
+// ... with the emissive-model table (C39); table NULL: a grid of cube emitters, sampled without the flag
+extern "C" octpt_status octpt_emitter_sample_models(const octpt_emitter_grid_arrays *grid,
+                                                    const octpt_emitter_model_arrays *table, const octpt_quad *quads,
+                                                    uint32_t quad_count, uint32_t depth, uint32_t grid_size,
+                                                    const float hit[3], const float normal[3], uint32_t rng_state,
+                                                    float out[8], uint32_t *emitter, uint32_t *list_length,
+                                                    uint32_t *quad) {
+    if (!grid || !hit || !normal || !out || !emitter || !list_length || !quad) return OCTPT_ERR_INVALID_ARG;
     if (!grid->cell_first || !grid->cell_emitters || !grid->emitters) return OCTPT_ERR_INVALID_ARG;
     if (depth < 1 || depth > 21 || grid_size == 0u || (grid_size & (grid_size - 1u)) || grid_size > (1u << depth))
         return OCTPT_ERR_INVALID_ARG;
     uint32_t shift = 0;
     while ((1u << shift) < grid_size) ++shift;
     if (grid->cells_per_axis != (1u << (depth - shift))) return OCTPT_ERR_INVALID_ARG;
-    const octpt::EmitGrid G{grid->cell_first, grid->cell_emitters, grid->emitters, shift, depth - shift, 1u << depth, 1.0f};
+    octpt::EmitGrid G{grid->cell_first, grid->cell_emitters, grid->emitters, shift, depth - shift, 1u << depth, 1.0f,
+                      0u, 0u, nullptr, nullptr, nullptr, nullptr};
+    std::vector<float> ouv;
+    if (table) {
+        if (!table->model_first || !table->quad_index || !table->cum_area || (quad_count && !quads))
+            return OCTPT_ERR_INVALID_ARG;
+        if (table->model_first[table->model_count] != table->entry_count) return OCTPT_ERR_INVALID_ARG;
+        // every model record of the grid names a model of the table that has entries
+        for (uint32_t k = 0; k < grid->emitter_count; ++k) {
+            const uint32_t w = grid->emitters[k].s;
+            if (!(w & octpt::kEmitModelBit)) continue;
+            const uint32_t m = w & ~octpt::kEmitModelBit;
+            if (m >= table->model_count || table->model_first[m + 1u] <= table->model_first[m] ||
+                table->model_first[m + 1u] > table->entry_count)
+                return OCTPT_ERR_INVALID_ARG;
+        }
+        try {
+            ouv.resize((size_t)table->entry_count * 9u);
+        } catch (const std::bad_alloc &) {
+            return OCTPT_ERR_OOM;
+        }
+        for (uint32_t i = 0; i < table->entry_count; ++i) {
+            const uint32_t q = table->quad_index[i];
+            if (q >= quad_count) return OCTPT_ERR_INVALID_ARG;
+            for (int c = 0; c < 3; ++c) {
+                ouv[9u * i + c] = quads[q].origin[c];
+                ouv[9u * i + 3 + c] = quads[q].u[c];
+                ouv[9u * i + 6 + c] = quads[q].v[c];
+            }
+        }
+        G.flags = OCTPT_EMITTERS_MODELS;
+        G.model_first = table->model_first;
+        G.quad_index = table->quad_index;
+        G.cum_area = table->cum_area;
+        G.quad_ouv = ouv.data();
+    }
     octpt::EmitShot s{};
     const bool traced = octpt::emitter_sample(G, hit, normal, rng_state, s);
     *list_length = s.K;
     *emitter = traced ? s.emitter : 0xFFFFFFFFu;
+    *quad = traced ? s.quad : 0xFFFFFFFFu;
     for (int i = 0; i < 3; ++i) {
         out[i] = s.p[i];
         out[3 + i] = traced ? s.dir[i] : 0.0f;

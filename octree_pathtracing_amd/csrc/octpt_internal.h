@@ -478,6 +478,23 @@ bool block_emissive_flags(const octpt_block *blocks, uint32_t nb, const octpt_ma
                           std::vector<uint32_t> &out);
 octpt_status emitter_grid_receive(octpt_emitter_grid_arrays *out, uint32_t n_cells, uint32_t n_entries,
                                   uint32_t n_emitters, uint32_t cells_axis, bool &fill);
+// The emissive-model table (C39, octpt_emitter_model_table in include/octpt.h) as the host holds it: first[n_models
+// + 1], and per entry the quad, the running area within its model and the quad's (origin, u, v) -- nine floats, what
+// the sample reads (EmitGrid::quad_ouv).  emissive_model_table: false on a model whose quad range leaves the table
+// or a quad of a model whose material is outside the material table.  emitter_models_receive: the count-then-fill rule.
+struct EmissiveModelTable {
+    std::vector<uint32_t> first, quad;
+    std::vector<float> cum, ouv;
+};
+bool emissive_model_table(const octpt_block_model *models, uint32_t n_models, const octpt_quad *quads, uint32_t n_quads,
+                          const octpt_material *mats, uint32_t nm, EmissiveModelTable &out);
+octpt_status emitter_models_receive(octpt_emitter_model_arrays *out, uint32_t n_models, uint32_t n_entries, bool &fill);
+// the emissive byte of every model (it has an entry), and the flag of every block when model emitters are listed too:
+// 1 a full-cell emitter as block_emissive_flags, kEmitModelBit | model a block whose model is emissive, 0 else --
+// a leaf's record's fourth word but for the cube's side; false: a block's model outside the table
+std::vector<uint8_t> model_emissive_bytes(const EmissiveModelTable &t);
+bool block_emissive_flags_models(const octpt_block *blocks, uint32_t nb, const std::vector<uint8_t> &model_emissive,
+                                 std::vector<uint32_t> &flags);
 
 // grow-only device scratch of the GPU octree builder, owned by the context: repeated builds
 // (scene edits) reuse it instead of paying hipMalloc / hipFree per buffer
@@ -569,10 +586,15 @@ struct DeviceEmitterGrid {
     uint32_t *cell_first = nullptr, *cell_emitters = nullptr;
     octpt_emitter *emitters = nullptr;
     uint32_t n_cells = 0, n_entries = 0, n_emitters = 0, cells_axis = 0, grid_shift = 0;
+    uint32_t flags = 0;  // OCTPT_EMITTERS_MODELS: model emitters are listed (C39; set by the context)
 };
+// model_emissive (C39, OCTPT_EMITTERS_MODELS; NULL without it): the host's emissive byte of each of the scene's n_models
+// models, which the leaf-count and record kernels test beside the per-block flag through S.blk_model; such a leaf's
+// record is (x, y, z, 0x80000000 | model).
 hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, const DevScene &S,
                                   const uint32_t *emissive, uint32_t grid_shift, DeviceEmitterGrid &out,
-                                  octpt_status &refusal);
+                                  octpt_status &refusal, const uint8_t *model_emissive = nullptr,
+                                  uint32_t n_models = 0u);
 
 }  // namespace octpt
 

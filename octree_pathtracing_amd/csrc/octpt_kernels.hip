@@ -1526,11 +1526,12 @@ __device__ inline bool emitter_shot(const DevScene &S, const DevMaterial &m, Pat
 }
 
 // ... and after that segment: it contributes when it hit a full-cell block leaf (key kPrimNone) whose entered face's
-// material emits and whose texel is not transparent -- any listed emitter, as in Chunky.  Then the waiting sun sample's
-// shadow segments start, or the waiting bounce resumes.
+// material emits and whose texel is not transparent -- any listed emitter, as in Chunky.  With model emitters listed
+// (C39, OCTPT_EMITTERS_MODELS) a block-model quad counts the same way: its material's emittance, its texel's alpha.
+// Then the waiting sun sample's shadow segments start, or the waiting bounce resumes.
 template <bool kNee>
 __device__ inline void emitter_segment_done(const DevScene &S, PathState &ray, bool hit) {
-    if (hit && ray.last_prim == kPrimNone) {
+    if (hit && (ray.last_prim == kPrimNone || (emit_grid_of(S).flags & OCTPT_EMITTERS_MODELS) != 0u)) {
         const float emittance = S.mats[ray.cur].emittance;
         if (emittance > RAY_EPSILON && ray.col[3] > RAY_EPSILON) {
             const float e = emitter_scale(ray.mult, emittance, emit_grid_of(S).intensity, (uint32_t)(-ray.att[3]));
@@ -1612,9 +1613,12 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
         specular_reflection(ray, m.roughness);
     } else if (rng_next(ray.rng) < diffuse) {
         // emitter sampling (C38): own emittance at depth 1 as ever, and dropped at depth > 1 exactly on a full-cell
-        // block leaf (a listed emitter, which the sample reaches; its key is kPrimNone, a quad's is not)
+        // block leaf (a listed emitter, which the sample reaches; its key is kPrimNone, a quad's is not); with model
+        // emitters listed (C39) on every emissive hit: a block scene has no other emissive surface
 #if defined(OCTPT_EMIT_TU)
-        if (!kLean && S.emitters && m.emittance > RAY_EPSILON && (ray.depth == 1u || ray.last_prim != kPrimNone)) {
+        if (!kLean && S.emitters && m.emittance > RAY_EPSILON &&
+            (ray.depth == 1u ||
+             (ray.last_prim != kPrimNone && (emit_grid_of(S).flags & OCTPT_EMITTERS_MODELS) == 0u))) {
 #else
         if (!kLean && S.emitters && m.emittance > RAY_EPSILON) {
 #endif

@@ -181,7 +181,8 @@ class HipRenderer:
         self._check(self._lib.octpt_scene_upload(self._ctx, C.byref(desc)))
         # the scene's emitter sampling (C38) is the renderer's from here on: a scene with NONE switches it off
         if scene.emitter_sampling != _lib.EMITTERS_NONE or self._scene_emitters:
-            self.set_emitter_sampling(scene.emitter_sampling, scene.emitter_grid_size, scene.emitter_intensity)
+            self.set_emitter_sampling(scene.emitter_sampling, scene.emitter_grid_size, scene.emitter_intensity,
+                                      models=scene.emitter_models)
         self._scene_emitters = scene.emitter_sampling != _lib.EMITTERS_NONE
         self._scene_keep = keep
         self.reset_render()
@@ -671,12 +672,22 @@ class HipRenderer:
         return tile_spp, res.as_dict()
 
     # ------------------------------------------------------------ emitter sampling (C38)
-    def set_emitter_sampling(self, strategy: int, grid_size: int = 8, intensity: float = 1.0) -> None:
+    def set_emitter_sampling(self, strategy: int, grid_size: int = 8, intensity: float = 1.0,
+                             models: bool = False) -> None:
         """Scene::emitter_sampling_strategy and emmitter_intensity (octpt_set_emitter_sampling): _lib.EMITTERS_NONE or
         _lib.EMITTERS_ONE, the emitter grid's cell side in voxels and the intensity, for every later render.  With
-        ONE and a block-value scene this GPU builds the emitter grid (emitter_grid)."""
-        self._check(self._lib.octpt_set_emitter_sampling(
-            self._ctx, C.byref(_lib.EmitterParams(int(strategy), int(grid_size), float(intensity)))))
+        ONE and a block-value scene this GPU builds the emitter grid (emitter_grid).  models: emissive block models
+        (torches, lanterns) are emitters too (_lib.EMITTERS_MODELS; emitter_models)."""
+        p = _lib.EmitterParams(int(strategy), int(grid_size), float(intensity))
+        p.flags = _lib.EMITTERS_MODELS if models else 0
+        self._check(self._lib.octpt_set_emitter_sampling(self._ctx, C.byref(p)))
+
+    def emitter_models(self) -> dict:
+        """The emissive-model table this GPU holds beside a grid built with models=True (octpt_emitter_models), as
+        scene.emitter_model_table returns the host's."""
+        from .scene import take_emitter_models
+
+        return take_emitter_models(lambda t: self._check(self._lib.octpt_emitter_models(self._ctx, C.byref(t))))
 
     def emitter_grid(self) -> dict:
         """The emitter grid this GPU built (octpt_emitter_grid), as scene.build_emitter_grid returns the host's."""

@@ -309,6 +309,9 @@ class Scene:
     emitter_sampling: int = _lib.EMITTERS_NONE
     emitter_grid_size: int = 8
     emitter_intensity: float = 1.0
+    # emissive block models (torches, lanterns) are emitters too (C39, _lib.EMITTERS_MODELS); carried by set_scene
+    # like the three above
+    emitter_models: bool = False
 
     # ---------------------------------------------------------------- octree
     def build_octree(self, depth: int, renderer=None, compact: bool = False, device_cells=None,
@@ -430,6 +433,11 @@ class Scene:
         return (_lib.Material * len(self.materials))(*[
             _lib.Material(m.ior, m.specular, m.emittance, m.roughness, m.metalness, m.texture_index, m.tint_index, m.flags)
             for m in self.materials])
+
+    def model_structs(self):
+        """octpt_block_model rows of `models`."""
+        rows = np.asarray(self.models, np.uint32).reshape(-1, 2)
+        return (_lib.BlockModel * max(len(rows), 1))(*[_lib.BlockModel(0, int(a), int(n), 0) for a, n in rows])
 
     def block_structs(self):
         """octpt_block rows of `blocks` / `block_model` (C23)."""
@@ -563,28 +571,68 @@ def take_emitter_grid(call) -> dict:
             "cells_per_axis": int(g.cells_per_axis)}
 
 
-def build_emitter_grid(scene: Scene, depth: int, grid_size: int, compact: bool = False) -> dict:
+def build_emitter_grid(scene: Scene, depth: int, grid_size: int, compact: bool = False, models: bool = False) -> dict:
     """The emitter grid of a block-value scene's cells on the host (octpt_build_emitter_grid, the grid's definition,
-    DESIGN.md C38): see take_emitter_grid for the result."""
+    DESIGN.md C38): see take_emitter_grid for the result.  models: emissive block models are emitters too
+    (octpt_build_emitter_grid_models with OCTPT_EMITTERS_MODELS, C39), their records (x, y, z, 0x80000000 | model)."""
     if scene.blocks is None:
         raise ValueError("build_emitter_grid: a block-value scene (scene.blocks) is needed")
     lib = _lib.load()
     cells, blocks, mats = scene.cells_array(), scene.block_structs(), scene.material_structs()
+    mdl, quads = scene.model_structs(), np.ascontiguousarray(scene.quads)
 
     def call(g):
-        _lib.check(lib, None, lib.octpt_build_emitter_grid(
+        if not models:
+            _lib.check(lib, None, lib.octpt_build_emitter_grid(
+                cells.ctypes.data_as(C.c_void_p) if len(cells) else None, len(cells), C.cast(blocks, C.c_void_p),
+                len(scene.blocks), C.cast(mats, C.c_void_p), len(scene.materials), depth,
+                _lib.BUILD_COMPACT if compact else 0, grid_size, C.byref(g)))
+            return
+        _lib.check(lib, None, lib.octpt_build_emitter_grid_models(
             cells.ctypes.data_as(C.c_void_p) if len(cells) else None, len(cells), C.cast(blocks, C.c_void_p),
-            len(scene.blocks), C.cast(mats, C.c_void_p), len(scene.materials), depth,
-            _lib.BUILD_COMPACT if compact else 0, grid_size, C.byref(g)))
+            len(scene.blocks), C.cast(mats, C.c_void_p), len(scene.materials), C.cast(mdl, C.c_void_p), len(scene.models),
+            quads.ctypes.data_as(C.c_void_p) if len(quads) else None, len(quads), depth,
+            _lib.BUILD_COMPACT if compact else 0, grid_size, _lib.EMITTERS_MODELS, C.byref(g)))
 
     return take_emitter_grid(call)
 
 
-def emitter_sample(grid: dict, depth: int, grid_size: int, hit, normal, rng_state: int) -> dict:
+def take_emitter_models(call) -> dict:
+    """The emissive-model table of a count-then-fill entry (as take_emitter_grid): model_first (n_models + 1),
+    quad_index and cum_area (f32) per entry."""
+    t = _lib.EmitterModelArrays()
+    call(t)
+    first = np.zeros(t.model_count + 1, np.uint32)
+    quad = np.zeros(max(t.entry_count, 1), np.uint32)
+    cum = np.zeros(max(t.entry_count, 1), F32)
+    t.model_first, t.model_first_capacity = first.ctypes.data, len(first)
+    t.quad_index, t.quad_index_capacity = quad.ctypes.data, len(quad)
+    t.cum_area, t.cum_area_capacity = cum.ctypes.data, len(cum)
+    call(t)
+    return {"model_first": first, "quad_index": quad[: t.entry_count], "cum_area": cum[: t.entry_count]}
+
+
+def emitter_model_table(scene: Scene) -> dict:
+    """The emissive-model table of the scene's models, quads and materials on the host (octpt_emitter_model_table, its
+    definition): see take_emitter_models."""
+    lib = _lib.load()
+    mdl, quads, mats = scene.model_structs(), np.ascontiguousarray(scene.quads), scene.material_structs()
+
+    def call(t):
+        _lib.check(lib, None, lib.octpt_emitter_model_table(
+            C.cast(mdl, C.c_void_p), len(scene.models), quads.ctypes.data_as(C.c_void_p) if len(quads) else None,
+            len(quads), C.cast(mats, C.c_void_p), len(scene.materials), C.byref(t)))
+
+    return take_emitter_models(call)
+
+
+def emitter_sample(grid: dict, depth: int, grid_size: int, hit, normal, rng_state: int, table: dict | None = None,
+                   quads=None) -> dict:
     """octpt_emitter_sample: the emitter sample of one diffuse hit as the emitter instances of shade take it
     (csrc/octpt_emitter.h; host-only).  grid: a build_emitter_grid / HipRenderer.emitter_grid result.  Returns p, dir
     (f32 [3]), dist, geom, K (the hit's cell list's length) and emitter (index into grid["emitters"], None when no
-    segment is traced)."""
+    segment is traced).  With table (an emitter_model_table result) and quads (the scene's, _lib.QUAD_DTYPE) the grid
+    may list model emitters (octpt_emitter_sample_models, C39), and `quad` is the picked quad (None for a cube)."""
     lib = _lib.load()
     first = np.ascontiguousarray(grid["cell_first"], np.uint32)
     entries = np.ascontiguousarray(grid["cell_emitters"], np.uint32)
@@ -598,11 +646,27 @@ def emitter_sample(grid: dict, depth: int, grid_size: int, hit, normal, rng_stat
     g.cells_per_axis = int(grid["cells_per_axis"])
     h, n = np.ascontiguousarray(hit, F32), np.ascontiguousarray(normal, F32)
     out, em, K = np.zeros(8, F32), C.c_uint32(), C.c_uint32()
-    _lib.check(lib, None, lib.octpt_emitter_sample(C.byref(g), depth, grid_size, h.ctypes.data_as(C.c_void_p),
-                                                   n.ctypes.data_as(C.c_void_p), int(rng_state) & 0xFFFFFFFF,
-                                                   out.ctypes.data_as(C.c_void_p), C.byref(em), C.byref(K)))
+    quad = C.c_uint32(0xFFFFFFFF)
+    if table is None:
+        _lib.check(lib, None, lib.octpt_emitter_sample(C.byref(g), depth, grid_size, h.ctypes.data_as(C.c_void_p),
+                                                       n.ctypes.data_as(C.c_void_p), int(rng_state) & 0xFFFFFFFF,
+                                                       out.ctypes.data_as(C.c_void_p), C.byref(em), C.byref(K)))
+    else:
+        mf = np.ascontiguousarray(table["model_first"], np.uint32)
+        qi, ca = np.ascontiguousarray(table["quad_index"], np.uint32), np.ascontiguousarray(table["cum_area"], F32)
+        t = _lib.EmitterModelArrays()
+        t.model_first, t.model_first_capacity = mf.ctypes.data, len(mf)
+        t.quad_index, t.quad_index_capacity = (qi if len(qi) else pad).ctypes.data, len(qi)
+        t.cum_area, t.cum_area_capacity = (ca if len(ca) else pad).ctypes.data, len(ca)
+        t.model_count, t.entry_count = len(mf) - 1, len(qi)
+        qd = np.ascontiguousarray(quads)
+        _lib.check(lib, None, lib.octpt_emitter_sample_models(
+            C.byref(g), C.byref(t), qd.ctypes.data_as(C.c_void_p) if len(qd) else None, len(qd), depth, grid_size,
+            h.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), int(rng_state) & 0xFFFFFFFF,
+            out.ctypes.data_as(C.c_void_p), C.byref(em), C.byref(K), C.byref(quad)))
     return {"p": out[:3].copy(), "dir": out[3:6].copy(), "dist": float(out[6]), "geom": float(out[7]),
-            "K": int(K.value), "emitter": None if em.value == 0xFFFFFFFF else int(em.value)}
+            "K": int(K.value), "emitter": None if em.value == 0xFFFFFFFF else int(em.value),
+            "quad": None if quad.value == 0xFFFFFFFF else int(quad.value)}
 
 
 @dataclass
