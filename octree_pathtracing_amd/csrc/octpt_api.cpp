@@ -3,7 +3,9 @@
 // Replaces the reference's wgpu backend (src/renderer/gpu_renderer.rs:151-702): scene
 // validation + upload (set_scene / create_pipeline), camera uniform construction
 // (render_frame :590-599), progressive render submission, FrameInFlight polling, and the
-// device octree and scene build entries.  The host builders are in octpt_build_host.cpp.
+// device octree and scene build entries.  The host builders are in octpt_build_host.cpp, the
+// post-processing entries (guide buffers, denoisers, temporal passes, variance, adaptive and final
+// frames) in octpt_post.cpp; octpt_ctx.h holds the context and what the two files share.
 // No CPU rendering path exists here.
 #include <hip/hip_runtime.h>
 
@@ -20,46 +22,14 @@
 #include <memory>
 #include <vector>
 
-#include "../../include/octpt.h"
-#include "octpt_internal.h"
+#include "octpt_ctx.h"
 #include "octpt_lens.h"
-#include "octpt_emitter.h"
 #include "octpt_mask.h"
-#include "octpt_reproject.h"
+#include "octpt_stage.h"
 
 using namespace octpt;
 
 namespace {
-
-constexpr uint32_t kCounterRing = 256;
-constexpr uint64_t kMaxChunkPaths = 1ull << 31;    // colour buffer: up to 32 GiB of float4 per chunk (OCTPT_CHUNK)
-constexpr uint64_t kDefaultChunkPaths = 1ull << 29;  // 4K: 64-spp chunks (C5 4634 vs 3882 Mrays/s at 2^30; C3 stays one chunk)
-                                                    // (C3 = 530 M paths = one chunk: one drain tail)
-#ifndef OCTPT_LOOKAHEAD
-#define OCTPT_LOOKAHEAD 3
-#endif
-constexpr uint32_t kLookahead = OCTPT_LOOKAHEAD;    // host steering: iterations queued ahead of the check
-constexpr uint32_t kDefaultPool = 512u << 20;        // path slots in flight (124 B each: queues + path state)
-constexpr uint32_t kMaxPool = 1u << 30;              // the sun-sampling planes index 4 * pool slots in uint32
-constexpr uint32_t kMinPool = 1u << 20;              // floor of the out-of-memory fallback (halving)
-constexpr uint32_t kDefaultRefill = 0;               // extend: idle lanes before a wave refills (0: adaptive)
-constexpr uint32_t kDefaultDrainRays = 4096;         // drain the chunk in one launch below this many queued rays
-#ifndef OCTPT_SAMPLE_GROUP_DEFAULT
-#define OCTPT_SAMPLE_GROUP_DEFAULT 64  // best on C3 once resolve reads a grouped chunk's records once
-#endif
-// a pixel's samples per wave of the chunk's item order, at most (1, 4, 16 or 64; OCTPT_SAMPLE_GROUP)
-constexpr uint32_t kDefaultSampleGroup = OCTPT_SAMPLE_GROUP_DEFAULT;
-constexpr uint64_t kGroupMinItems = 1ull << 27;       // chunks below this many items keep G = 1 unless OCTPT_SAMPLE_GROUP is set
-// extend's refill threshold in the first launch of a grouped chunk whose queue holds the seed's camera records
-// (OCTPT_REFILL_FIRST), per extend instance; 0: the adaptive rule, as in every other launch
-#ifndef OCTPT_REFILL_FIRST_SPHERES
-#define OCTPT_REFILL_FIRST_SPHERES 64  // C3 -6.6 % of its step; 32 / 60 give -1.3 %, 48 / 56 under 1 %
-#endif
-#ifndef OCTPT_REFILL_FIRST_BOXES
-#define OCTPT_REFILL_FIRST_BOXES 64  // C4 -5.6 %; 60 gives -1.3 %, 48 -0.9 %
-#endif
-constexpr uint32_t kRefillFirstSpheres = OCTPT_REFILL_FIRST_SPHERES;
-constexpr uint32_t kRefillFirstBoxes = OCTPT_REFILL_FIRST_BOXES;  // scenes with cuboids, without blocks or models
 
 // log2 of the largest G in {1, 4, 16, 64} that is at most `most` and divides the chunk's sample count
 uint32_t group_shift_of(uint32_t most, uint32_t chunk_spp) {
@@ -74,197 +44,6 @@ uint32_t env_u32(const char *name, uint32_t dflt) {
     const long x = std::strtol(v, nullptr, 10);
     return x > 0 ? (uint32_t)x : dflt;
 }
-
-struct EventPair {
-    hipEvent_t start, stop;
-};
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-};
-
-}  // namespace
-
-struct octpt_ctx {
-    int device = 0;
-    int num_cu = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    // scene
-    bool has_scene = false;
-    DevScene S{};
-    std::vector<void *> scene_allocs;
-    // camera
-    bool has_camera = false;
-    octpt_camera cam{};
-    DevCamera C{};
-    // per-context device state
-    uint32_t *d_counters = nullptr;  // ring of work counters, one per launch
-    // branch schedule of the current render (C20): host copy + grow-only device table
-    std::vector<uint2> h_subs;
-    uint2 *d_subs = nullptr;
-    size_t subs_cap = 0;
-    // beam starts of the camera rays, one per kBeamTile^2 pixels (beam_kernel), grow-only
-    float *d_beam = nullptr;
-    size_t beam_cap = 0;
-    uint32_t launch_seq = 0;
-    unsigned long long *d_stats = nullptr;
-    uint8_t *d_lut_byte = nullptr;
-    float *d_lut_float = nullptr;
-    std::vector<EventPair> pending;
-    double kernel_ms = 0.0;
-    uint64_t launches = 0;
-    // per-kernel timing (OCTPT_RENDER_KERNEL_TIMING): kind 0 extend, 1 shade
-    bool ktiming = false;
-    std::vector<std::pair<int, EventPair>> kpending;
-    std::vector<EventPair> ev_pool;
-    double kern_ms[2] = {0.0, 0.0};
-    uint64_t kern_n[2] = {0, 0};
-    float build_ms = 0.0f;  // device time of the last octpt_build_octree_device
-    BuildScratch build_scratch;
-    int blocks_per_cu_cache[kMaxDepth + 1] = {0};
-    int extend_bpc_cache[kMaxDepth + 1][4] = {};  // [depth][kPrims]
-    int shade_bpc_cache[2][2][3] = {};            // [sun sampling][LDS tables][shade_mode]
-    bool lean_scene = false;  // no emitters, no sun sampling: the lean path state applies when the pool holds the chunk
-    bool no_lean = false;     // OCTPT_LEAN=0: always the 40-B path state (A/B, tests)
-    bool sample_group_set = false;                // OCTPT_SAMPLE_GROUP given: no rule about where the order is grouped
-    uint32_t sample_group = kDefaultSampleGroup;  // OCTPT_SAMPLE_GROUP: the item order's G at most; 1 = one sample per wave
-    // wavefront pool (grown on demand)
-    WaveBuffers wb{};
-    size_t pool = 0, color_cap = 0, nee_pool = 0;  // nee_pool: slots of the sun-sampling planes (wb.pd)
-    void *nee_alloc = nullptr;
-    std::vector<void *> wave_allocs;
-    void *color_alloc = nullptr;
-    // device bytes of the wavefront state (queues, path state, colour records, sun-sampling planes),
-    // tracked against mem_limit (OCTPT_DEVICE_MEM_LIMIT, MiB, 0 = none: a test hook that makes the
-    // out-of-memory fallback reproducible on an idle GPU)
-    size_t wave_bytes = 0, mem_limit = 0;
-    std::vector<std::pair<void *, size_t>> wave_sizes;
-    uint64_t wave_allocs_n = 0;  // successful (re)allocations of the queues + path state
-    bool oom_warned = false;
-    uint32_t *h_count = nullptr;  // pinned ring: the segment counters after each iteration's shade
-    uint32_t *d_count = nullptr;  // its device address (wf_snapshot_kernel)
-    hipEvent_t count_ev[kLookahead + 1] = {};
-    uint32_t pool_cap = kDefaultPool, refill = kDefaultRefill;
-    int32_t refill_first = -1;  // OCTPT_REFILL_FIRST (0..64); -1: unset, the extend instance's compiled default
-    bool beam = true;  // camera rays start at their tile's beam (OCTPT_BEAM=0: off)
-    uint32_t drain_rays = kDefaultDrainRays;  // queue length at which the drain takes over (OCTPT_DRAIN_RAYS, 0 = off)
-    bool drain_models = false;                // the drain in block-model scenes too (OCTPT_DRAIN_MODELS=1, A/B)
-    uint64_t chunk_cap = kDefaultChunkPaths;  // (pixel, sample) items per chunk (OCTPT_CHUNK)
-    // one asynchronous frame may be in flight; device-touching calls join it first
-    octpt_frame *inflight = nullptr;
-    // multi-device context (octpt_create_multi): one child context per device entry; this context's own
-    // device is the first entry's, where the caller's buffers live.  Empty for octpt_create.
-    std::vector<octpt_ctx *> sub;
-    // multi-device renders: the staged compact tile buffers (this context: every entry's, side by side on
-    // the first device; a child: its own), grow-only
-    float4 *m_acc = nullptr;
-    uint32_t *m_seg = nullptr;
-    size_t m_acc_cap = 0, m_seg_cap = 0;
-    // the denoiser's two ping-pong frames (octpt_denoise_device, C25), allocated on first use, grow-only
-    float4 *dn_frame[2] = {nullptr, nullptr};
-    size_t dn_cap[2] = {0, 0};
-    // the tile deal (octpt_set_tile_order): for order_w x order_h frames, dealing position -> frame tile and
-    // its inverse, on this context's device; empty = the round-robin deal
-    std::vector<uint32_t> h_order;
-    uint32_t order_w = 0, order_h = 0;
-    uint32_t *d_order = nullptr, *d_order_pos = nullptr;
-    // what the beam table in d_beam was computed for (round 5): the scene, camera and tile order (their
-    // generations) and the frame size and shard.  A render with the same key reuses it -- a progressive
-    // renderer calls render_frame again and again with one camera -- and anything else recomputes it.
-    uint64_t scene_gen = 0, camera_gen = 0, order_gen = 0;
-    struct BeamKey {
-        uint64_t scene = 0, camera = 0, order = 0;
-        // a tile-list render (octpt_render_tiles_device) computes only its tiles' starts: its list's number, a
-        // fresh one per call (0 = an ordinary render), so that no render takes such a table for its own
-        uint64_t list = 0;
-        uint32_t w = 0, h = 0, shard_index = 0, shard_count = 0;
-        bool valid = false;
-        bool operator==(const BeamKey &o) const {
-            return valid && o.valid && scene == o.scene && camera == o.camera && order == o.order && list == o.list &&
-                   w == o.w && h == o.h && shard_index == o.shard_index && shard_count == o.shard_count;
-        }
-    } beam_key;
-    // tile-list renders (C30): the list as the deal (DevRender::tile_order), grow-only like d_subs, and the
-    // number of the last list (BeamKey::list)
-    uint32_t *d_tiles = nullptr;
-    size_t tiles_cap = 0;
-    uint64_t list_gen = 0;
-    // the adaptive driver (C32): its device copies of tile_spp and the per-tile error, grow-only
-    uint32_t *d_tile_spp = nullptr;
-    float *d_tile_err = nullptr;
-    size_t tile_spp_cap = 0, tile_err_cap = 0;
-    // the sample clamp of resolve (C33, octpt_set_sample_clamp): 0 = off
-    float sample_clamp = 0.0f;
-    // emitter sampling (C38, octpt_set_emitter_sampling): the setting, the scene's emissive flag per block (empty
-    // for a scene of primitive leaves), and the device grid built when strategy ONE and a block-value scene are
-    // both known (grid_valid; its three arrays are allocations of their own)
-    uint32_t emit_strategy = OCTPT_EMITTERS_NONE, emit_grid_size = 8u;
-    float emit_intensity = 1.0f;
-    uint32_t emit_flags = 0u;  // OCTPT_EMITTERS_MODELS (C39)
-    std::vector<uint32_t> block_emissive;
-    // model emitters (C39): the scene's emissive-model table, built on the host at the scene entry, its emissive
-    // byte per model, and the table on the device (scene allocations, uploaded once per scene when a grid with
-    // OCTPT_EMITTERS_MODELS is first built)
-    EmissiveModelTable emit_models;
-    std::vector<uint8_t> model_emissive;
-    uint32_t *d_model_first = nullptr, *d_model_quad = nullptr;
-    float *d_model_cum = nullptr, *d_model_ouv = nullptr;
-    DeviceEmitterGrid emit_grid;
-    bool grid_valid = false;
-    EmitGrid *d_emit_hdr = nullptr;  // the render's EmitGrid on the device (the emitter instances' S.leaf_sph)
-    EmitGrid emit_hdr_host{};        // ... and what it holds (uploaded again only when the grid or the intensity changed)
-    bool emit_hdr_valid = false;
-    size_t nee_planes = 0;           // planes of wb.pd per slot: 4 (sun sampling) or 6 (emitter sampling)
-    // the seam rule's spread error plane (C34, the _ex driver) and the finished frame's guide and variance planes
-    // (C36, octpt_render_final_device), grow-only
-    float *d_tile_spread = nullptr;
-    size_t tile_spread_cap = 0;
-    float4 *fin_normal = nullptr, *fin_albedo = nullptr;
-    float *fin_depth = nullptr, *fin_var = nullptr;
-    size_t fin_normal_cap = 0, fin_albedo_cap = 0, fin_depth_cap = 0, fin_var_cap = 0;
-    // recorded on the stream that computed the table: a render on another stream that reuses it waits for it
-    hipEvent_t beam_ev = nullptr;
-    hipStream_t beam_stream = nullptr;  // the stream the valid table was computed on
-    bool beam_shared = false;           // ... and whether a render on another stream has read it since
-};
-
-struct octpt_frame {
-    octpt_ctx *ctx = nullptr;
-    octpt_render_params params{};  // the call's parameters (a multi-device context re-derives each entry's)
-    std::thread worker;
-    std::atomic<bool> finished{false};
-    std::atomic<bool> cancel_requested{false};
-    octpt_status status = OCTPT_OK;
-    float *user_accum = nullptr;
-    uint8_t *user_rgba = nullptr;
-    size_t n_pixels = 0;
-    float4 *d_accum = nullptr;
-    uchar4 *d_rgba = nullptr;
-    float *h_accum = nullptr;   // pinned
-    uint8_t *h_rgba = nullptr;  // pinned
-    bool delivered = false;
-};
-
-namespace {
-
-octpt_status fail(octpt_ctx *ctx, octpt_status st, const std::string &msg) {
-    if (ctx) ctx->err = msg;
-    return st;
-}
-
-octpt_status hip_fail(octpt_ctx *ctx, hipError_t e, const char *what) {
-    return fail(ctx, e == hipErrorOutOfMemory ? OCTPT_ERR_OOM : OCTPT_ERR_DEVICE,
-                std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(ctx, expr)                                 \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) return hip_fail(ctx, _e, #expr); \
-    } while (0)
 
 // colour LUTs (texture.rs:42-62), computed with the host libm like the reference
 void make_luts(float lut_float[256], uint8_t lut_byte[256]) {
@@ -745,7 +524,9 @@ uint32_t tiles_of_shard(uint32_t n_tiles, uint32_t shard, uint32_t count) {
     return shard < n_tiles ? (n_tiles - shard + count - 1) / count : 0;
 }
 
-octpt_status make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender &R) {
+}  // namespace
+
+octpt_status octpt::make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender &R) {
     if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
     if (!ctx->has_scene) return fail(ctx, OCTPT_ERR_INVALID_ARG, "no scene uploaded (set_scene)");
     if (!ctx->has_camera) return fail(ctx, OCTPT_ERR_INVALID_ARG, "no camera set");
@@ -817,16 +598,11 @@ octpt_status make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender
             return fail(ctx, OCTPT_ERR_INVALID_ARG, "spp_start + spp_count is not a pass boundary of the branch schedule");
         if (!ctx->h_subs.empty()) {
             HIP_TRY(ctx, hipDeviceSynchronize());  // an earlier render may still read the table
-            if (ctx->h_subs.size() > ctx->subs_cap) {
-                if (ctx->d_subs) (void)hipFree(ctx->d_subs);
-                ctx->d_subs = nullptr;
-                ctx->subs_cap = 0;
-                HIP_TRY(ctx, hipMalloc(&ctx->d_subs, ctx->h_subs.size() * sizeof(uint2)));
-                ctx->subs_cap = ctx->h_subs.size();
-            }
-            HIP_TRY(ctx, hipMemcpy(ctx->d_subs, ctx->h_subs.data(), ctx->h_subs.size() * sizeof(uint2),
+            const octpt_status st = grow_buf(ctx, ctx->d_subs, ctx->h_subs.size());
+            if (st != OCTPT_OK) return st;
+            HIP_TRY(ctx, hipMemcpy(ctx->d_subs.p, ctx->h_subs.data(), ctx->h_subs.size() * sizeof(uint2),
                                    hipMemcpyHostToDevice));
-            R.subs = ctx->d_subs;
+            R.subs = ctx->d_subs.p;
         }
     }
     // RendererMode::Preview renders one replacing pass; spp and max_depth do not apply (C16)
@@ -835,7 +611,7 @@ octpt_status make_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender
     return OCTPT_OK;
 }
 
-size_t accum_pixels(const DevRender &R) { return R.compact ? (size_t)R.total_items : (size_t)R.W * R.H; }
+namespace {
 
 // wavefront-state allocations, counted against the optional mem_limit
 hipError_t wave_malloc(octpt_ctx *ctx, void **p, size_t bytes) {
@@ -1152,14 +928,11 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             whole.list = 0u;
             if (whole == ctx->beam_key) key = whole;
         }
-        if (n_tiles > ctx->beam_cap) {
+        if (needs_grow(n_tiles, ctx->d_beam)) {
             HIP_TRY(ctx, hipDeviceSynchronize());  // an earlier render may still read the table
-            if (ctx->d_beam) (void)hipFree(ctx->d_beam);
-            ctx->d_beam = nullptr;
-            ctx->beam_cap = 0;
             ctx->beam_key.valid = false;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_beam, n_tiles * sizeof(float)));
-            ctx->beam_cap = n_tiles;
+            const octpt_status st = grow_buf(ctx, ctx->d_beam, n_tiles);
+            if (st != OCTPT_OK) return st;
         }
         if (!ctx->beam_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->beam_ev, hipEventDisableTiming));
         if (!(key == ctx->beam_key)) {  // same scene, camera, size, shard and deal: the table is already there
@@ -1167,7 +940,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             // so the device drains first; a render on the computing stream is ordered by the stream itself
             if (ctx->beam_key.valid && (s != ctx->beam_stream || ctx->beam_shared)) HIP_TRY(ctx, hipDeviceSynchronize());
             ctx->beam_key.valid = false;
-            HIP_TRY(ctx, launch_beam(ctx->S, ctx->C, R, ctx->d_beam, s));
+            HIP_TRY(ctx, launch_beam(ctx->S, ctx->C, R, ctx->d_beam.p, s));
             HIP_TRY(ctx, hipEventRecord(ctx->beam_ev, s));
             ctx->beam_key = key;
             ctx->beam_stream = s;
@@ -1176,7 +949,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->beam_ev, 0));  // (a no-op on the stream that computed it)
             ctx->beam_shared |= s != ctx->beam_stream;  // read on another stream: a recompute drains the device
         }
-        beam = ctx->d_beam;
+        beam = ctx->d_beam.p;
     }
     for (uint32_t c0 = 0, c1 = 0; c0 < R.spp_count; c0 = c1) {
         c1 = c0 + std::min(chunk_spp, R.spp_count - c0);
@@ -1284,9 +1057,10 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     return OCTPT_OK;
 }
 
-octpt_status enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d_accum, uint32_t *d_seg, hipStream_t s,
-                            bool megakernel, const std::atomic<bool> *cancel = nullptr, float2 *d_moments = nullptr,
-                            uint64_t list = 0) {
+}  // namespace
+
+octpt_status octpt::enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d_accum, uint32_t *d_seg, hipStream_t s,
+                                   bool megakernel, const std::atomic<bool> *cancel, float2 *d_moments, uint64_t list) {
     if (R.spp_count == 0 || R.total_items == 0) return OCTPT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     EventPair ev{};
@@ -1315,7 +1089,7 @@ octpt_status enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d_accum,
 // tiles between the caller's buffers on the first device and the children's compact buffers with peer
 // copies (hipMemcpyPeerAsync: xGMI DMA between MI355X devices; a plain device copy when an entry repeats
 // a device).  Per-pixel RNG streams make the result bit-identical to one device's.
-bool is_multi(const octpt_ctx *ctx) { return !ctx->sub.empty(); }
+namespace {
 
 // fn(i) for every child i, one host thread each; the first failing entry's status and message are returned
 template <class F>
@@ -1340,18 +1114,6 @@ octpt_status for_each_sub(octpt_ctx *ctx, F fn) {
     return OCTPT_OK;
 }
 
-// grow-only device buffer of n elements on the current device
-template <class T>
-octpt_status grow_buf(octpt_ctx *ctx, T *&p, size_t &cap, size_t n) {
-    if (n <= cap) return OCTPT_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(ctx, hipMalloc(&p, n * sizeof(T)));
-    cap = n;
-    return OCTPT_OK;
-}
-
 // One render call over every device entry: scatter the caller's running mean (and segment counts) into the
 // entries' compact tile buffers, render each entry's shard, gather back.  R is the call's layout (on the
 // first device, stream s); the caller's buffers are read and written on s, the entries work on their own
@@ -1363,10 +1125,10 @@ octpt_status multi_render(octpt_ctx *ctx, const octpt_render_params &p, const De
     const uint32_t n = (uint32_t)ctx->sub.size();
     const size_t stride = (size_t)((R.shard_tiles + n - 1) / n) * 64u;  // the largest entry's pixels
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    octpt_status st = grow_buf(ctx, ctx->m_acc, ctx->m_acc_cap, stride * n);
-    if (st == OCTPT_OK && d_seg) st = grow_buf(ctx, ctx->m_seg, ctx->m_seg_cap, stride * n);
+    octpt_status st = grow_buf(ctx, ctx->m_acc, stride * n);
+    if (st == OCTPT_OK && d_seg) st = grow_buf(ctx, ctx->m_seg, stride * n);
     if (st != OCTPT_OK) return st;
-    HIP_TRY(ctx, launch_multi_stage(R, n, (uint32_t)stride, d_accum, d_seg, ctx->m_acc, ctx->m_seg, true, s));
+    HIP_TRY(ctx, launch_multi_stage(R, n, (uint32_t)stride, d_accum, d_seg, ctx->m_acc.p, ctx->m_seg.p, true, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     const bool megakernel = (p.flags & OCTPT_RENDER_MEGAKERNEL) != 0;
     st = for_each_sub(ctx, [&](size_t i) -> octpt_status {
@@ -1380,36 +1142,40 @@ octpt_status multi_render(octpt_ctx *ctx, const octpt_render_params &p, const De
         octpt_status r = make_render(c, &pi, Ri);
         if (r != OCTPT_OK || Ri.total_items == 0) return r;
         const size_t np = Ri.total_items;
-        if ((r = grow_buf(c, c->m_acc, c->m_acc_cap, np)) != OCTPT_OK) return r;
-        if (d_seg && (r = grow_buf(c, c->m_seg, c->m_seg_cap, np)) != OCTPT_OK) return r;
-        float4 *stage_acc = ctx->m_acc + i * stride;
-        uint32_t *stage_seg = d_seg ? ctx->m_seg + i * stride : nullptr;
-        HIP_TRY(c, hipMemcpyPeerAsync(c->m_acc, c->device, stage_acc, ctx->device, np * sizeof(float4), c->stream));
-        if (d_seg) HIP_TRY(c, hipMemcpyPeerAsync(c->m_seg, c->device, stage_seg, ctx->device, np * 4, c->stream));
-        r = enqueue_render(c, Ri, c->m_acc, d_seg ? c->m_seg : nullptr, c->stream, megakernel, cancel);
+        if ((r = grow_buf(c, c->m_acc, np)) != OCTPT_OK) return r;
+        if (d_seg && (r = grow_buf(c, c->m_seg, np)) != OCTPT_OK) return r;
+        float4 *stage_acc = ctx->m_acc.p + i * stride;
+        uint32_t *stage_seg = d_seg ? ctx->m_seg.p + i * stride : nullptr;
+        HIP_TRY(c, hipMemcpyPeerAsync(c->m_acc.p, c->device, stage_acc, ctx->device, np * sizeof(float4), c->stream));
+        if (d_seg) HIP_TRY(c, hipMemcpyPeerAsync(c->m_seg.p, c->device, stage_seg, ctx->device, np * 4, c->stream));
+        r = enqueue_render(c, Ri, c->m_acc.p, d_seg ? c->m_seg.p : nullptr, c->stream, megakernel, cancel);
         if (r != OCTPT_OK) {
             (void)hipStreamSynchronize(c->stream);
             return r;
         }
-        HIP_TRY(c, hipMemcpyPeerAsync(stage_acc, ctx->device, c->m_acc, c->device, np * sizeof(float4), c->stream));
-        if (d_seg) HIP_TRY(c, hipMemcpyPeerAsync(stage_seg, ctx->device, c->m_seg, c->device, np * 4, c->stream));
+        HIP_TRY(c, hipMemcpyPeerAsync(stage_acc, ctx->device, c->m_acc.p, c->device, np * sizeof(float4), c->stream));
+        if (d_seg) HIP_TRY(c, hipMemcpyPeerAsync(stage_seg, ctx->device, c->m_seg.p, c->device, np * 4, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return OCTPT_OK;
     });
     if (st != OCTPT_OK) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_multi_stage(R, n, (uint32_t)stride, d_accum, d_seg, ctx->m_acc, ctx->m_seg, false, s));
+    HIP_TRY(ctx, launch_multi_stage(R, n, (uint32_t)stride, d_accum, d_seg, ctx->m_acc.p, ctx->m_seg.p, false, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     ctx->kernel_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ctx->launches++;
     return OCTPT_OK;
 }
 
-void join_inflight(octpt_ctx *ctx) {
+}  // namespace
+
+void octpt::join_inflight(octpt_ctx *ctx) {
     octpt_frame *f = ctx->inflight;
     if (f && f->worker.joinable()) f->worker.join();
     ctx->inflight = nullptr;
 }
+
+namespace {
 
 void free_frame_buffers(octpt_frame *f) {
     if (f->d_accum) (void)hipFree(f->d_accum);
@@ -1839,21 +1605,11 @@ void octpt_destroy(octpt_ctx *ctx) {
     for (auto &ev : ctx->count_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->d_subs) (void)hipFree(ctx->d_subs);
-    if (ctx->d_beam) (void)hipFree(ctx->d_beam);
     if (ctx->beam_ev) (void)hipEventDestroy(ctx->beam_ev);
     if (ctx->d_order) (void)hipFree(ctx->d_order);
     if (ctx->d_order_pos) (void)hipFree(ctx->d_order_pos);
-    if (ctx->d_tiles) (void)hipFree(ctx->d_tiles);
-    if (ctx->d_tile_spp) (void)hipFree(ctx->d_tile_spp);
-    if (ctx->d_tile_err) (void)hipFree(ctx->d_tile_err);
-    for (void *q : {(void *)ctx->d_tile_spread, (void *)ctx->fin_normal, (void *)ctx->fin_albedo, (void *)ctx->fin_depth,
-                    (void *)ctx->fin_var})
-        if (q) (void)hipFree(q);
-    if (ctx->m_acc) (void)hipFree(ctx->m_acc);
-    if (ctx->m_seg) (void)hipFree(ctx->m_seg);
-    for (float4 *f : ctx->dn_frame)
-        if (f) (void)hipFree(f);
+    free_bufs(ctx->d_subs, ctx->d_beam, ctx->d_tiles, ctx->d_tile_spp, ctx->d_tile_err, ctx->d_tile_spread, ctx->fin_normal,
+              ctx->fin_albedo, ctx->fin_depth, ctx->fin_var, ctx->m_acc, ctx->m_seg, ctx->dn_frame[0], ctx->dn_frame[1]);
     if (ctx->d_stats) (void)hipFree(ctx->d_stats);
     if (ctx->d_lut_float) (void)hipFree(ctx->d_lut_float);
     if (ctx->d_lut_byte) (void)hipFree(ctx->d_lut_byte);
@@ -1866,7 +1622,7 @@ const char *octpt_last_error(const octpt_ctx *ctx) { return ctx ? ctx->err.c_str
 octpt_status octpt_scene_upload(octpt_ctx *ctx, const octpt_scene_desc *d) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     join_inflight(ctx);
-    try {
+    try {  // (not guarded(): the handlers drop the half-made scene, here and in build_scene_device)
         if (is_multi(ctx)) return scene_on_every_sub(ctx, [&](octpt_ctx *c) { return octpt_scene_upload(c, d); });
         std::vector<uint16_t> masks;  // reader-form child masks (C21)
         octpt_status st = validate_scene(ctx, d, masks);
@@ -2023,7 +1779,7 @@ octpt_status octpt_render_device(octpt_ctx *ctx, const octpt_render_params *p, f
                                  void *stream) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     if (!d_accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "d_accum NULL");
-    try {
+    return guarded(ctx, "render", [&]() -> octpt_status {
         join_inflight(ctx);
         DevRender R{};
         octpt_status st = make_render(ctx, p, R);
@@ -2033,9 +1789,7 @@ octpt_status octpt_render_device(octpt_ctx *ctx, const octpt_render_params *p, f
                                 nullptr);
         return enqueue_render(ctx, R, reinterpret_cast<float4 *>(d_accum), d_seg, static_cast<hipStream_t>(stream),
                               (p->flags & OCTPT_RENDER_MEGAKERNEL) != 0);
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render");
-    }
+    });
 }
 
 namespace {
@@ -2191,7 +1945,7 @@ octpt_status octpt_unshard_device(octpt_ctx *ctx, uint32_t W, uint32_t H, uint32
 octpt_status octpt_set_tile_order(octpt_ctx *ctx, uint32_t width, uint32_t height, const uint32_t *order) {
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     join_inflight(ctx);
-    try {
+    try {  // (not guarded(): this entry's message names no entry)
         // validated once, before any entry changes (a failure part-way through a multi-device
         // context's entries must not leave them dealing differently)
         uint32_t T = 0;
@@ -2295,1035 +2049,49 @@ octpt_status octpt_intersect(octpt_ctx *ctx, const float *rays, const uint32_t *
     if (!ctx->has_scene) return fail(ctx, OCTPT_ERR_INVALID_ARG, "no scene uploaded");
     if (n == 0) return OCTPT_OK;
     if (!rays || !t || !prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, "NULL buffer");
-    if (is_multi(ctx)) {  // one batch on the first entry's replica
-        const octpt_status st = octpt_intersect(ctx->sub[0], rays, last_prim, last_normal, n, t, prim, normal, steps);
-        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-    }
-    // esvo_begin's t_coef = 1 / -|d| comes from rcp_rn, exact for |d| in [2^-23, 2^126] (smaller
-    // components are clamped to 2^-23 first, octree_traversal.rs:86-93): a ray with a non-finite
-    // component or a direction component |d| > 2^126 is outside that range.  Such a ray is reported as a
-    // miss -- t = +inf, prim = none, normal 0, 0 steps -- and the rest of the batch is traced as usual (the
-    // kernel sees a placeholder ray in its place).  For a non-finite ray this is what the reference's
-    // comparisons with NaN t-values give.  For a finite direction above 2^126 it is a DELIBERATE DEVIATION:
-    // the reference does not normalise directions (Ray::new, ray/mod.rs:32), its t_coef would be subnormal
-    // (octree_traversal.rs:95) and its walk could still hit something; no reference fixture covers that
-    // case (parity unpinned), and the render kernels never produce such a direction.
-    std::vector<uint32_t> unsupported;
-    std::vector<float> clean;
-    for (size_t i = 0; i < (size_t)n * 6; ++i) {
-        const float v = rays[i];
-        if (!std::isfinite(v) || (i % 6 >= 3 && std::fabs(v) > 0x1p126f)) {
-            if (clean.empty()) clean.assign(rays, rays + (size_t)n * 6);
-            const size_t r = i / 6;
-            if (unsupported.empty() || unsupported.back() != r) unsupported.push_back((uint32_t)r);
-            for (int k = 0; k < 6; ++k) clean[r * 6 + k] = k == 3 ? 1.0f : 0.0f;
-        }
-    }
-    if (!clean.empty()) rays = clean.data();
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float *d_rays = nullptr, *d_ln = nullptr, *d_t = nullptr, *d_n = nullptr;
-    uint32_t *d_lp = nullptr, *d_p = nullptr, *d_s = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_rays, (void *)d_ln, (void *)d_t, (void *)d_n, (void *)d_lp, (void *)d_p, (void *)d_s})
-            if (q) (void)hipFree(q);
-    };
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = hipMalloc(&d_rays, (size_t)n * 24)) != hipSuccess) break;
-        if ((e = hipMemcpy(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice)) != hipSuccess) break;
-        if (last_prim) {
-            if ((e = hipMalloc(&d_lp, (size_t)n * 4)) != hipSuccess) break;
-            if ((e = hipMemcpy(d_lp, last_prim, (size_t)n * 4, hipMemcpyHostToDevice)) != hipSuccess) break;
-        }
-        if (last_normal) {
-            if ((e = hipMalloc(&d_ln, (size_t)n * 12)) != hipSuccess) break;
-            if ((e = hipMemcpy(d_ln, last_normal, (size_t)n * 12, hipMemcpyHostToDevice)) != hipSuccess) break;
-        }
-        if ((e = hipMalloc(&d_t, (size_t)n * 4)) != hipSuccess) break;
-        if ((e = hipMalloc(&d_p, (size_t)n * 4)) != hipSuccess) break;
-        if (normal && (e = hipMalloc(&d_n, (size_t)n * 12)) != hipSuccess) break;
-        if (steps && (e = hipMalloc(&d_s, (size_t)n * 4)) != hipSuccess) break;
-        if ((e = launch_intersect(ctx->S, d_rays, d_lp, d_ln, n, d_t, d_p, d_n, d_s, ctx->stream)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
-        if ((e = hipMemcpy(t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) break;
-        if ((e = hipMemcpy(prim, d_p, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) break;
-        if (normal && (e = hipMemcpy(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost)) != hipSuccess) break;
-        if (steps && (e = hipMemcpy(steps, d_s, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    } while (0);
-    cleanup();
-    if (e != hipSuccess) return hip_fail(ctx, e, "intersect");
-    for (uint32_t r : unsupported) {
-        t[r] = INFINITY;
-        prim[r] = 0xFFFFFFFFu;
-        if (normal) normal[3 * (size_t)r] = normal[3 * (size_t)r + 1] = normal[3 * (size_t)r + 2] = 0.0f;
-        if (steps) steps[r] = 0u;
-    }
-    return OCTPT_OK;
-}
-
-// ---------------- first-hit guide buffers (C24) and the preview denoiser (C25) ----------------
-namespace {
-
-// the render layout of a guide-buffer pass: only the frame size, the shard and the compact flag apply
-octpt_status make_aov_render(octpt_ctx *ctx, const octpt_render_params *p, DevRender &R) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
-    octpt_render_params q{};
-    q.width = p->width;
-    q.height = p->height;
-    q.spp_count = 1u;
-    q.max_depth = 1u;
-    q.branch_count = 1u;
-    q.shard_index = p->shard_index;
-    q.shard_count = p->shard_count;
-    q.flags = p->flags & OCTPT_RENDER_SHARD_COMPACT;
-    const bool ktiming = ctx->ktiming;
-    const octpt_status st = make_render(ctx, &q, R);
-    ctx->ktiming = ktiming;
-    return st;
-}
-
-bool aov_any(const octpt_aov_buffers &b) { return b.albedo || b.normal || b.depth || b.prim || b.material; }
-
-octpt_status enqueue_aov(octpt_ctx *ctx, const DevRender &R, const octpt_aov_buffers &dev, hipStream_t s) {
-    if (R.total_items == 0 || !aov_any(dev)) return OCTPT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    EventPair ev{};
-    HIP_TRY(ctx, hipEventCreate(&ev.start));
-    HIP_TRY(ctx, hipEventCreate(&ev.stop));
-    ctx->pending.push_back(ev);  // destroyed by get_stats / destroy
-    HIP_TRY(ctx, hipEventRecord(ev.start, s));
-    const DevAov out{reinterpret_cast<float4 *>(dev.albedo), reinterpret_cast<float4 *>(dev.normal), dev.depth, dev.prim,
-                     dev.material};
-    const hipError_t e = launch_gbuffer(ctx->S, ctx->C, R, out, ctx->d_stats, s);
-    HIP_TRY(ctx, hipEventRecord(ev.stop, s));
-    if (e != hipSuccess) return hip_fail(ctx, e, "guide buffer launch");
-    ctx->launches++;
-    return OCTPT_OK;
-}
-
-octpt_status check_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const void *color,
-                           const octpt_aov_buffers *g, const void *out) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise params NULL");
-    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: zero frame size");
-    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: bad resolution");
-    if (p->iterations < 1u || p->iterations > 5u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: iterations must be 1..5");
-    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_depth})
-        if (!(s > 0.0f) || !std::isfinite(s))
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: sigma_color, sigma_normal and sigma_depth must be positive and finite");
-    if (p->flags & ~OCTPT_DENOISE_DEMODULATE)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG,
-                    "denoise: unknown flag (full frames only: no shard or compact tile layout; OCTPT_DENOISE_DEMODULATE is the one flag)");
-    if (!color || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: NULL colour or output buffer");
-    if (!g || !g->normal || !g->depth)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: the normal and depth guides are required");
-    if ((p->flags & OCTPT_DENOISE_DEMODULATE) && !g->albedo)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise: OCTPT_DENOISE_DEMODULATE needs the albedo guide");
-    return OCTPT_OK;
-}
-
-}  // namespace
-
-octpt_status octpt_render_aov_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_aov_buffers *dev,
-                                     void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
-    if (!dev) return fail(ctx, OCTPT_ERR_INVALID_ARG, "guide buffers NULL");
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {  // on the first entry's replica (the caller's buffers live on its device)
-            const octpt_status st = octpt_render_aov_device(ctx->sub[0], p, dev, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        DevRender R{};
-        const octpt_status st = make_aov_render(ctx, p, R);
-        if (st != OCTPT_OK) return st;
-        return enqueue_aov(ctx, R, *dev, static_cast<hipStream_t>(stream));
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in guide buffer render");
-    }
-}
-
-octpt_status octpt_render_aov(octpt_ctx *ctx, const octpt_render_params *p, const octpt_aov_buffers *host) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render params NULL");
-    if (!host) return fail(ctx, OCTPT_ERR_INVALID_ARG, "guide buffers NULL");
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            const octpt_status st = octpt_render_aov(ctx->sub[0], p, host);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        DevRender R{};
-        octpt_status st = make_aov_render(ctx, p, R);
-        if (st != OCTPT_OK) return st;
-        if (R.total_items == 0 || !aov_any(*host)) return OCTPT_OK;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = accum_pixels(R);
-        // bytes per pixel of the five buffers, in octpt_aov_buffers order
-        void *const h[5] = {host->albedo, host->normal, host->depth, host->prim, host->material};
-        const size_t bpp[5] = {16, 16, 4, 4, 4};
-        void *d[5] = {};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-            if (!h[i]) continue;
-            // pixels the pass does not write (a partial shard of a full frame, tile padding) keep the caller's values
-            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) {
-            const octpt_aov_buffers dev{static_cast<float *>(d[0]), static_cast<float *>(d[1]), static_cast<float *>(d[2]),
-                                        static_cast<uint32_t *>(d[3]), static_cast<uint32_t *>(d[4])};
-            st = enqueue_aov(ctx, R, dev, ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-        }
-        for (int i = 0; i < 5 && e == hipSuccess && st == OCTPT_OK; ++i)
-            if (h[i]) e = hipMemcpy(h[i], d[i], n * bpp[i], hipMemcpyDeviceToHost);
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "guide buffer render");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in guide buffer render");
-    }
-}
-
-octpt_status octpt_denoise_device(octpt_ctx *ctx, const octpt_denoise_params *p, const float *d_color,
-                                  const octpt_aov_buffers *g, float *d_out, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_denoise(ctx, p, d_color, g, d_out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_denoise_device(ctx->sub[0], p, d_color, g, d_out, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        // the working signal lives in frame 0 after the prep pass, then ping-pongs; the last iteration writes d_out.
-        // A frame that has to grow may still be read by an earlier call on another stream: drain first
-        const bool two = p->iterations > 1u;
-        if (n > ctx->dn_cap[0] || (two && n > ctx->dn_cap[1])) HIP_TRY(ctx, hipDeviceSynchronize());
-        if ((st = grow_buf(ctx, ctx->dn_frame[0], ctx->dn_cap[0], n)) != OCTPT_OK) return st;
-        if (two && (st = grow_buf(ctx, ctx->dn_frame[1], ctx->dn_cap[1], n)) != OCTPT_OK) return st;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        DevDenoise D{};
-        D.W = p->width;
-        D.H = p->height;
-        D.sigma_color = p->sigma_color;
-        D.sn2 = p->sigma_normal * p->sigma_normal;
-        D.sz2 = p->sigma_depth * p->sigma_depth;
-        D.normal = reinterpret_cast<const float4 *>(g->normal);
-        D.albedo = (p->flags & OCTPT_DENOISE_DEMODULATE) ? reinterpret_cast<const float4 *>(g->albedo) : nullptr;
-        D.depth = g->depth;
-        HIP_TRY(ctx, launch_denoise_prep(D.W, D.H, reinterpret_cast<const float4 *>(d_color), D.albedo, D.depth,
-                                         ctx->dn_frame[0], s));
-        for (uint32_t i = 0; i < p->iterations; ++i) {
-            const bool last = i + 1u == p->iterations;
-            float4 *dst = last ? reinterpret_cast<float4 *>(d_out) : ctx->dn_frame[(i + 1u) & 1u];
-            HIP_TRY(ctx, launch_atrous(D, i, last, ctx->dn_frame[i & 1u], dst, s));
-        }
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise");
-    }
-}
-
-octpt_status octpt_denoise(octpt_ctx *ctx, const octpt_denoise_params *p, const float *color,
-                           const octpt_aov_buffers *g, float *out) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_denoise(ctx, p, color, g, out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_denoise(ctx->sub[0], p, color, g, out);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
-        // colour (filtered in place on the device), normal, depth, albedo
-        const void *h[4] = {color, g->normal, g->depth, demod ? g->albedo : nullptr};
-        const size_t bpp[4] = {16, 16, 4, 16};
-        void *d[4] = {};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) {
-            if (!h[i]) continue;
-            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) {
-            const octpt_aov_buffers dg{static_cast<float *>(d[3]), static_cast<float *>(d[1]), static_cast<float *>(d[2]),
-                                       nullptr, nullptr};
-            st = octpt_denoise_device(ctx, p, static_cast<float *>(d[0]), &dg, static_cast<float *>(d[0]), ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "denoise");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise");
-    }
-}
-
-// ---------------- temporal reprojection of the preview history (C26) ----------------
-namespace {
-
-// `who` names the pass in the messages; moments: the C27 entries, which also accept OCTPT_TEMPORAL_DEMODULATE
-octpt_status check_temporal(octpt_ctx *ctx, const char *who, bool moments, const octpt_temporal_params *p, const void *color,
-                            const octpt_aov_buffers *g, const octpt_temporal_history *prev, const void *out,
-                            const void *out_length) {
-    const std::string w = std::string(who) + ": ";
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, std::string(who) + " params NULL");
-    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "zero frame size");
-    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "bad resolution");
-    if (p->max_history < 1u || p->max_history > 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "max_history must be 1..65535");
-    if (!(p->depth_tolerance > 0.0f) || !std::isfinite(p->depth_tolerance))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "depth_tolerance must be positive and finite");
-    if (!(p->normal_threshold >= -1.0f && p->normal_threshold <= 1.0f))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "normal_threshold must be in [-1, 1]");
-    if (p->flags & ~(OCTPT_TEMPORAL_MATCH_PRIM | (moments ? OCTPT_TEMPORAL_DEMODULATE : 0u)))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG,
-                    w + (moments ? "unknown flag (full frames only: no shard or compact tile layout; OCTPT_TEMPORAL_MATCH_PRIM and OCTPT_TEMPORAL_DEMODULATE are the flags)"
-                                 : "unknown flag (full frames only: no shard or compact tile layout; OCTPT_TEMPORAL_MATCH_PRIM is the one flag)"));
-    const char *why = nullptr;
-    const octpt_status st = check_reproject_cameras(&p->camera, &p->prev_camera, &why);
-    if (st != OCTPT_OK) return fail(ctx, st, w + why);
-    const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
-    if (!color || !out || !out_length) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "NULL colour, output or output length buffer");
-    if (!g || !g->normal || !g->depth) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the normal and depth guides are required");
-    if (match && !g->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "OCTPT_TEMPORAL_MATCH_PRIM needs the prim guide");
-    if ((p->flags & OCTPT_TEMPORAL_DEMODULATE) && !g->albedo)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "OCTPT_TEMPORAL_DEMODULATE needs the albedo guide");
-    if (prev) {
-        if (!prev->color || !prev->normal || !prev->depth || !prev->length)
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the history needs its colour, normal, depth and length");
-        if (match && !prev->prim) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "OCTPT_TEMPORAL_MATCH_PRIM needs the history's prim");
-        // the pass gathers from the history while it writes: only the current colour may be the output
-        if (out == prev->color) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the output must not be the history colour");
-        if (out_length == prev->length)
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "the output length must not be the history length");
-    }
-    return OCTPT_OK;
-}
-
-// C27's own arguments, after check_temporal
-octpt_status check_moments(octpt_ctx *ctx, const octpt_temporal_history *prev, const void *prev_moments,
-                           const void *out_moments) {
-    if (!out_moments) return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: NULL output moments buffer");
-    if (prev && !prev_moments)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: a history needs its moments");
-    if (!prev && prev_moments)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: previous moments without a history (the first frame takes neither)");
-    if (out_moments == prev_moments)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "temporal_moments: the output moments must not be the history moments");
-    return OCTPT_OK;
-}
-
-DevCamera dev_camera(const octpt_camera &c) {
-    const CameraBasis b = camera_basis(c.eye, c.direction, c.up, c.fov);
-    DevCamera C{};
-    std::memcpy(C.eye, b.eye, 12);
-    std::memcpy(C.dir, b.dir, 12);
-    std::memcpy(C.right, b.right, 12);
-    std::memcpy(C.up, b.up, 12);
-    C.d_factor = b.d_factor;
-    return C;
-}
-
-}  // namespace
-
-namespace {
-
-// both temporal entries' device form after their checks; d_out_moments NULL = octpt_temporal_device (C26)
-octpt_status enqueue_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color, const octpt_aov_buffers *g,
-                              const octpt_temporal_history *prev, const float *d_prev_moments, float *d_out,
-                              uint32_t *d_out_length, float *d_out_moments, void *stream) {
-    join_inflight(ctx);
-    if (is_multi(ctx)) {
-        const octpt_status st = d_out_moments
-                                    ? octpt_temporal_moments_device(ctx->sub[0], p, d_color, g, prev, d_prev_moments, d_out,
-                                                                    d_out_length, d_out_moments, stream)
-                                    : octpt_temporal_device(ctx->sub[0], p, d_color, g, prev, d_out, d_out_length, stream);
-        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
-    DevTemporal T{};
-    T.W = p->width;
-    T.H = p->height;
-    T.dim = (float)(p->width > p->height ? p->width : p->height);
-    T.cur = dev_camera(p->camera);
-    T.prev = dev_camera(p->prev_camera);
-    T.max_history = p->max_history;
-    T.depth_tolerance = p->depth_tolerance;
-    T.normal_threshold = p->normal_threshold;
-    T.match_prim = match ? 1u : 0u;
-    T.color = reinterpret_cast<const float4 *>(d_color);
-    T.normal = reinterpret_cast<const float4 *>(g->normal);
-    T.depth = g->depth;
-    T.prim = match ? g->prim : nullptr;
-    if (prev) {
-        T.h_color = reinterpret_cast<const float4 *>(prev->color);
-        T.h_normal = reinterpret_cast<const float4 *>(prev->normal);
-        T.h_depth = prev->depth;
-        T.h_prim = match ? prev->prim : nullptr;
-        T.h_length = prev->length;
-        T.h_moments = reinterpret_cast<const float2 *>(d_prev_moments);
-    }
-    T.out = reinterpret_cast<float4 *>(d_out);
-    T.out_length = d_out_length;
-    T.albedo = (p->flags & OCTPT_TEMPORAL_DEMODULATE) ? reinterpret_cast<const float4 *>(g->albedo) : nullptr;
-    T.out_moments = reinterpret_cast<float2 *>(d_out_moments);
-    HIP_TRY(ctx, launch_temporal(T, d_out_moments != nullptr, static_cast<hipStream_t>(stream)));
-    return OCTPT_OK;
-}
-
-// both temporal entries' host form after their checks; out_moments NULL = octpt_temporal (C26)
-octpt_status temporal_host(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color, const octpt_aov_buffers *g,
-                           const octpt_temporal_history *prev, const float *prev_moments, float *out, uint32_t *out_length,
-                           float *out_moments) {
-    join_inflight(ctx);
-    if (is_multi(ctx)) {
-        const octpt_status st =
-            out_moments ? octpt_temporal_moments(ctx->sub[0], p, color, g, prev, prev_moments, out, out_length, out_moments)
-                        : octpt_temporal(ctx->sub[0], p, color, g, prev, out, out_length);
-        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)p->width * p->height;
-    const bool match = (p->flags & OCTPT_TEMPORAL_MATCH_PRIM) != 0u;
-    const bool demod = (p->flags & OCTPT_TEMPORAL_DEMODULATE) != 0u;
-    // colour (blended in place on the device), normal, depth, prim; the history's five; albedo and the history's
-    // moments (C27); then the two outputs
-    const void *h[11] = {color, g->normal, g->depth, match ? g->prim : nullptr,
-                         prev ? prev->color : nullptr, prev ? prev->normal : nullptr, prev ? prev->depth : nullptr,
-                         prev && match ? prev->prim : nullptr, prev ? prev->length : nullptr,
-                         demod ? g->albedo : nullptr, prev ? prev_moments : nullptr};
-    const size_t bpp[11] = {16, 16, 4, 4, 16, 16, 4, 4, 4, 16, 8};
-    void *d[13] = {};
-    octpt_status st = OCTPT_OK;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 11 && e == hipSuccess; ++i) {
-        if (!h[i]) continue;
-        if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMalloc(&d[11], n * 4);
-    if (e == hipSuccess && out_moments) e = hipMalloc(&d[12], n * 8);
-    if (e == hipSuccess) {
-        const octpt_aov_buffers dg{static_cast<float *>(d[9]), static_cast<float *>(d[1]), static_cast<float *>(d[2]),
-                                   static_cast<uint32_t *>(d[3]), nullptr};
-        const octpt_temporal_history dp{static_cast<float *>(d[4]), static_cast<float *>(d[5]), static_cast<float *>(d[6]),
-                                        static_cast<uint32_t *>(d[7]), static_cast<uint32_t *>(d[8])};
-        st = enqueue_temporal(ctx, p, static_cast<float *>(d[0]), &dg, prev ? &dp : nullptr, static_cast<float *>(d[10]),
-                              static_cast<float *>(d[0]), static_cast<uint32_t *>(d[11]), static_cast<float *>(d[12]),
-                              ctx->stream);
-        if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-        if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
-        if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out_length, d[11], n * 4, hipMemcpyDeviceToHost);
-        if (st == OCTPT_OK && e == hipSuccess && out_moments) e = hipMemcpy(out_moments, d[12], n * 8, hipMemcpyDeviceToHost);
-    }
-    for (void *q : d)
-        if (q) (void)hipFree(q);
-    if (st != OCTPT_OK) return st;
-    if (e != hipSuccess) return hip_fail(ctx, e, "temporal");
-    return OCTPT_OK;
-}
-
-}  // namespace
-
-octpt_status octpt_temporal_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
-                                   const octpt_aov_buffers *g, const octpt_temporal_history *prev, float *d_out,
-                                   uint32_t *d_out_length, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    const octpt_status st = check_temporal(ctx, "temporal", false, p, d_color, g, prev, d_out, d_out_length);
-    if (st != OCTPT_OK) return st;
-    try {
-        return enqueue_temporal(ctx, p, d_color, g, prev, nullptr, d_out, d_out_length, nullptr, stream);
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
-    }
-}
-
-octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color,
-                            const octpt_aov_buffers *g, const octpt_temporal_history *prev, float *out,
-                            uint32_t *out_length) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    const octpt_status st = check_temporal(ctx, "temporal", false, p, color, g, prev, out, out_length);
-    if (st != OCTPT_OK) return st;
-    try {
-        return temporal_host(ctx, p, color, g, prev, nullptr, out, out_length, nullptr);
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal");
-    }
-}
-
-// ---------------- luminance moments, variance and the variance-guided filter (C27-C29) ----------------
-octpt_status octpt_temporal_moments_device(octpt_ctx *ctx, const octpt_temporal_params *p, const float *d_color,
-                                           const octpt_aov_buffers *g, const octpt_temporal_history *prev,
-                                           const float *d_prev_moments, float *d_out, uint32_t *d_out_length,
-                                           float *d_out_moments, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_temporal(ctx, "temporal_moments", true, p, d_color, g, prev, d_out, d_out_length);
-    if (st == OCTPT_OK) st = check_moments(ctx, prev, d_prev_moments, d_out_moments);
-    if (st != OCTPT_OK) return st;
-    try {
-        return enqueue_temporal(ctx, p, d_color, g, prev, d_prev_moments, d_out, d_out_length, d_out_moments, stream);
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal_moments");
-    }
-}
-
-octpt_status octpt_temporal_moments(octpt_ctx *ctx, const octpt_temporal_params *p, const float *color,
-                                    const octpt_aov_buffers *g, const octpt_temporal_history *prev,
-                                    const float *prev_moments, float *out, uint32_t *out_length, float *out_moments) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_temporal(ctx, "temporal_moments", true, p, color, g, prev, out, out_length);
-    if (st == OCTPT_OK) st = check_moments(ctx, prev, prev_moments, out_moments);
-    if (st != OCTPT_OK) return st;
-    try {
-        return temporal_host(ctx, p, color, g, prev, prev_moments, out, out_length, out_moments);
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in temporal_moments");
-    }
-}
-
-namespace {
-
-octpt_status check_variance(octpt_ctx *ctx, const octpt_variance_params *p, const void *moments, const void *length,
-                            const octpt_aov_buffers *g, const void *out) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance params NULL");
-    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: zero frame size");
-    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: bad resolution");
-    if (p->min_history < 1u || p->min_history > 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: min_history must be 1..65535");
-    for (float s : {p->sigma_normal, p->sigma_depth})
-        if (!(s > 0.0f) || !std::isfinite(s))
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: sigma_normal and sigma_depth must be positive and finite");
-    if (!moments || !length || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: NULL moments, length or output buffer");
-    if (!g || !g->normal || !g->depth)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "variance: the normal and depth guides are required");
-    return OCTPT_OK;
-}
-
-octpt_status check_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const void *color,
-                                    const void *variance, const octpt_aov_buffers *g, const void *out) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance params NULL");
-    if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: zero frame size");
-    if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: bad resolution");
-    if (p->iterations < 1u || p->iterations > 5u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: iterations must be 1..5");
-    for (float s : {p->sigma_luminance, p->luminance_floor, p->sigma_normal, p->sigma_depth})
-        if (!(s > 0.0f) || !std::isfinite(s))
-            return fail(ctx, OCTPT_ERR_INVALID_ARG,
-                        "denoise_variance: sigma_luminance, luminance_floor, sigma_normal and sigma_depth must be positive and finite");
-    if (p->flags & ~OCTPT_DENOISE_DEMODULATE)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG,
-                    "denoise_variance: unknown flag (full frames only: no shard or compact tile layout; OCTPT_DENOISE_DEMODULATE is the one flag)");
-    if (!color || !variance || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: NULL colour, variance or output buffer");
-    if (!g || !g->normal || !g->depth)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: the normal and depth guides are required");
-    if ((p->flags & OCTPT_DENOISE_DEMODULATE) && !g->albedo)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "denoise_variance: OCTPT_DENOISE_DEMODULATE needs the albedo guide");
-    return OCTPT_OK;
-}
-
-}  // namespace
-
-octpt_status octpt_variance_device(octpt_ctx *ctx, const octpt_variance_params *p, const float *d_moments,
-                                   const uint32_t *d_length, const octpt_aov_buffers *g, float *d_out, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_variance(ctx, p, d_moments, d_length, g, d_out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_variance_device(ctx->sub[0], p, d_moments, d_length, g, d_out, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        DevVariance V{};
-        V.W = p->width;
-        V.H = p->height;
-        V.min_history = p->min_history;
-        V.sn2 = p->sigma_normal * p->sigma_normal;
-        V.sz2 = p->sigma_depth * p->sigma_depth;
-        V.moments = reinterpret_cast<const float2 *>(d_moments);
-        V.length = d_length;
-        V.normal = reinterpret_cast<const float4 *>(g->normal);
-        V.depth = g->depth;
-        V.out = d_out;
-        HIP_TRY(ctx, launch_variance(V, static_cast<hipStream_t>(stream)));
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in variance");
-    }
-}
-
-octpt_status octpt_variance(octpt_ctx *ctx, const octpt_variance_params *p, const float *moments, const uint32_t *length,
-                            const octpt_aov_buffers *g, float *out) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_variance(ctx, p, moments, length, g, out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_variance(ctx->sub[0], p, moments, length, g, out);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        const void *h[4] = {moments, length, g->normal, g->depth};  // then the output
-        const size_t bpp[4] = {8, 4, 16, 4};
-        void *d[5] = {};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 4 && e == hipSuccess; ++i)
-            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&d[4], n * 4);
-        if (e == hipSuccess) {
-            const octpt_aov_buffers dg{nullptr, static_cast<float *>(d[2]), static_cast<float *>(d[3]), nullptr, nullptr};
-            st = octpt_variance_device(ctx, p, static_cast<float *>(d[0]), static_cast<uint32_t *>(d[1]), &dg,
-                                       static_cast<float *>(d[4]), ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[4], n * 4, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "variance");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in variance");
-    }
-}
-
-octpt_status octpt_denoise_variance_device(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const float *d_color,
-                                           const float *d_variance, const octpt_aov_buffers *g, float *d_out,
-                                           float *d_out_variance, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_denoise_variance(ctx, p, d_color, d_variance, g, d_out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_denoise_variance_device(ctx->sub[0], p, d_color, d_variance, g, d_out, d_out_variance, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        // octpt_denoise_device's two frames and its rule: (s.rgb, v) lives in frame 0 after the prep pass, then
-        // ping-pongs; the last iteration writes the caller's buffers.  A frame that has to grow may still be read by
-        // an earlier call on another stream: drain first
-        const bool two = p->iterations > 1u;
-        if (n > ctx->dn_cap[0] || (two && n > ctx->dn_cap[1])) HIP_TRY(ctx, hipDeviceSynchronize());
-        if ((st = grow_buf(ctx, ctx->dn_frame[0], ctx->dn_cap[0], n)) != OCTPT_OK) return st;
-        if (two && (st = grow_buf(ctx, ctx->dn_frame[1], ctx->dn_cap[1], n)) != OCTPT_OK) return st;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        DevDenoiseVar D{};
-        D.W = p->width;
-        D.H = p->height;
-        D.sigma_luminance = p->sigma_luminance;
-        D.luminance_floor = p->luminance_floor;
-        D.sn2 = p->sigma_normal * p->sigma_normal;
-        D.sz2 = p->sigma_depth * p->sigma_depth;
-        D.normal = reinterpret_cast<const float4 *>(g->normal);
-        D.albedo = (p->flags & OCTPT_DENOISE_DEMODULATE) ? reinterpret_cast<const float4 *>(g->albedo) : nullptr;
-        D.depth = g->depth;
-        D.color = reinterpret_cast<const float4 *>(d_color);
-        D.out = reinterpret_cast<float4 *>(d_out);
-        D.out_variance = d_out_variance;
-        HIP_TRY(ctx, launch_denoise_var_prep(D.W, D.H, D.color, d_variance, D.albedo, D.depth, ctx->dn_frame[0], s));
-        for (uint32_t i = 0; i < p->iterations; ++i) {
-            const bool last = i + 1u == p->iterations;
-            HIP_TRY(ctx, launch_atrous_var(D, i, last, ctx->dn_frame[i & 1u], last ? nullptr : ctx->dn_frame[(i + 1u) & 1u], s));
-        }
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise_variance");
-    }
-}
-
-octpt_status octpt_denoise_variance(octpt_ctx *ctx, const octpt_denoise_variance_params *p, const float *color,
-                                    const float *variance, const octpt_aov_buffers *g, float *out, float *out_variance) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_denoise_variance(ctx, p, color, variance, g, out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_denoise_variance(ctx->sub[0], p, color, variance, g, out, out_variance);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
-        // colour and variance (both filtered in place on the device), normal, depth, albedo
-        const void *h[5] = {color, variance, g->normal, g->depth, demod ? g->albedo : nullptr};
-        const size_t bpp[5] = {16, 4, 16, 4, 16};
-        void *d[5] = {};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-            if (!h[i]) continue;
-            if ((e = hipMalloc(&d[i], n * bpp[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], n * bpp[i], hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) {
-            const octpt_aov_buffers dg{static_cast<float *>(d[4]), static_cast<float *>(d[2]), static_cast<float *>(d[3]),
-                                       nullptr, nullptr};
-            st = octpt_denoise_variance_device(ctx, p, static_cast<float *>(d[0]), static_cast<float *>(d[1]), &dg,
-                                               static_cast<float *>(d[0]), out_variance ? static_cast<float *>(d[1]) : nullptr,
-                                               ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[0], n * 16, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && out_variance) e = hipMemcpy(out_variance, d[1], n * 4, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "denoise_variance");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in denoise_variance");
-    }
-}
-
-// ---------------- adaptive sampling: tile-list renders, sample moments, per-tile error ----------------
-namespace {
-
-// what a tile-list render refuses of the render parameters and the context (C30), before anything else is read
-octpt_status check_tile_render(octpt_ctx *ctx, const char *who, const octpt_render_params *p) {
-    const std::string w(who);
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + ": render params NULL");
-    if (p->flags & (OCTPT_RENDER_MEGAKERNEL | OCTPT_RENDER_PREVIEW))
-        return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + ": the wavefront path only (no megakernel, no preview)");
-    if (is_multi(ctx)) return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + ": not on a multi-device context");
-    if (p->shard_count != 1u || p->shard_index != 0u || (p->flags & OCTPT_RENDER_SHARD_COMPACT))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + ": full frames of one shard only (shard_count 1, no compact layout)");
-    if (!ctx->h_order.empty())
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, w + ": a tile order is set on the context (octpt_set_tile_order; NULL resets it)");
-    return OCTPT_OK;
-}
-
-// octpt_render_tiles_device after its NULL checks
-octpt_status render_tiles(octpt_ctx *ctx, const octpt_render_params *p, const uint32_t *tiles, uint32_t n_tiles,
-                          float4 *d_accum, float2 *d_moments, uint32_t *d_seg, hipStream_t s) {
-    octpt_status st = check_tile_render(ctx, "render_tiles", p);
-    if (st != OCTPT_OK) return st;
-    join_inflight(ctx);
-    DevRender R{};
-    if ((st = make_render(ctx, p, R)) != OCTPT_OK) return st;
-    uint64_t list = 0;
-    if (tiles) {
-        const uint32_t T = R.tiles_x * ((R.H + kTile - 1) / kTile);
-        if (n_tiles > T) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_tiles: more tiles than the frame has (a duplicate)");
-        std::vector<uint8_t> seen(T, 0);
-        for (uint32_t i = 0; i < n_tiles; ++i) {
-            if (tiles[i] >= T) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_tiles: tile index outside the frame");
-            if (seen[tiles[i]]) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_tiles: duplicate tile index");
-            seen[tiles[i]] = 1;
-        }
-        if (n_tiles == 0 || p->spp_count == 0) return OCTPT_OK;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        // the list is the deal.  An earlier render on any stream may still read the table: drain before overwriting
-        // it, as the branch schedule's and the tile order's tables do
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        if ((st = grow_buf(ctx, ctx->d_tiles, ctx->tiles_cap, (size_t)n_tiles)) != OCTPT_OK) return st;
-        HIP_TRY(ctx, hipMemcpy(ctx->d_tiles, tiles, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
-        R.tile_order = ctx->d_tiles;
-        R.shard_tiles = n_tiles;
-        R.total_items = n_tiles * 64u;
-        R.div_items = udiv_magic(R.total_items);
-        list = ++ctx->list_gen;
-    }
-    return enqueue_render(ctx, R, d_accum, d_seg, s, false, nullptr, d_moments, list);
-}
-
-octpt_status check_tile_error(octpt_ctx *ctx, const octpt_tile_error_params *p, const void *moments, const void *tile_spp,
-                              const void *error) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error params NULL");
-    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error: bad resolution");
-    if (!(p->luminance_floor > 0.0f) || !std::isfinite(p->luminance_floor))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error: luminance_floor must be positive and finite");
-    if (!moments || !tile_spp || !error)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error: NULL moments, tile_spp or error buffer");
-    return OCTPT_OK;
-}
-
-uint32_t frame_tiles(uint32_t W, uint32_t H) { return ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile); }
-
-}  // namespace
-
-octpt_status octpt_render_tiles_device(octpt_ctx *ctx, const octpt_render_params *p, const uint32_t *tiles,
-                                       uint32_t n_tiles, float *d_accum, float *d_moments, uint32_t *d_seg,
-                                       void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    if (!d_accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "d_accum NULL");
-    try {
-        return render_tiles(ctx, p, tiles, n_tiles, reinterpret_cast<float4 *>(d_accum),
-                            reinterpret_cast<float2 *>(d_moments), d_seg, static_cast<hipStream_t>(stream));
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_tiles");
-    }
-}
-
-octpt_status octpt_tile_error_device(octpt_ctx *ctx, const octpt_tile_error_params *p, const float *d_moments,
-                                     const uint32_t *d_tile_spp, float *d_error, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_tile_error(ctx, p, d_moments, d_tile_spp, d_error);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_tile_error_device(ctx->sub[0], p, d_moments, d_tile_spp, d_error, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, launch_tile_error(p->width, p->height, p->luminance_floor, reinterpret_cast<const float2 *>(d_moments),
-                                       d_tile_spp, d_error, static_cast<hipStream_t>(stream)));
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error");
-    }
-}
-
-octpt_status octpt_tile_error(octpt_ctx *ctx, const octpt_tile_error_params *p, const float *moments,
-                              const uint32_t *tile_spp, float *error) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_tile_error(ctx, p, moments, tile_spp, error);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_tile_error(ctx->sub[0], p, moments, tile_spp, error);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height, T = frame_tiles(p->width, p->height);
-        void *d[3] = {};
-        hipError_t e = hipMalloc(&d[0], n * 8);
-        if (e == hipSuccess) e = hipMemcpy(d[0], moments, n * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&d[1], T * 4);
-        if (e == hipSuccess) e = hipMemcpy(d[1], tile_spp, T * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&d[2], T * 4);
-        if (e == hipSuccess) {
-            st = octpt_tile_error_device(ctx, p, static_cast<float *>(d[0]), static_cast<uint32_t *>(d[1]),
-                                         static_cast<float *>(d[2]), ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(error, d[2], T * 4, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "tile_error");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error");
-    }
-}
-
-namespace {
-
-// the plain driver's parameters as the _ex form's: neighbour weight 0, C32's loop
-octpt_adaptive_params_ex adaptive_ex_of(const octpt_adaptive_params &a) {
-    octpt_adaptive_params_ex x{};
-    x.min_spp = a.min_spp;
-    x.step_spp = a.step_spp;
-    x.threshold = a.threshold;
-    x.luminance_floor = a.luminance_floor;
-    return x;
-}
-
-// what the adaptive drivers refuse of their parameters (C32, C34b) besides make_render's own refusals; buffers: whether
-// the accum, moments and tile_spp pointers are all set
-octpt_status check_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a, bool buffers) {
-    octpt_status st = check_tile_render(ctx, "render_adaptive", p);
-    if (st != OCTPT_OK) return st;
-    if (!a) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: adaptive params NULL");
-    if (!buffers) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: NULL accum, moments or tile_spp buffer");
-    if (a->min_spp < 2u || a->step_spp < 1u)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: min_spp must be >= 2 and step_spp >= 1");
-    for (float x : {a->threshold, a->luminance_floor})
-        if (!(x > 0.0f) || !std::isfinite(x))
-            return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: threshold and luminance_floor must be positive and finite");
-    if (!(a->neighbour_weight >= 0.0f && a->neighbour_weight <= 1.0f))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: neighbour_weight must be in [0, 1]");
-    if (a->reserved[0] | a->reserved[1] | a->reserved[2])
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: the reserved words must be 0");
-    if (p->spp_start != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: a fresh render (spp_start must be 0)");
-    if (p->spp_count < a->min_spp)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: spp_count (the per-pixel cap) must be >= min_spp");
-    if (p->branch_count > 1u)
-        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "render_adaptive: branch_count > 1 (its pass boundaries fix the round sizes)");
-    return OCTPT_OK;
-}
-
-// the drivers' device form after the NULL-context check
-octpt_status adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a,
-                             float *d_accum, float *d_moments, uint32_t *d_seg, uint32_t *tile_spp,
-                             octpt_adaptive_result *result, void *stream) {
-    octpt_status st = check_adaptive(ctx, p, a, d_accum && d_moments && tile_spp);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        DevRender R{};
-        if ((st = make_render(ctx, p, R)) != OCTPT_OK) return st;  // the remaining refusals, before the buffers are touched
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const uint32_t T = frame_tiles(p->width, p->height), max_spp = p->spp_count;
-        const bool spread = a->neighbour_weight != 0.0f;  // C34: the plane the host reads is the spread one
-        // the tables below are rewritten every round, each time after the stream has drained; a call on another
-        // stream ended with its own drain
-        if ((st = grow_buf(ctx, ctx->d_tile_spp, ctx->tile_spp_cap, (size_t)T)) != OCTPT_OK) return st;
-        if ((st = grow_buf(ctx, ctx->d_tile_err, ctx->tile_err_cap, (size_t)T)) != OCTPT_OK) return st;
-        if (spread && (st = grow_buf(ctx, ctx->d_tile_spread, ctx->tile_spread_cap, (size_t)T)) != OCTPT_OK) return st;
-        float4 *acc = reinterpret_cast<float4 *>(d_accum);
-        float2 *mom = reinterpret_cast<float2 *>(d_moments);
-        HIP_TRY(ctx, launch_adaptive_init(p->width * p->height, acc, mom, s));
-        std::vector<uint32_t> active(T), next;
-        std::vector<float> err(T, INFINITY);
-        for (uint32_t t = 0; t < T; ++t) active[t] = t;
-        std::fill(tile_spp, tile_spp + T, 0u);
-        uint32_t n = 0, rounds = 0;
-        while (!active.empty() && n < max_spp) {
-            const uint32_t k = std::min(n == 0u ? a->min_spp : a->step_spp, max_spp - n);
-            octpt_render_params q = *p;
-            q.spp_start = n;
-            q.spp_count = k;
-            // round 1 is every tile in frame order: the plain deal (its beam starts serve the later lists)
-            st = render_tiles(ctx, &q, n == 0u ? nullptr : active.data(), (uint32_t)active.size(), acc, mom, d_seg, s);
-            if (st != OCTPT_OK) {
-                (void)hipStreamSynchronize(s);
-                return st;
+    return guarded(ctx, "intersect", [&]() -> octpt_status {
+        if (is_multi(ctx))  // one batch on the first entry's replica
+            return forwarded(ctx, octpt_intersect(ctx->sub[0], rays, last_prim, last_normal, n, t, prim, normal, steps));
+        // esvo_begin's t_coef = 1 / -|d| comes from rcp_rn, exact for |d| in [2^-23, 2^126] (smaller
+        // components are clamped to 2^-23 first, octree_traversal.rs:86-93): a ray with a non-finite
+        // component or a direction component |d| > 2^126 is outside that range.  Such a ray is reported as a
+        // miss -- t = +inf, prim = none, normal 0, 0 steps -- and the rest of the batch is traced as usual (the
+        // kernel sees a placeholder ray in its place).  For a non-finite ray this is what the reference's
+        // comparisons with NaN t-values give.  For a finite direction above 2^126 it is a DELIBERATE DEVIATION:
+        // the reference does not normalise directions (Ray::new, ray/mod.rs:32), its t_coef would be subnormal
+        // (octree_traversal.rs:95) and its walk could still hit something; no reference fixture covers that
+        // case (parity unpinned), and the render kernels never produce such a direction.
+        std::vector<uint32_t> unsupported;
+        std::vector<float> clean;
+        for (size_t i = 0; i < (size_t)n * 6; ++i) {
+            const float v = rays[i];
+            if (!std::isfinite(v) || (i % 6 >= 3 && std::fabs(v) > 0x1p126f)) {
+                if (clean.empty()) clean.assign(rays, rays + (size_t)n * 6);
+                const size_t r = i / 6;
+                if (unsupported.empty() || unsupported.back() != r) unsupported.push_back((uint32_t)r);
+                for (int k = 0; k < 6; ++k) clean[r * 6 + k] = k == 3 ? 1.0f : 0.0f;
             }
-            n += k;
-            for (uint32_t t : active) tile_spp[t] = n;
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tile_spp, tile_spp, (size_t)T * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, launch_tile_error(p->width, p->height, a->luminance_floor, mom, ctx->d_tile_spp, ctx->d_tile_err, s));
-            if (spread)
-                HIP_TRY(ctx, launch_tile_error_spread(p->width, p->height, a->neighbour_weight, ctx->d_tile_err,
-                                                      ctx->d_tile_spread, s));
-            HIP_TRY(ctx, hipMemcpyAsync(err.data(), spread ? ctx->d_tile_spread : ctx->d_tile_err, (size_t)T * 4,
-                                        hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-            next.clear();
-            for (uint32_t t : active)
-                if (err[t] > a->threshold) next.push_back(t);
-            active.swap(next);
-            ++rounds;
         }
-        if (result) {
-            octpt_adaptive_result r{};
-            r.rounds = rounds;
-            r.total_tiles = T;
-            for (uint32_t t = 0; t < T; ++t) {
-                r.tile_samples += tile_spp[t];
-                if (err[t] <= a->threshold) ++r.converged_tiles;
-            }
-            *result = r;
-        }
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_adaptive");
-    }
-}
-
-// the drivers' host form after the NULL-context check
-octpt_status adaptive_host(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a, float *accum,
-                           float *moments, uint32_t *tile_spp, uint8_t *out_rgba8, octpt_adaptive_result *result) {
-    octpt_status st = check_tile_render(ctx, "render_adaptive", p);
-    if (st != OCTPT_OK) return st;
-    if (!accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_adaptive: accum NULL");
-    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
-    try {
-        join_inflight(ctx);
+        if (!clean.empty()) rays = clean.data();
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        std::vector<uint32_t> spp(frame_tiles(p->width, p->height));
-        void *d[3] = {};  // accum, moments, rgba8
-        hipError_t e = hipMalloc(&d[0], n * 16);
-        if (e == hipSuccess) e = hipMalloc(&d[1], n * 8);
-        if (e == hipSuccess && out_rgba8) e = hipMalloc(&d[2], n * 4);
-        if (e == hipSuccess) {
-            st = adaptive_device(ctx, p, a, static_cast<float *>(d[0]), static_cast<float *>(d[1]), nullptr, spp.data(),
-                                 result, ctx->stream);
-            if (st == OCTPT_OK && out_rgba8)
-                e = launch_tonemap(static_cast<float4 *>(d[0]), static_cast<uchar4 *>(d[2]), (uint32_t)n, ctx->d_lut_byte,
-                                   ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(accum, d[0], n * 16, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && moments) e = hipMemcpy(moments, d[1], n * 8, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d[2], n * 4, hipMemcpyDeviceToHost);
+        HostStage hs(ctx->stream);
+        const float *d_rays = hs.in(rays, (size_t)n * 6);
+        const uint32_t *d_lp = hs.in(last_prim, n);
+        const float *d_ln = hs.in(last_normal, (size_t)n * 3);
+        float *d_t = hs.out(t, n);
+        uint32_t *d_p = hs.out(prim, n);
+        float *d_n = hs.out(normal, (size_t)n * 3);
+        uint32_t *d_s = hs.out(steps, n);
+        if (hs.ok()) hs.note(launch_intersect(ctx->S, d_rays, d_lp, d_ln, n, d_t, d_p, d_n, d_s, ctx->stream));
+        if (hs.finish() != hipSuccess) return hip_fail(ctx, hs.error(), "intersect");
+        for (uint32_t r : unsupported) {
+            t[r] = INFINITY;
+            prim[r] = 0xFFFFFFFFu;
+            if (normal) normal[3 * (size_t)r] = normal[3 * (size_t)r + 1] = normal[3 * (size_t)r + 2] = 0.0f;
+            if (steps) steps[r] = 0u;
         }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "render_adaptive");
-        if (tile_spp) std::copy(spp.begin(), spp.end(), tile_spp);
         return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_adaptive");
-    }
-}
-
-}  // namespace
-
-octpt_status octpt_render_adaptive_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
-                                          float *d_accum, float *d_moments, uint32_t *d_seg, uint32_t *tile_spp,
-                                          octpt_adaptive_result *result, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    const octpt_adaptive_params_ex x = a ? adaptive_ex_of(*a) : octpt_adaptive_params_ex{};
-    return adaptive_device(ctx, p, a ? &x : nullptr, d_accum, d_moments, d_seg, tile_spp, result, stream);
-}
-
-octpt_status octpt_render_adaptive(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params *a,
-                                   float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
-                                   octpt_adaptive_result *result) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    const octpt_adaptive_params_ex x = a ? adaptive_ex_of(*a) : octpt_adaptive_params_ex{};
-    return adaptive_host(ctx, p, a ? &x : nullptr, accum, moments, tile_spp, out_rgba8, result);
-}
-
-octpt_status octpt_render_adaptive_ex_device(octpt_ctx *ctx, const octpt_render_params *p,
-                                             const octpt_adaptive_params_ex *a, float *d_accum, float *d_moments,
-                                             uint32_t *d_seg, uint32_t *tile_spp, octpt_adaptive_result *result,
-                                             void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    return adaptive_device(ctx, p, a, d_accum, d_moments, d_seg, tile_spp, result, stream);
-}
-
-octpt_status octpt_render_adaptive_ex(octpt_ctx *ctx, const octpt_render_params *p, const octpt_adaptive_params_ex *a,
-                                      float *accum, float *moments, uint32_t *tile_spp, uint8_t *out_rgba8,
-                                      octpt_adaptive_result *result) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    return adaptive_host(ctx, p, a, accum, moments, tile_spp, out_rgba8, result);
-}
-
-// ---------------- final-quality adaptive frames: clamp, seam rule, sample variance, finished frame ----------------
-octpt_status octpt_set_sample_clamp(octpt_ctx *ctx, float max_luminance) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    if (!(max_luminance >= 0.0f)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample clamp must be >= 0 (0 or +inf: off), not NaN");
-    join_inflight(ctx);  // a frame in flight keeps the value its call was made with
-    ctx->sample_clamp = std::isfinite(max_luminance) ? max_luminance : 0.0f;
-    for (octpt_ctx *sc : ctx->sub) {
-        const octpt_status st = octpt_set_sample_clamp(sc, max_luminance);
-        if (st != OCTPT_OK) return fail(ctx, st, sc->err);
-    }
-    return OCTPT_OK;
+    });
 }
 
 // ---------------- emitter sampling: the setting and the grid ----------------
@@ -3399,10 +2167,7 @@ octpt_status octpt_emitter_grid(octpt_ctx *ctx, octpt_emitter_grid_arrays *out) 
     if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter grid arrays NULL");
     out->cell_count = out->entry_count = out->emitter_count = out->cells_per_axis = 0u;
     join_inflight(ctx);
-    if (is_multi(ctx)) {
-        const octpt_status st = octpt_emitter_grid(ctx->sub[0], out);
-        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-    }
+    if (is_multi(ctx)) return forwarded(ctx, octpt_emitter_grid(ctx->sub[0], out));
     if (!ctx->grid_valid)
         return fail(ctx, OCTPT_ERR_INVALID_ARG,
                     "the context holds no emitter grid (strategy OCTPT_EMITTERS_ONE and a block-value scene build it)");
@@ -3425,10 +2190,7 @@ octpt_status octpt_emitter_models(octpt_ctx *ctx, octpt_emitter_model_arrays *ou
     if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter model arrays NULL");
     out->model_count = out->entry_count = 0u;
     join_inflight(ctx);
-    if (is_multi(ctx)) {
-        const octpt_status st = octpt_emitter_models(ctx->sub[0], out);
-        return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-    }
+    if (is_multi(ctx)) return forwarded(ctx, octpt_emitter_models(ctx->sub[0], out));
     if (!ctx->grid_valid || !(ctx->emit_grid.flags & OCTPT_EMITTERS_MODELS) || !ctx->d_model_first)
         return fail(ctx, OCTPT_ERR_INVALID_ARG,
                     "the context holds no emissive-model table (a grid built with OCTPT_EMITTERS_MODELS holds one)");
@@ -3444,250 +2206,6 @@ octpt_status octpt_emitter_models(octpt_ctx *ctx, octpt_emitter_model_arrays *ou
         HIP_TRY(ctx, hipMemcpy(out->cum_area, ctx->d_model_cum, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
     }
     return OCTPT_OK;
-}
-
-namespace {
-
-octpt_status check_spread(octpt_ctx *ctx, uint32_t W, uint32_t H, float w, const void *error, const void *out) {
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: bad resolution");
-    if (!(w >= 0.0f && w <= 1.0f)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: neighbour_weight must be in [0, 1]");
-    if (!error || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: NULL error or output buffer");
-    if (error == out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "tile_error_spread: the output must not be the input plane");
-    return OCTPT_OK;
-}
-
-octpt_status check_sample_variance(octpt_ctx *ctx, const octpt_sample_variance_params *p, const void *moments,
-                                   const void *tile_spp, const octpt_aov_buffers *g, const void *out) {
-    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance params NULL");
-    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: bad resolution");
-    if (p->flags & ~OCTPT_DENOISE_DEMODULATE)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: unknown flag (OCTPT_DENOISE_DEMODULATE is the one flag)");
-    if (!moments || !tile_spp || !out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: NULL moments, tile_spp or output buffer");
-    if (!g || !g->depth) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: the depth guide is required");
-    const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
-    if (demod && !g->albedo) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: OCTPT_DENOISE_DEMODULATE needs the albedo guide");
-    if (out == moments || out == tile_spp || out == g->depth || (demod && out == g->albedo))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "sample_variance: the output must be distinct from the inputs");
-    return OCTPT_OK;
-}
-
-}  // namespace
-
-octpt_status octpt_tile_error_spread_device(octpt_ctx *ctx, uint32_t W, uint32_t H, float w, const float *d_error,
-                                            float *d_out, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_spread(ctx, W, H, w, d_error, d_out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_tile_error_spread_device(ctx->sub[0], W, H, w, d_error, d_out, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, launch_tile_error_spread(W, H, w, d_error, d_out, static_cast<hipStream_t>(stream)));
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error_spread");
-    }
-}
-
-octpt_status octpt_tile_error_spread(octpt_ctx *ctx, uint32_t W, uint32_t H, float w, const float *error, float *out) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_spread(ctx, W, H, w, error, out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_tile_error_spread(ctx->sub[0], W, H, w, error, out);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t T = frame_tiles(W, H);
-        void *d[2] = {};
-        hipError_t e = hipMalloc(&d[0], T * 4);
-        if (e == hipSuccess) e = hipMemcpy(d[0], error, T * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&d[1], T * 4);
-        if (e == hipSuccess) {
-            st = octpt_tile_error_spread_device(ctx, W, H, w, static_cast<float *>(d[0]), static_cast<float *>(d[1]), ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[1], T * 4, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "tile_error_spread");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in tile_error_spread");
-    }
-}
-
-octpt_status octpt_sample_variance_device(octpt_ctx *ctx, const octpt_sample_variance_params *p, const float *d_moments,
-                                          const uint32_t *d_tile_spp, const octpt_aov_buffers *g, float *d_out,
-                                          void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_sample_variance(ctx, p, d_moments, d_tile_spp, g, d_out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_sample_variance_device(ctx->sub[0], p, d_moments, d_tile_spp, g, d_out, stream);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
-        HIP_TRY(ctx, launch_sample_variance(p->width, p->height, reinterpret_cast<const float2 *>(d_moments), d_tile_spp,
-                                            g->depth, demod ? reinterpret_cast<const float4 *>(g->albedo) : nullptr, d_out,
-                                            static_cast<hipStream_t>(stream)));
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in sample_variance");
-    }
-}
-
-octpt_status octpt_sample_variance(octpt_ctx *ctx, const octpt_sample_variance_params *p, const float *moments,
-                                   const uint32_t *tile_spp, const octpt_aov_buffers *g, float *out) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_sample_variance(ctx, p, moments, tile_spp, g, out);
-    if (st != OCTPT_OK) return st;
-    try {
-        join_inflight(ctx);
-        if (is_multi(ctx)) {
-            st = octpt_sample_variance(ctx->sub[0], p, moments, tile_spp, g, out);
-            return st == OCTPT_OK ? st : fail(ctx, st, ctx->sub[0]->err);
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height, T = frame_tiles(p->width, p->height);
-        const bool demod = (p->flags & OCTPT_DENOISE_DEMODULATE) != 0u;
-        // moments, tile_spp, depth, albedo, then the output
-        const void *h[4] = {moments, tile_spp, g->depth, demod ? g->albedo : nullptr};
-        const size_t bytes[4] = {n * 8, T * 4, n * 4, n * 16};
-        void *d[5] = {};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) {
-            if (!h[i]) continue;
-            if ((e = hipMalloc(&d[i], bytes[i])) == hipSuccess) e = hipMemcpy(d[i], h[i], bytes[i], hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMalloc(&d[4], n * 4);
-        if (e == hipSuccess) {
-            const octpt_aov_buffers dg{static_cast<float *>(d[3]), nullptr, static_cast<float *>(d[2]), nullptr, nullptr};
-            st = octpt_sample_variance_device(ctx, p, static_cast<float *>(d[0]), static_cast<uint32_t *>(d[1]), &dg,
-                                              static_cast<float *>(d[4]), ctx->stream);
-            if (st == OCTPT_OK) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[4], n * 4, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "sample_variance");
-        return OCTPT_OK;
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in sample_variance");
-    }
-}
-
-octpt_status octpt_render_final_device(octpt_ctx *ctx, const octpt_render_params *p, const octpt_final_params *f,
-                                       float *d_accum, float *d_moments, float *d_out, float *d_out_variance,
-                                       uint32_t *tile_spp, octpt_adaptive_result *result, void *stream) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    if (!f) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: final params NULL");
-    // every refusal of the four steps, before any buffer is touched
-    octpt_status st = check_adaptive(ctx, p, &f->adaptive, d_accum && d_moments && tile_spp);
-    if (st != OCTPT_OK) return st;
-    const bool demod = (f->filter.flags & OCTPT_DENOISE_DEMODULATE) != 0u;
-    {
-        // the filter's own checks of its parameters; its buffers are this call's and the context's planes
-        const octpt_aov_buffers some{d_accum, d_accum, d_accum, nullptr, nullptr};
-        if ((st = check_denoise_variance(ctx, &f->filter, d_accum, d_accum, &some, d_out)) != OCTPT_OK) return st;
-    }
-    if (f->filter.width != p->width || f->filter.height != p->height)
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: the filter's width / height differ from the render's");
-    if (d_out == d_accum) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: d_out must not alias d_accum");
-    try {
-        join_inflight(ctx);
-        {
-            DevRender R{};
-            if ((st = make_render(ctx, p, R)) != OCTPT_OK) return st;
-        }
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height, T = frame_tiles(p->width, p->height);
-        // the context's planes, grow-only; one that has to grow may still be read by an earlier call on another
-        // stream: drain first
-        if (n > ctx->fin_normal_cap || n > ctx->fin_depth_cap || n > ctx->fin_var_cap || (demod && n > ctx->fin_albedo_cap) ||
-            T > ctx->tile_spp_cap)
-            HIP_TRY(ctx, hipDeviceSynchronize());
-        if ((st = grow_buf(ctx, ctx->fin_normal, ctx->fin_normal_cap, n)) != OCTPT_OK) return st;
-        if ((st = grow_buf(ctx, ctx->fin_depth, ctx->fin_depth_cap, n)) != OCTPT_OK) return st;
-        if ((st = grow_buf(ctx, ctx->fin_var, ctx->fin_var_cap, n)) != OCTPT_OK) return st;
-        if (demod && (st = grow_buf(ctx, ctx->fin_albedo, ctx->fin_albedo_cap, n)) != OCTPT_OK) return st;
-        // 1. the adaptive render; it leaves its final tile_spp in the context's device table
-        if ((st = octpt_render_adaptive_ex_device(ctx, p, &f->adaptive, d_accum, d_moments, nullptr, tile_spp, result,
-                                                  stream)) != OCTPT_OK)
-            return st;
-        // 2. the guides
-        const octpt_aov_buffers g{demod ? reinterpret_cast<float *>(ctx->fin_albedo) : nullptr,
-                                  reinterpret_cast<float *>(ctx->fin_normal), ctx->fin_depth, nullptr, nullptr};
-        if ((st = octpt_render_aov_device(ctx, p, &g, stream)) != OCTPT_OK) return st;
-        // 3. the variance of the pixel means
-        const octpt_sample_variance_params vp{p->width, p->height, f->filter.flags & OCTPT_DENOISE_DEMODULATE};
-        if ((st = octpt_sample_variance_device(ctx, &vp, d_moments, ctx->d_tile_spp, &g, ctx->fin_var, stream)) != OCTPT_OK)
-            return st;
-        // 4. the filter
-        return octpt_denoise_variance_device(ctx, &f->filter, d_accum, ctx->fin_var, &g, d_out, d_out_variance, stream);
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_final");
-    }
-}
-
-octpt_status octpt_render_final(octpt_ctx *ctx, const octpt_render_params *p, const octpt_final_params *f, float *accum,
-                                float *moments, float *out, float *out_variance, uint32_t *tile_spp, uint8_t *out_rgba8,
-                                octpt_adaptive_result *result) {
-    if (!ctx) return OCTPT_ERR_INVALID_ARG;
-    octpt_status st = check_tile_render(ctx, "render_final", p);
-    if (st != OCTPT_OK) return st;
-    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "render_final: out NULL");
-    if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
-        return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
-    try {
-        join_inflight(ctx);
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t n = (size_t)p->width * p->height;
-        std::vector<uint32_t> spp(frame_tiles(p->width, p->height));
-        void *d[5] = {};  // accum, moments, out, out variance, rgba8
-        hipError_t e = hipMalloc(&d[0], n * 16);
-        if (e == hipSuccess) e = hipMalloc(&d[1], n * 8);
-        if (e == hipSuccess) e = hipMalloc(&d[2], n * 16);
-        if (e == hipSuccess && out_variance) e = hipMalloc(&d[3], n * 4);
-        if (e == hipSuccess && out_rgba8) e = hipMalloc(&d[4], n * 4);
-        if (e == hipSuccess) {
-            st = octpt_render_final_device(ctx, p, f, static_cast<float *>(d[0]), static_cast<float *>(d[1]),
-                                           static_cast<float *>(d[2]), static_cast<float *>(d[3]), spp.data(), result,
-                                           ctx->stream);
-            if (st == OCTPT_OK && out_rgba8)
-                e = launch_tonemap(static_cast<float4 *>(d[2]), static_cast<uchar4 *>(d[4]), (uint32_t)n, ctx->d_lut_byte,
-                                   ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (st == OCTPT_OK && e == hipSuccess) e = hipMemcpy(out, d[2], n * 16, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && accum) e = hipMemcpy(accum, d[0], n * 16, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && moments) e = hipMemcpy(moments, d[1], n * 8, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && out_variance) e = hipMemcpy(out_variance, d[3], n * 4, hipMemcpyDeviceToHost);
-            if (st == OCTPT_OK && e == hipSuccess && out_rgba8) e = hipMemcpy(out_rgba8, d[4], n * 4, hipMemcpyDeviceToHost);
-        }
-        for (void *q : d)
-            if (q) (void)hipFree(q);
-        if (st != OCTPT_OK) return st;
-        if (e != hipSuccess) return hip_fail(ctx, e, "render_final");
-        if (tile_spp) std::copy(spp.begin(), spp.end(), tile_spp);
-        return OCTPT_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, OCTPT_ERR_OOM, "host allocation");
-    } catch (...) {
-        return fail(ctx, OCTPT_ERR_INTERNAL, "unexpected exception in render_final");
-    }
 }
 
 octpt_status octpt_get_stats(const octpt_ctx *cctx, octpt_stats *out) {
