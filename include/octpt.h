@@ -305,6 +305,37 @@ octpt_status octpt_scene_build_device(octpt_ctx *ctx, const octpt_scene_desc *sc
 octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *camera);
 octpt_status octpt_get_camera(const octpt_ctx *ctx, octpt_camera *camera);
 
+/* The camera's projection: how a pixel's position (sx, sy) -- C37's, jitter included, in units of half
+ * the longer image side -- becomes a path's first ray.  It changes that ray and nothing else; a path's random draws are
+ * the same in every mode.
+ *   PINHOLE    the perspective view of octpt_camera::fov (the state of a new context); param is not read
+ *   PARALLEL   every ray along `direction`, from eye + right * (sx * param / 2) + up * (sy * param / 2): param is the
+ *              world-space length the longer image side spans, finite and > 0 (isometric map renders)
+ *   FISHEYE    equidistant: the angle from `direction` is |(sx, sy)| * param / 2
+ *   PANORAMIC  equirectangular: longitude sx * param / 2 about `up`, latitude sy * param / 2 (a 360-degree panorama is
+ *              param = 2 pi at width = 2 * height)
+ * For FISHEYE and PANORAMIC param is the full angle in radians across the longer image side, finite and in (0, 2 pi]
+ * (the float nearest 2 pi included).  octpt_camera::fov is not read in the three new modes -- no ray depends on it --
+ * but octpt_set_camera and octpt_projection_rays still validate it: a camera is valid or not whatever the projection.
+ * Unknown mode: UNSUPPORTED.  A bad param or a non-zero reserved word: INVALID_ARG.  A mode other than PINHOLE while
+ * the context's camera has an aperture: UNSUPPORTED, and likewise octpt_set_camera with an aperture while the
+ * projection is not PINHOLE (the camera then stays as it was).  A refused call leaves the setting as it was.
+ * The call joins a frame in flight and the setting holds for every later render of the context: sync, device, async,
+ * tile list, adaptive, final, megakernel, and with the un-jittered ray the preview and the guide buffers; every entry
+ * of a multi-device context follows it.  Camera-ray beam starts are off while it is not PINHOLE.  octpt_temporal*
+ * and octpt_reproject_coords_ctx refuse (UNSUPPORTED) while it is not PINHOLE: reprojection is the pinhole camera's. */
+#define OCTPT_PROJECTION_PINHOLE 0u /* the state of a new context */
+#define OCTPT_PROJECTION_PARALLEL 1u
+#define OCTPT_PROJECTION_FISHEYE 2u
+#define OCTPT_PROJECTION_PANORAMIC 3u
+typedef struct octpt_projection {
+    uint32_t mode;
+    float param;
+    uint32_t reserved[6]; /* 0 */
+} octpt_projection;
+octpt_status octpt_set_projection(octpt_ctx *ctx, const octpt_projection *projection);
+octpt_status octpt_get_projection(const octpt_ctx *ctx, octpt_projection *projection);
+
 /* Synchronous render into host memory.  accum_rgba: width*height*4 floats (or the shard's
  * compact tiles), in/out running mean, initialise to F32Color::BLACK (0,0,0,1).
  * out_rgba8 (nullable): tone-mapped U8Color image (colors/mod.rs:408-420) of accum. */
@@ -394,6 +425,19 @@ octpt_status octpt_camera_rays(const octpt_camera *camera, uint32_t width, uint3
  * octpt_set_camera's for aperture and focal_distance; a failed call writes nothing.  Host-only, no context. */
 octpt_status octpt_lens_rays(const octpt_camera *camera, uint32_t width, uint32_t height, uint32_t seed,
                              uint32_t sample, float *rays);
+/* The first ray under a projection, for n chosen samples: xys[3 * i] = (x, y, sample) and
+ * rays[6 * i] = (origin xyz, unit direction xyz) of the ray that a width x height render with this seed traces for
+ * that sample of pixel (x, y) under `projection`, bit for bit (one text, csrc/octpt_lens.h).  rng_state (nullable):
+ * rng_state[i] = the path's RNG state after the ray, the same in every mode.  With OCTPT_PROJECTION_RAYS_CENTRE the
+ * rays are the un-jittered ones of OCTPT_RENDER_PREVIEW and the guide buffers (the sample is not read, rng_state gets
+ * the path's initial state).  PINHOLE gives octpt_lens_rays' ray (octpt_camera_rays' with the flag); the camera
+ * follows octpt_lens_rays' rules and the projection octpt_set_projection's, an aperture with another mode than
+ * PINHOLE UNSUPPORTED as there; x >= width, y >= height or an unknown flag: INVALID_ARG.  Every check comes before
+ * the first write: a failed call writes nothing.  Host-only, no context. */
+#define OCTPT_PROJECTION_RAYS_CENTRE 0x1u
+octpt_status octpt_projection_rays(const octpt_camera *camera, const octpt_projection *projection, uint32_t width,
+                                   uint32_t height, uint32_t seed, const uint32_t *xys, uint32_t n, uint32_t flags,
+                                   float *rays, uint32_t *rng_state);
 
 /* First-hit guide buffers (AOVs) of the preview's camera ray (C24): one un-jittered ray per pixel, continued
  * through material-0 and alpha-0 hits exactly as RendererMode::Preview continues it (preview_render,
@@ -487,6 +531,12 @@ octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, cons
  * orthonormal as above.  Host-only, no context. */
 octpt_status octpt_reproject_coords(const octpt_camera *camera, const octpt_camera *prev_camera, uint32_t width,
                                     uint32_t height, const float *depth, float *prev_xy, float *prev_depth);
+/* The same for the frames of a context: UNSUPPORTED, nothing written, while the context's projection is not PINHOLE
+ * (C40: the mapping is the pinhole camera's; the entry above knows no context and maps pinhole frames whatever a
+ * context renders).  The cameras are the arguments', not the context's. */
+octpt_status octpt_reproject_coords_ctx(octpt_ctx *ctx, const octpt_camera *camera, const octpt_camera *prev_camera,
+                                        uint32_t width, uint32_t height, const float *depth, float *prev_xy,
+                                        float *prev_depth);
 
 /* --- luminance moments, variance and the variance-guided filter (SVGF, Schied et al. 2017) ---
  * The a-trous filter above stops at colour edges under one global sigma_color.  With temporal accumulation in

@@ -209,6 +209,18 @@ class Camera(C.Structure):
                 ("aperture", C.c_float), ("focal_distance", C.c_float)]
 
 
+PROJECTION_PINHOLE = 0  # OCTPT_PROJECTION_* 
+PROJECTION_PARALLEL = 1
+PROJECTION_FISHEYE = 2
+PROJECTION_PANORAMIC = 3
+PROJECTION_RAYS_CENTRE = 0x1  # OCTPT_PROJECTION_RAYS_CENTRE
+
+
+class Projection(C.Structure):
+    """octpt_projection (octpt_set_projection): the mode and its extent or angle."""
+    _fields_ = [("mode", C.c_uint32), ("param", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp_start", C.c_uint32), ("spp_count", C.c_uint32),
                 ("max_depth", C.c_uint32), ("branch_count", C.c_uint32), ("seed", C.c_uint32),
@@ -346,6 +358,8 @@ SIGNATURES = {
     "octpt_scene_build_device": (_i32, [_vp, C.POINTER(SceneDesc), _u32]),
     "octpt_set_camera": (_i32, [_vp, C.POINTER(Camera)]),
     "octpt_get_camera": (_i32, [_vp, C.POINTER(Camera)]),
+    "octpt_set_projection": (_i32, [_vp, C.POINTER(Projection)]),
+    "octpt_get_projection": (_i32, [_vp, C.POINTER(Projection)]),
     "octpt_render": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp]),
     "octpt_render_device": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]),
     "octpt_render_async": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, C.POINTER(_vp)]),
@@ -362,6 +376,8 @@ SIGNATURES = {
     "octpt_traversal_data": (_i32, [_vp, _u32, _u32, _u32, _vp, _f, _vp, _vp, _vp, _vp]),
     "octpt_camera_rays": (_i32, [C.POINTER(Camera), _u32, _u32, _vp]),
     "octpt_lens_rays": (_i32, [C.POINTER(Camera), _u32, _u32, _u32, _u32, _vp]),
+    "octpt_projection_rays": (_i32, [C.POINTER(Camera), C.POINTER(Projection), _u32, _u32, _u32, _vp, _u32, _u32, _vp,
+                                     _vp]),
     "octpt_render_aov": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers)]),
     "octpt_render_aov_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers), _vp]),
     "octpt_denoise_device": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp, _vp]),
@@ -402,6 +418,7 @@ SIGNATURES = {
     "octpt_render_final": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(FinalParams), _vp, _vp, _vp, _vp, _vp, _vp,
                                   C.POINTER(AdaptiveResult)]),
     "octpt_reproject_coords": (_i32, [C.POINTER(Camera), C.POINTER(Camera), _u32, _u32, _vp, _vp, _vp]),
+    "octpt_reproject_coords_ctx": (_i32, [_vp, C.POINTER(Camera), C.POINTER(Camera), _u32, _u32, _vp, _vp, _vp]),
     "octpt_get_stats": (_i32, [_vp, C.POINTER(Stats)]),
     "octpt_reset_stats": (_i32, [_vp]),
     "octpt_build_octree": (_i32, [_vp, _u32, _vp, _u32, _u32, C.POINTER(_vp)]),

@@ -907,7 +907,9 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     // share them (OCTPT_BEAM=0 switches them off; results are identical, ESVO iterations fewer)
     // A camera with an aperture (C37) renders without them: behind the focal plane a lens ray leaves the tile's
     // pyramid from the eye without bound, so the table is not conservative for it
-    const bool lens = ctx->C.aperture > 0.0f;
+    // A projection other than pinhole (C40) likewise: the table is computed for the pinhole's pyramids, and such rays
+    // take the lens's path through the chunk (origins of their own, full records, the general shade's twins)
+    const bool lens = ctx->C.aperture > 0.0f || ctx->C.proj_mode != OCTPT_PROJECTION_PINHOLE;
     const float *beam = nullptr;
     if (ctx->beam && !lens) {
         const size_t n_tiles = (size_t)R.beam_tx * ((R.H + kBeamTile - 1) / kBeamTile);
@@ -1748,6 +1750,8 @@ octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
     if (!lens_fields_valid(c->aperture, c->focal_distance))
         return fail(ctx, OCTPT_ERR_INVALID_ARG,
                     "aperture must be finite and >= 0, and focal_distance finite and > 0 when aperture > 0");
+    if (c->aperture > 0.0f && ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "an aperture needs the pinhole projection (octpt_set_projection)");
     ctx->cam = *c;
     DevCamera C{};
     std::memcpy(C.eye, c->eye, 12);
@@ -1758,6 +1762,10 @@ octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
     // the thin lens (C37): focal_distance is read with an aperture alone, and divided here once
     C.aperture = c->aperture;
     C.focal_scale = c->aperture > 0.0f ? c->focal_distance / C.d_factor : 0.0f;
+    // the projection (C40) rides in the device camera: a projected camera has no aperture, so proj_half takes the
+    // slot of focal_scale
+    C.proj_mode = ctx->proj.mode;
+    if (C.proj_mode != OCTPT_PROJECTION_PINHOLE) C.proj_half = ctx->proj.param * 0.5f;
     ctx->C = C;
     ctx->has_camera = true;
     ++ctx->camera_gen;
@@ -1765,6 +1773,41 @@ octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
         const octpt_status st = octpt_set_camera(sc, c);
         if (st != OCTPT_OK) return fail(ctx, st, sc->err);
     }
+    return OCTPT_OK;
+}
+
+octpt_status octpt_set_projection(octpt_ctx *ctx, const octpt_projection *p) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "projection NULL");
+    if (!proj_mode_known(p->mode)) return fail(ctx, OCTPT_ERR_UNSUPPORTED, "unknown projection mode");
+    for (uint32_t r : p->reserved)
+        if (r != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "projection: a reserved word is not zero");
+    if (!proj_param_valid(p->mode, p->param))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "projection param must be finite and > 0, and an angle at most 2 pi");
+    if (p->mode != OCTPT_PROJECTION_PINHOLE && ctx->has_camera && ctx->cam.aperture > 0.0f)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a projection other than pinhole needs a camera without an aperture");
+    // (the pinhole's param is not read: every pinhole setting is one state)
+    const float param = p->mode == OCTPT_PROJECTION_PINHOLE ? 0.0f : p->param;
+    // the setting the context (and with it every entry) already holds: nothing changes, the beam table stays valid
+    if (p->mode == ctx->proj.mode && param == ctx->proj.param) return OCTPT_OK;
+    join_inflight(ctx);  // a frame in flight reads ctx->C
+    ctx->proj = *p;
+    ctx->proj.param = param;
+    ctx->C.proj_mode = ctx->proj.mode;
+    if (ctx->proj.mode != OCTPT_PROJECTION_PINHOLE) ctx->C.proj_half = ctx->proj.param * 0.5f;
+    else if (!(ctx->C.aperture > 0.0f)) ctx->C.focal_scale = 0.0f;  // back to what octpt_set_camera derives
+    ++ctx->camera_gen;  // the beam table is the pinhole camera's (enqueue_wavefront)
+    for (octpt_ctx *sc : ctx->sub) {
+        const octpt_status st = octpt_set_projection(sc, p);
+        if (st != OCTPT_OK) return fail(ctx, st, sc->err);
+    }
+    return OCTPT_OK;
+}
+
+octpt_status octpt_get_projection(const octpt_ctx *ctx, octpt_projection *p) {
+    if (!ctx || !p) return OCTPT_ERR_INVALID_ARG;
+    *p = ctx->proj;
     return OCTPT_OK;
 }
 

@@ -74,6 +74,8 @@ struct octpt_ctx {
     bool has_camera = false;
     octpt_camera cam{};
     octpt::DevCamera C{};
+    // the projection (C40, octpt_set_projection): PINHOLE in a new context; ctx->C carries its mode and half-param
+    octpt_projection proj{};
     // per-context device state
     uint32_t *d_counters = nullptr;  // ring of work counters, one per launch
     // branch schedule of the current render (C20): host copy + grow-only device table

@@ -203,6 +203,73 @@ extern "C" octpt_status octpt_lens_rays(const octpt_camera *camera, uint32_t wid
     return OCTPT_OK;
 }
 
+// The first ray under a projection for chosen samples: csrc/octpt_lens.h's projection_ray, the text
+// the projected kernel instances compile; PINHOLE is lens_ray (octpt_lens_rays' text), with the centre flag
+// octpt_camera_rays' text.  Every check comes before the first write.
+extern "C" octpt_status octpt_projection_rays(const octpt_camera *camera, const octpt_projection *projection,
+                                              uint32_t width, uint32_t height, uint32_t seed, const uint32_t *xys,
+                                              uint32_t n, uint32_t flags, float *rays, uint32_t *rng_state) {
+    if (!camera || !projection || !rays || (n != 0u && !xys) || width == 0u || height == 0u) return OCTPT_ERR_INVALID_ARG;
+    if ((uint64_t)width * height >= (1ull << 31)) return OCTPT_ERR_INVALID_ARG;
+    if (flags & ~OCTPT_PROJECTION_RAYS_CENTRE) return OCTPT_ERR_INVALID_ARG;
+    if (!(camera->fov > 0.0f && camera->fov < 3.14159265f)) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::lens_fields_valid(camera->aperture, camera->focal_distance)) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::proj_mode_known(projection->mode)) return OCTPT_ERR_UNSUPPORTED;
+    for (uint32_t r : projection->reserved)
+        if (r != 0u) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::proj_param_valid(projection->mode, projection->param)) return OCTPT_ERR_INVALID_ARG;
+    const bool pinhole = projection->mode == OCTPT_PROJECTION_PINHOLE;
+    if (!pinhole && camera->aperture > 0.0f) return OCTPT_ERR_UNSUPPORTED;
+    for (uint32_t i = 0; i < n; ++i)
+        if (xys[3u * i] >= width || xys[3u * i + 1u] >= height) return OCTPT_ERR_INVALID_ARG;
+    const bool centre = (flags & OCTPT_PROJECTION_RAYS_CENTRE) != 0u;
+    const octpt::LensCamera L = octpt::lens_camera(camera->eye, camera->direction, camera->up, camera->fov,
+                                                   camera->aperture, camera->focal_distance);
+    octpt::ProjCamera P;
+    std::memcpy(P.eye, L.eye, 12);
+    std::memcpy(P.dir, L.dir, 12);
+    std::memcpy(P.right, L.right, 12);
+    std::memcpy(P.up, L.up, 12);
+    P.proj_mode = projection->mode;
+    P.proj_half = projection->param * 0.5f;  // octpt_set_projection's product
+    octpt::LensFrame F;
+    F.W = width;
+    F.H = height;
+    F.seed = seed;
+    F.dim = (float)(width > height ? width : height);  // make_render's dim, jlo and jhi
+    F.jlo = -1.0f / F.dim;
+    F.jhi = 1.0f / F.dim;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t x = xys[3u * i], y = xys[3u * i + 1u], sample = xys[3u * i + 2u];
+        float *o = rays + 6u * (size_t)i, *d = o + 3;
+        uint32_t st;
+        if (pinhole && centre) {  // octpt_camera_rays' expressions (the preview's and the guide buffers' ray)
+            const float xn = ((float)(2u * x + 1u) - (float)width) / F.dim;
+            const float yn = ((float)(2u * (height - y) - 1u) - (float)height) / F.dim;
+            float nd[3];
+            for (int k = 0; k < 3; ++k) nd[k] = (L.dir[k] * L.d_factor + L.right[k] * xn) + L.up[k] * yn;
+            const float r = 1.0f / sqrtf((nd[0] * nd[0] + nd[1] * nd[1]) + nd[2] * nd[2]);
+            for (int k = 0; k < 3; ++k) {
+                o[k] = L.eye[k];
+                d[k] = nd[k] * r;
+            }
+            st = octpt::path_state(seed, y * width + x, sample);
+        } else {
+            if (pinhole) st = L.aperture > 0.0f ? octpt::lens_ray<true>(L, F, x, y, sample, o, d)
+                                               : octpt::lens_ray<false>(L, F, x, y, sample, o, d);
+            else st = centre ? octpt::projection_ray<false>(P, F, x, y, sample, o, d)
+                             : octpt::projection_ray<true>(P, F, x, y, sample, o, d);
+            if ((d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) || std::isnan(d[0]) || std::isnan(d[1]) || std::isnan(d[2])) {
+                d[0] = 0.0f;  // Scene::hit's direction guard (scene/mod.rs:175-179), as octpt_lens_rays applies it
+                d[1] = 1.0f;
+                d[2] = 0.0f;
+            }
+        }
+        if (rng_state) rng_state[i] = st;
+    }
+    return OCTPT_OK;
+}
+
 // The mapping of DESIGN.md C26 alone: csrc/octpt_reproject.h's reproject_pixel, the text temporal_kernel compiles,
 // over the whole frame.
 extern "C" octpt_status octpt_reproject_coords(const octpt_camera *camera, const octpt_camera *prev_camera, uint32_t width,

@@ -130,8 +130,17 @@ struct DevCamera {
     float d_factor;  // 1 / tan(fov / 2)  (camera.rs:79)
     // the thin lens, read by the lens instances of seed, shade and the megakernel alone
     float aperture;     // lens radius, 0 = pinhole
-    float focal_scale;  // focal_distance / d_factor, divided once on the host (0 with aperture 0)
+    // The projection, read by the projected instances alone (octpt_kernels_proj.hip).  A camera has an
+    // aperture or a projection, never both (octpt_set_camera, octpt_set_projection), so the projection's float shares
+    // the lens's slot, and its mode takes the four bytes that padded the struct to the 8-byte alignment of the kernel
+    // argument after it: no kernel's argument block changed in size or layout.
+    union {
+        float focal_scale;  // focal_distance / d_factor, divided once on the host (0 with aperture 0)
+        float proj_half;    // octpt_projection::param * 0.5f, multiplied once on the host
+    };
+    uint32_t proj_mode;  // OCTPT_PROJECTION_*; 0 = pinhole
 };
+static_assert(sizeof(DevCamera) == 64, "DevCamera fills the 64 bytes it always took as a kernel argument");
 
 // n / d for a divisor d fixed per launch (Lemire, Kaser & Kurz 2019, "Faster remainder by direct computation"):
 // with c = ceil(2^64 / d), floor(c * n / 2^64) = floor(n / d) for every 32-bit n and 2 <= d < 2^32; c = 0 marks d = 1.
@@ -355,6 +364,15 @@ hipError_t launch_render(const DevScene &S, const DevCamera &C, const DevRender 
 const void *lens_render_kernel(bool nee, bool blocks);
 const void *lens_seed_kernel();
 const void *lens_shade_kernel(bool nee, bool lds, int mode);
+// the projected instances (C40; octpt_kernels_proj.hip, a module of its own), taken for a camera whose projection is not
+// pinhole: the same three, the preview's and the guide-buffer kernel's (prims: the scene's kPrims*), and the emitter
+// instances of the general shade (octpt_kernels_proj_emit.hip)
+const void *proj_render_kernel(bool nee, bool blocks);
+const void *proj_seed_kernel();
+const void *proj_shade_kernel(bool nee, bool lds, int mode);
+const void *proj_preview_kernel(int prims);
+const void *proj_gbuffer_kernel(int prims);
+const void *proj_emit_shade_kernel(bool nee, bool lds, int mode);
 hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t n_seed,
                           uint32_t chunk_items, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q, bool cam, uint32_t refill, int grid,

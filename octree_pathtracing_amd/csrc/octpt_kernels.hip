@@ -1399,13 +1399,17 @@ __device__ inline v3 random_sun_direction(const DevSun &K, uint32_t &rng) {
 // ---------------------------------------------------------------------------
 // path logic shared by the megakernel and the wavefront shade kernel
 // ---------------------------------------------------------------------------
-// camera ray + fresh path (camera.rs:77-86, tile_renderer.rs:695-703; lens_ray).  kLens: the
-// camera has an aperture, the ray leaves its point of the lens (the instances without it never read the lens)
-template <bool kLens = false>
+// camera ray + fresh path (camera.rs:77-86, tile_renderer.rs:695-703; lens_ray).  kCam, the form of
+// the camera the instance is compiled for: kCamPinhole; kCamLens, the camera has an aperture and the ray leaves its
+// point of the lens (C37); kCamProj, a parallel, fisheye or panoramic projection (projection_ray, C40), the mode a
+// field of the camera, uniform over the launch.  An instance reads only its own form's fields.
+constexpr int kCamPinhole = 0, kCamLens = 1, kCamProj = 2;
+template <int kCam = kCamPinhole>
 __device__ inline void new_path(const DevCamera &C, const DevRender &R, uint32_t x, uint32_t y, uint32_t sample,
                                 PathState &ps) {
     float o[3], d[3];
-    ps.rng = lens_ray<kLens>(C, R, x, y, sample, o, d);
+    if constexpr (kCam == kCamProj) ps.rng = projection_ray<true>(C, R, x, y, sample, o, d);
+    else ps.rng = lens_ray<kCam == kCamLens>(C, R, x, y, sample, o, d);
     ps.o = V(o[0], o[1], o[2]);
     ps.d = V(d[0], d[1], d[2]);
     ps.n = V(0.0f, 0.0f, 0.0f);
@@ -1782,7 +1786,7 @@ __device__ __forceinline__ uint32_t wave_ticket(uint32_t *ctr, bool want) {
 // ===========================================================================
 enum : uint32_t { ST_IDLE = 0, ST_NEWPATH, ST_BEGIN, ST_TRAV, ST_HIT, ST_MISS, ST_FINISH, ST_DONE };
 
-template <bool kNee, int kPrims, bool kLens = false>
+template <bool kNee, int kPrims, int kCam = kCamPinhole>
 __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C, DevRender R, float4 *__restrict__ accum,
                                                         uint32_t *__restrict__ segcount, uint32_t *__restrict__ counter,
                                                         unsigned long long *__restrict__ stats) {
@@ -1821,7 +1825,7 @@ __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C,
         }
         if (__ballot(state != ST_DONE) == 0ull) break;
         if (state == ST_NEWPATH) {
-            new_path<kLens>(C, R, pix % R.W, pix / R.W, R.spp_start + k, ray);
+            new_path<kCam>(C, R, pix % R.W, pix / R.W, R.spp_start + k, ray);
             cnt.paths++;
             state = ST_BEGIN;
         }
@@ -1890,7 +1894,8 @@ __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C,
 // one wave per SIMD above the natural allocation (78 / 86 / 102 VGPRs -> 72 / 80 / 96), as for extend
 #define OCTPT_PREVIEW_WAVES_OF(k) \
     (OCTPT_PREVIEW_BOUNDS ? ((k) == kPrimsSpheres ? 7 : ((k) == kPrimsBoxes || (k) == kPrimsBlocks) ? 6 : 5) : 1)
-template <int kPrims>
+// kProj (C40): the un-jittered ray of the camera's projection (projection_ray<false>) in place of get_ray's
+template <int kPrims, bool kProj = false>
 __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void preview_kernel(DevScene S, DevCamera C, DevRender R,
                                                          float4 *__restrict__ accum, uint32_t *__restrict__ segcount,
                                                          unsigned long long *__restrict__ stats) {
@@ -1911,6 +1916,12 @@ __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void previe
                            vscale(V(C.up[0], C.up[1], C.up[2]), yn));
         ps.o = V(C.eye[0], C.eye[1], C.eye[2]);
         ps.d = vnorm(nd);
+        if constexpr (kProj) {
+            float po[3], pd[3];
+            (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
+            ps.o = V(po[0], po[1], po[2]);
+            ps.d = V(pd[0], pd[1], pd[2]);
+        }
         ps.n = V(0.0f, 0.0f, 0.0f);
         ps.col[0] = ps.col[1] = ps.col[2] = ps.col[3] = 0.0f;
         ps.T = V(1.0f, 1.0f, 1.0f);
@@ -2118,7 +2129,7 @@ __device__ __forceinline__ size_t item_of(const DevRender &R, uint32_t s_local, 
 }
 
 // the path of chunk item `item`, its first segment begun; false when the pixel lies outside the image
-template <bool kFastDiv = true, bool kLens = false>
+template <bool kFastDiv = true, int kCam = kCamPinhole>
 __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R, uint32_t item, PathState &ps,
                                           uint32_t &x, uint32_t &y) {
     uint32_t s_local, px_item;
@@ -2131,7 +2142,7 @@ __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R
         sample = sb.x;
         branch = sb.y >> 16;
     }
-    new_path<kLens>(C, R, x, y, sample, ps);
+    new_path<kCam>(C, R, x, y, sample, ps);
     ps.branch = branch;
     begin_segment(ps);  // first segment: never capped
     return true;
@@ -2140,11 +2151,11 @@ __device__ __forceinline__ bool item_path(const DevCamera &C, const DevRender &R
 // generate the path of chunk item `item` into `slot`; false when the pixel lies outside the image.
 // kSeed (wf_seed_kernel): only the item is stored (item0); the chunk's first shade rebuilds the path
 // state from it (shade_lane) instead of reading 40 B per slot that the seed would have written.
-template <bool kSeed = false, bool kLens = false>
+template <bool kSeed = false, int kCam = kCamPinhole>
 __device__ inline bool seed_item(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t slot,
                                  uint32_t item, PathState &ps, Counters &cnt) {
     uint32_t x, y;
-    if (!item_path<true, kLens>(C, R, item, ps, x, y)) {
+    if (!item_path<true, kCam>(C, R, item, ps, x, y)) {
         B.color[item] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return false;
     }
@@ -2186,7 +2197,7 @@ struct ItemCursor {
 // with items left.  Items whose pixel lies outside the image are consumed (zero colour) and the
 // lane draws again, so a slot only goes idle once every shard is exhausted.  Every lane of the
 // wave must call this.
-template <bool kSeed = false, bool kLens = false>
+template <bool kSeed = false, int kCam = kCamPinhole>
 __device__ inline bool regen(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t slot, bool want,
                              uint32_t chunk_items, ItemCursor &cur, PathState &ps, Counters &cnt) {
     bool need = want, ok = false;
@@ -2196,7 +2207,7 @@ __device__ inline bool regen(const DevCamera &C, const DevRender &R, const WaveB
         bool dry = false;
         if (need) {
             if (t >= n) dry = true;
-            else if (seed_item<kSeed, kLens>(C, R, B, slot, lo + t, ps, cnt)) { ok = true; need = false; }
+            else if (seed_item<kSeed, kCam>(C, R, B, slot, lo + t, ps, cnt)) { ok = true; need = false; }
         }
         if (__ballot(dry) != 0ull) {
             const uint32_t j = threadIdx.x & 63u;
@@ -2217,9 +2228,10 @@ __device__ inline bool regen(const DevCamera &C, const DevRender &R, const WaveB
 // order, so the extend waves draining the 64 segments side by side trace the same image tile for
 // 64 sample groups (the item-claim path's order, whose L2 locality this keeps).  Otherwise slot i
 // claims items from the shards (regen).
-// kLens (C37): a camera with an aperture, whose rays have origins of their own: full ray records at the direct
-// positions (store_ray, slot = item) in place of the 16-B camera records, for the ordinary extend and first shade
-template <bool kLens = false>
+// kCam other than kCamPinhole (C37, C40): a camera with an aperture or a projection, whose rays may have origins of
+// their own: full ray records at the direct positions (store_ray, slot = item) in place of the 16-B camera records,
+// for the ordinary extend and first shade
+template <int kCam = kCamPinhole>
 __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender R, WaveBuffers B, uint32_t n_seed,
                                                          uint32_t chunk_items, unsigned long long *__restrict__ stats) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -2234,7 +2246,7 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         const uint32_t lo = shard_lo(seg, chunk_items), hi = shard_lo(seg + 1u, chunk_items);
         const uint32_t item = lo + (i >> 6) / kSegs * 64u + (i & 63u);
         slot = item;
-        if (item < hi) ok = seed_item<true, kLens>(C, R, B, slot, item, ps, cnt);
+        if (item < hi) ok = seed_item<true, kCam>(C, R, B, slot, item, ps, cnt);
         // Every tile inside the image (W and H multiples of the 8x8 tile: C3's 1080p, the 4K frames): no
         // item is dropped, so shard k's items fill segment k in item order -- position item - lo, the
         // count set by block 0 -- without a queue ticket per wave (8.3 M atomics per C3 frame on 64
@@ -2242,7 +2254,7 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         if (((R.W | R.H) & (kTile - 1u)) == 0u) {
             if (blockIdx.x == 0u && threadIdx.x < kSegs)
                 B.ctrl[ctr_count(0u, threadIdx.x)] = shard_lo(threadIdx.x + 1u, chunk_items) - shard_lo(threadIdx.x, chunk_items);
-            if constexpr (kLens) {
+            if constexpr (kCam != kCamPinhole) {
                 if (ok) store_ray(B, 0u, seg * B.seg_cap + (item - lo), slot, ps);
             } else {
                 if (ok) store_cam_ray(B, seg * B.seg_cap + (item - lo), ps);
@@ -2255,7 +2267,7 @@ __global__ __launch_bounds__(kBlock) void wf_seed_kernel(DevCamera C, DevRender 
         }
     } else {
         ItemCursor cur = {seg, true};
-        ok = regen<true, kLens>(C, R, B, i, i < n_seed, chunk_items, cur, ps, cnt);
+        ok = regen<true, kCam>(C, R, B, i, i < n_seed, chunk_items, cur, ps, cnt);
     }
     const uint32_t t = wave_ticket(B.ctrl + ctr_count(0u, seg), ok);
     if (ok) store_ray(B, 0u, seg * B.seg_cap + t, slot, ps);
@@ -2451,7 +2463,7 @@ __global__ __launch_bounds__(kBlock, OCTPT_EXTEND_WAVES_OF(kPrims)) void wf_exte
 // through the same pack / unpack as a stored path, instead of being read.
 // kLean: the state is read at (q, pos) and a continuing path's is not stored here: the caller
 // stores it at the position its next ray takes (store_lean_at).
-template <bool kNee, bool kLean = false, int kSP = kPrimsModels, bool kLens = false>
+template <bool kNee, bool kLean = false, int kSP = kPrimsModels, int kCam = kCamPinhole>
 __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C, const DevRender &R,
                                            const WaveBuffers &B, bool first, float4 r0, float4 r1, const uint2 *hit_rec,
                                            const uint4 *hit4_rec, PathState &ps, uint32_t &slot, uint32_t &item,
@@ -2461,12 +2473,13 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
         item = kLean ? slot : B.item0[slot];
         PathState s0;
         uint32_t x, y;
-        item_path<false, kLens>(C, R, item, s0, x, y);  // the seed only queued items inside the image
+        item_path<false, kCam>(C, R, item, s0, x, y);  // the seed only queued items inside the image
         float4 a, b;
         uint2 c;
         pack_path(s0, item, a, b, c);
-        // a camera ray's ray0 is (eye, kPrimNone), or with a lens (its origin as just rebuilt, kPrimNone): not re-read
-        unpack_path(a, b, c, kLens ? make_float4(s0.o.x, s0.o.y, s0.o.z, B.eye.w) : B.eye, r1, ps, item);
+        // a camera ray's ray0 is (eye, kPrimNone), or with a lens or a projection (its origin as just rebuilt,
+        // kPrimNone): not re-read
+        unpack_path(a, b, c, kCam != kCamPinhole ? make_float4(s0.o.x, s0.o.y, s0.o.z, B.eye.w) : B.eye, r1, ps, item);
     } else if constexpr (kLean) {  // L = +0 as the path started, item = slot (store_lean_at)
         const float4 a = (q ? B.pb : B.pa)[pos];
         unpack_path(make_float4(a.x, a.y, a.z, 0.0f), make_float4(0.0f, 0.0f, a.w, __uint_as_float(slot)),
@@ -2571,9 +2584,9 @@ constexpr uint32_t kShadeLdsBlocks = OCTPT_SHADE_LDS_BLOCKS;
 // regeneration, no sun sampling, kLean above)
 // kNoFirst: an instance for the chunk's later launches, compiled without the first
 // launch's path-state rebuild (first is 0)
-// kLens (C37): the camera has an aperture (the first launch's rebuild and the regeneration form lens rays); the
-// general instances (kMode 0 and 1) alone, a lens camera's chunks do not take the lean state
-template <bool kNee, bool kLdsMats, int kMode, bool kNoFirst = false, int kSP = kPrimsModels, bool kLens = false>
+// kCam (C37, C40): the camera has an aperture or a projection (the first launch's rebuild and the regeneration form
+// its rays); the general instances (kMode 0 and 1) alone, such a camera's chunks do not take the lean state
+template <bool kNee, bool kLdsMats, int kMode, bool kNoFirst = false, int kSP = kPrimsModels, int kCam = kCamPinhole>
 __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT_SHADE_WAVES) void wf_shade_kernel(DevScene Sg, DevCamera C, DevRender R, WaveBuffers B,
                                                           uint32_t q, uint32_t chunk_items, uint32_t first_arg,
                                                           unsigned long long *__restrict__ stats) {
@@ -2623,13 +2636,13 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT
                 cam_ray(B.eye, shard_lo(seg, chunk_items) + base + lane, r0c, r1);
             }
             const float4 r0 = first ? B.eye : B.ray0[q][i];  // (the chunk's first shade: the seed's camera rays)
-            append = shade_lane<kNee, kMode == 2, kSP, kLens>(S, C, R, B, first != 0u, r0, r1, B.hit + i,
+            append = shade_lane<kNee, kMode == 2, kSP, kCam>(S, C, R, B, first != 0u, r0, r1, B.hit + i,
                                                   S.has_blocks ? B.hit4 + i : nullptr, ps, slot, item, cnt, q, i);
             finished = !append;
         }
         // regenerate: finished lanes take the next chunk items (path regeneration)
         if constexpr (kMode == 1) {
-            if (regen<false, kLens>(C, R, B, slot, finished, chunk_items, cur, ps, cnt)) append = true;
+            if (regen<false, kCam>(C, R, B, slot, finished, chunk_items, cur, ps, cnt)) append = true;
         }
         const uint32_t t = wave_ticket(B.ctrl + ctr_count(q ^ 1u, seg), append);
         if (append) {
@@ -3188,7 +3201,8 @@ __global__ void multi_stage_kernel(DevRender R, uint32_t n_dev, uint32_t stride,
 // the natural allocation)
 #define OCTPT_GBUFFER_WAVES_OF(k) \
     (OCTPT_GBUFFER_BOUNDS ? ((k) == kPrimsSpheres ? 7 : ((k) == kPrimsBoxes || (k) == kPrimsBlocks) ? 6 : 5) : 1)
-template <int kPrims>
+// kProj (C40): the preview's projected ray
+template <int kPrims, bool kProj = false>
 __global__ __launch_bounds__(kBlock, OCTPT_GBUFFER_WAVES_OF(kPrims)) void gbuffer_kernel(DevScene S, DevCamera C, DevRender R,
                                                                                          DevAov out,
                                                                                          unsigned long long *__restrict__ stats) {
@@ -3208,6 +3222,12 @@ __global__ __launch_bounds__(kBlock, OCTPT_GBUFFER_WAVES_OF(kPrims)) void gbuffe
                            vscale(V(C.up[0], C.up[1], C.up[2]), yn));
         ps.o = V(C.eye[0], C.eye[1], C.eye[2]);
         ps.d = vnorm(nd);
+        if constexpr (kProj) {
+            float po[3], pd[3];
+            (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
+            ps.o = V(po[0], po[1], po[2]);
+            ps.d = V(pd[0], pd[1], pd[2]);
+        }
         ps.n = V(0.0f, 0.0f, 0.0f);
         ps.col[0] = ps.col[1] = ps.col[2] = ps.col[3] = 0.0f;
         ps.T = V(1.0f, 1.0f, 1.0f);
@@ -3718,7 +3738,52 @@ __global__ __launch_bounds__(256) void atrous_var_kernel(DevDenoiseVar D, uint32
 
 }  // namespace
 
-#if defined(OCTPT_LENS_TU)  // (set by octpt_kernels_lens.hip alone: not a build switch)
+#if defined(OCTPT_PROJ_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_proj_emit.hip alone: not a build switch)
+// The emitter instances (C38) of the general shade for a projected camera (C40), a module of their own like every
+// other family, so that octpt_kernels_emit.hip's instances stay the code they are.
+template <bool kNee, bool kLds>
+static const void *proj_emit_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamProj>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamProj>);
+}
+const void *proj_emit_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? proj_emit_shade_of<true, true>(mode) : proj_emit_shade_of<true, false>(mode))
+               : (lds ? proj_emit_shade_of<false, true>(mode) : proj_emit_shade_of<false, false>(mode));
+}
+#elif defined(OCTPT_PROJ_TU)  // (set by octpt_kernels_proj.hip alone: not a build switch)
+// The projected instances (C40) of the megakernel, the seed, the general shade, the preview and the guide-buffer
+// kernel, for octpt_kernels_proj.hip, which compiles this text for them alone (a module of their own, as the lens
+// instances below are, and for their reason).
+const void *proj_render_kernel(bool nee, bool blocks) {
+    return nee ? (blocks ? reinterpret_cast<const void *>(render_kernel<true, kPrimsBlocks, kCamProj>)
+                         : reinterpret_cast<const void *>(render_kernel<true, kPrimsModels, kCamProj>))
+               : (blocks ? reinterpret_cast<const void *>(render_kernel<false, kPrimsBlocks, kCamProj>)
+                         : reinterpret_cast<const void *>(render_kernel<false, kPrimsModels, kCamProj>));
+}
+const void *proj_seed_kernel() { return reinterpret_cast<const void *>(wf_seed_kernel<kCamProj>); }
+template <bool kNee, bool kLds>
+static const void *proj_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamProj>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamProj>);
+}
+const void *proj_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? proj_shade_of<true, true>(mode) : proj_shade_of<true, false>(mode))
+               : (lds ? proj_shade_of<false, true>(mode) : proj_shade_of<false, false>(mode));
+}
+// prims: the scene's primitive kinds, as launch_preview and launch_gbuffer pick their instances
+const void *proj_preview_kernel(int prims) {
+    return prims == kPrimsBlocks   ? reinterpret_cast<const void *>(preview_kernel<kPrimsBlocks, true>)
+           : prims == kPrimsModels ? reinterpret_cast<const void *>(preview_kernel<kPrimsModels, true>)
+           : prims == kPrimsBoxes  ? reinterpret_cast<const void *>(preview_kernel<kPrimsBoxes, true>)
+                                   : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres, true>);
+}
+const void *proj_gbuffer_kernel(int prims) {
+    return prims == kPrimsBlocks   ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBlocks, true>)
+           : prims == kPrimsModels ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsModels, true>)
+           : prims == kPrimsBoxes  ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBoxes, true>)
+                                   : reinterpret_cast<const void *>(gbuffer_kernel<kPrimsSpheres, true>);
+}
+#elif defined(OCTPT_LENS_TU)  // (set by octpt_kernels_lens.hip alone: not a build switch)
 // The lens instances (C37) of the megakernel, the seed and the general shade, for octpt_kernels_lens.hip, which
 // compiles this text for them alone.  A module of their own: in one module with the others they change how the
 // compiler inlines the functions they share, and with it the registers of the instances without a lens (the
@@ -3789,6 +3854,11 @@ int extend_blocks_per_cu(const DevScene &S) {
     return blocks > 0 ? blocks : 1;
 }
 
+// the primitive kinds of a scene, as the preview and guide-buffer instances are compiled per kind
+static int scene_prims(const DevScene &S) {
+    return S.has_blocks ? kPrimsBlocks : S.has_models ? kPrimsModels : S.has_cuboids ? kPrimsBoxes : kPrimsSpheres;
+}
+
 hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRender &R, float4 *accum,
                           uint32_t *segcount, unsigned long long *stats, hipStream_t stream) {
     const DevScene &S = S0;
@@ -3798,6 +3868,7 @@ hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRende
                      : S.has_models ? reinterpret_cast<const void *>(preview_kernel<kPrimsModels>)
                      : S.has_cuboids ? reinterpret_cast<const void *>(preview_kernel<kPrimsBoxes>)
                                      : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres>);
+    if (C.proj_mode != 0u) fn = proj_preview_kernel(scene_prims(S));  // the projected instance (C40)
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), &accum,
                     &segcount, &stats};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args,
@@ -3814,6 +3885,7 @@ hipError_t launch_gbuffer(const DevScene &S, const DevCamera &C, const DevRender
                      : S.has_models ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsModels>)
                      : S.has_cuboids ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBoxes>)
                                      : reinterpret_cast<const void *>(gbuffer_kernel<kPrimsSpheres>);
+    if (C.proj_mode != 0u) fn = proj_gbuffer_kernel(scene_prims(S));  // the projected instance (C40)
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
                     const_cast<DevAov *>(&out), &stats};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, render_lds_bytes(S.depth), stream);
@@ -3869,11 +3941,12 @@ hipError_t launch_render(const DevScene &S0, const DevCamera &C, const DevRender
     // the general instance (spheres, cuboids, cuboid models) or the block-value one (C23)
     auto kern = S.sun.sun_sampling ? (S.has_blocks ? render_kernel<true, kPrimsBlocks> : render_kernel<true, kPrimsModels>)
                                    : (S.has_blocks ? render_kernel<false, kPrimsBlocks> : render_kernel<false, kPrimsModels>);
-    if (C.aperture > 0.0f) {  // the lens instance (C37)
+    if (C.aperture > 0.0f || C.proj_mode != 0u) {  // the lens instance (C37) or the projected one (C40)
         void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), &accum,
                         &segcount, &counter, &stats};
-        const hipError_t e = hipLaunchKernel(lens_render_kernel(S.sun.sun_sampling != 0, S.has_blocks != 0u), dim3(grid),
-                                             dim3(kBlock), args, render_lds_bytes(S.depth), stream);
+        const void *fn = C.proj_mode != 0u ? proj_render_kernel(S.sun.sun_sampling != 0, S.has_blocks != 0u)
+                                           : lens_render_kernel(S.sun.sun_sampling != 0, S.has_blocks != 0u);
+        const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, render_lds_bytes(S.depth), stream);
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
@@ -3889,14 +3962,15 @@ hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuff
                                  ? (uint64_t)kSegs * ((((uint64_t)chunk_items + kSegs - 1u) / kSegs + 63u) / 64u) * 64u
                                  : (uint64_t)n_seed;
     const dim3 grid((uint32_t)((threads + kBlock - 1u) / kBlock));
-    if (C.aperture > 0.0f) {  // the lens instance (C37)
+    if (C.aperture > 0.0f || C.proj_mode != 0u) {  // the lens instance (C37) or the projected one (C40)
         void *args[] = {const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), const_cast<WaveBuffers *>(&B), &n_seed,
                         &chunk_items, &stats};
-        const hipError_t e = hipLaunchKernel(lens_seed_kernel(), grid, dim3(kBlock), args, 0, stream);
+        const hipError_t e = hipLaunchKernel(C.proj_mode != 0u ? proj_seed_kernel() : lens_seed_kernel(), grid,
+                                             dim3(kBlock), args, 0, stream);
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(wf_seed_kernel<false>, grid, dim3(kBlock), 0, stream, C, R, B, n_seed, chunk_items, stats);
+    hipLaunchKernelGGL(wf_seed_kernel<kCamPinhole>, grid, dim3(kBlock), 0, stream, C, R, B, n_seed, chunk_items, stats);
     return hipGetLastError();
 }
 
@@ -3934,13 +4008,17 @@ static const void *shade_instance_of(int mode, bool first, int prims) {
                      : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0>);
 }
 bool shade_lds_tables(const DevScene &S) { return S.n_mats <= kShadeLdsMats && S.n_texs <= kShadeLdsMats; }
-static const void *shade_instance(const DevScene &S, int mode, bool first = false, bool lens = false,
+static const void *shade_instance(const DevScene &S, int mode, bool first = false, int cam = kCamPinhole,
                                   bool emit = false) {
     const bool lds = shade_lds_tables(S);
     // emitter sampling (C38): the general instances' emitter twins (such chunks never take the lean state)
-    if (emit) return emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode, lens);
-    // a lens camera (C37): the general instances' lens twins (enqueue_wavefront keeps such chunks off the lean state)
-    if (lens) return lens_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
+    if (emit)
+        return cam == kCamProj ? proj_emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode)
+                               : emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode, cam == kCamLens);
+    // a lens camera (C37) or a projection (C40): the general instances' twins (enqueue_wavefront keeps such chunks
+    // off the lean state)
+    if (cam == kCamProj) return proj_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
+    if (cam == kCamLens) return lens_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
     const int prims = S.has_blocks    ? kPrimsBlocks
                       : S.has_models  ? kPrimsModels
                       : S.has_cuboids ? kPrimsBoxes
@@ -3964,7 +4042,8 @@ hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRende
     uint32_t first_u = first;
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
                     const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
-    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, C.aperture > 0.0f, emit),
+    const int cam = C.proj_mode != 0u ? kCamProj : C.aperture > 0.0f ? kCamLens : kCamPinhole;
+    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, cam, emit),
                                          dim3(grid), dim3(kBlock), args, 0, stream);
     if (e != hipSuccess) return e;
     return hipGetLastError();

@@ -136,4 +136,83 @@ OCTPT_LENS_FN uint32_t lens_ray(const Cam &C, const Frame &R, uint32_t x, uint32
     return st;
 }
 
+// ---------------------------------------------------------------------------
+// camera projections: the parallel, fisheye and panoramic first ray
+// ---------------------------------------------------------------------------
+// octpt_projection::mode (include/octpt.h has the same values); pinhole is lens_ray above, untouched
+constexpr uint32_t kProjPinhole = 0u, kProjParallel = 1u, kProjFisheye = 2u, kProjPanoramic = 3u;
+constexpr float kProjTwoPi = 6.28318530717958647692f;  // rounds to the f32 above 2 pi: the largest angle accepted
+
+// what projection_ray reads of a camera beside its basis (DevCamera has these fields too)
+struct ProjCamera {
+    float eye[3], dir[3], right[3], up[3];
+    uint32_t proj_mode;  // kProj*, not kProjPinhole
+    float proj_half;     // param * 0.5f, multiplied once on the host: half the extent, or half the angle
+};
+// host: octpt_set_projection's rule for mode and param (kProjPinhole reads no param); false on NaN
+inline bool proj_mode_known(uint32_t mode) { return mode <= kProjPanoramic; }
+inline bool proj_param_valid(uint32_t mode, float param) {
+    if (mode == kProjPinhole) return true;
+    if (!(param > 0.0f && param < INFINITY)) return false;
+    return mode == kProjParallel || param <= kProjTwoPi;
+}
+
+// The first ray of a non-pinhole projection.  The common part -- st0, xn, yn, the two jitter draws, sx, sy, the
+// returned state, the final normalisation -- is lens_ray's, so a path's later draws do not depend on the projection.
+// kJitter false: the un-jittered ray of the preview and the guide buffers, dx = dy = 0 (no draw; returns st0).
+// dm_sincos takes lon, lat in [-pi, pi] and fisheye angles up to pi * sqrt(2) as they are: its three-part pi/2
+// reduction is exact for |k| <= 3 quadrants and `k & 3` is the quadrant of a negative k too (C40 has the figures).
+template <bool kJitter, class Cam, class Frame>
+OCTPT_LENS_FN uint32_t projection_ray(const Cam &C, const Frame &R, uint32_t x, uint32_t y, uint32_t sample,
+                                      float o[3], float d[3]) {
+    const uint32_t st0 = path_state(R.seed, y * R.W + x, sample);
+    uint32_t st = st0;
+    const float jlo = R.jlo, jhi = R.jhi;  // -1 / dim, 1 / dim
+    const float xn = ((float)(2u * x + 1u) - (float)R.W) / R.dim;
+    const float yn = ((float)(2u * (R.H - y) - 1u) - (float)R.H) / R.dim;
+    float dx = 0.0f, dy = 0.0f;
+    if (kJitter) {
+        dx = jlo + (jhi - jlo) * rng_next(st);
+        dy = jlo + (jhi - jlo) * rng_next(st);
+    }
+    const float sx = xn + dx, sy = yn + dy;
+    const float hf = C.proj_half;
+    float t[3];
+    if (C.proj_mode == kProjParallel) {
+        const float a = sx * hf, b = sy * hf;
+        for (int i = 0; i < 3; ++i) {
+            o[i] = (C.eye[i] + C.right[i] * a) + C.up[i] * b;
+            t[i] = C.dir[i];
+        }
+    } else if (C.proj_mode == kProjFisheye) {  // equidistant: the angle from the axis grows with the image radius
+        const float ax = sx * hf, ay = sy * hf;
+        const float ang = sqrtf(ax * ax + ay * ay);
+        float cs = 1.0f, ka = 0.0f, kb = 0.0f;
+        if (ang != 0.0f) {
+            float sn;
+            dm_sincos(ang, sn, cs);
+            const float k = sn / ang;
+            ka = ax * k;
+            kb = ay * k;
+        }
+        for (int i = 0; i < 3; ++i) {
+            o[i] = C.eye[i];
+            t[i] = ang != 0.0f ? (C.dir[i] * cs + C.right[i] * ka) + C.up[i] * kb : C.dir[i];
+        }
+    } else {  // kProjPanoramic, equirectangular: sx is the longitude, sy the latitude
+        const float lon = sx * hf, lat = sy * hf;
+        float sl, cl, so, co;
+        dm_sincos(lat, sl, cl);
+        dm_sincos(lon, so, co);
+        const float a = cl * co, b = cl * so;
+        for (int i = 0; i < 3; ++i) {
+            o[i] = C.eye[i];
+            t[i] = (C.dir[i] * a + C.right[i] * b) + C.up[i] * sl;
+        }
+    }
+    const float rn = 1.0f / sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+    for (int i = 0; i < 3; ++i) d[i] = t[i] * rn;
+    return st;
+}
+
 }  // namespace octpt

@@ -187,6 +187,9 @@ octpt_status check_temporal(octpt_ctx *ctx, const char *who, bool moments, const
                             const octpt_aov_buffers *g, const octpt_temporal_history *prev, const void *out,
                             const void *out_length) {
     const std::string w = std::string(who) + ": ";
+    // the mapping is the pinhole camera's: a context whose renders are projected otherwise has no history to carry (C40)
+    if (ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + "the context's projection is not pinhole (octpt_set_projection)");
     if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, std::string(who) + " params NULL");
     if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "zero frame size");
     if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
@@ -346,6 +349,17 @@ octpt_status octpt_temporal(octpt_ctx *ctx, const octpt_temporal_params *p, cons
     return guarded(ctx, "temporal", [&]() -> octpt_status {
         return temporal_host(ctx, p, color, g, prev, nullptr, out, out_length, nullptr);
     });
+}
+
+// octpt_reproject_coords for a context's frames: refused while the context's projection is not pinhole (C40)
+octpt_status octpt_reproject_coords_ctx(octpt_ctx *ctx, const octpt_camera *camera, const octpt_camera *prev_camera,
+                                        uint32_t width, uint32_t height, const float *depth, float *prev_xy,
+                                        float *prev_depth) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "reproject_coords: the context's projection is not pinhole (octpt_set_projection)");
+    const octpt_status st = octpt_reproject_coords(camera, prev_camera, width, height, depth, prev_xy, prev_depth);
+    return st == OCTPT_OK ? st : fail(ctx, st, "reproject_coords: refused (octpt_reproject_coords' rules)");
 }
 
 // ---------------- luminance moments, variance and the variance-guided filter (C27-C29) ----------------

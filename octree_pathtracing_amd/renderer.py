@@ -8,6 +8,7 @@ reset_render).  Every render goes to the gfx950 kernels; there is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import enum
 
 import numpy as np
@@ -146,11 +147,44 @@ class HipRenderer:
         return self._camera
 
     def set_camera(self, camera: Camera) -> None:
-        c = _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction),
-                        (C.c_float * 3)(*camera.up), camera.fov, camera.aperture, camera.focal_distance)
-        self._check(self._lib.octpt_set_camera(self._ctx, C.byref(c)))
+        """octpt_set_camera, and the camera's projection through set_projection.  The library refuses
+        an aperture together with a projection other than pinhole whichever call comes second, so the order is: the
+        pinhole projection, the camera, any other projection.  A refused call leaves both as they were."""
+        mode, param = int(camera.projection[0]), float(camera.projection[1])
+        pinhole = mode == _lib.PROJECTION_PINHOLE
+        if not pinhole and camera.aperture > 0.0:
+            raise _lib.OctptError(_lib.ERR_UNSUPPORTED, "an aperture needs the pinhole projection")
+        old = self._camera
+        changed = (mode, param) != tuple(old.projection)  # else the setter is not called
+        if pinhole and changed:
+            self.set_projection(mode, param)
+        try:
+            self._check(self._lib.octpt_set_camera(self._ctx, C.byref(_c_camera(camera, lens=True))))
+            if not pinhole and changed:
+                self.set_projection(mode, param)
+        except _lib.OctptError:
+            # one of the two is already set; the other call, refused, left its half as it was
+            if pinhole and changed:
+                self.set_projection(*old.projection)
+            else:
+                self._lib.octpt_set_camera(self._ctx, C.byref(_c_camera(old, lens=True)))
+            raise
         self._camera = camera
         self.reset_render()
+
+    def set_projection(self, mode: int, param: float = 0.0) -> None:
+        """octpt_set_projection: _lib.PROJECTION_PINHOLE (a new renderer's), PARALLEL (param: the world-space length
+        across the longer image side), FISHEYE or PANORAMIC (param: the full angle across it, radians, at most 2 pi),
+        for every later render of this renderer -- path traced, preview and guide buffers."""
+        p = _lib.Projection(int(mode), float(param))
+        self._check(self._lib.octpt_set_projection(self._ctx, C.byref(p)))
+        self._camera = dataclasses.replace(self._camera, projection=(int(mode), float(param)))
+        self.reset_render()
+
+    def get_projection(self) -> tuple:
+        p = _lib.Projection()
+        self._check(self._lib.octpt_get_projection(self._ctx, C.byref(p)))
+        return int(p.mode), float(p.param)
 
     def which_backend(self) -> str:
         return "HIP (gfx950)"
@@ -353,6 +387,25 @@ class HipRenderer:
         """octpt_lens_rays of the current camera: [H, W, 6], the first ray a W x H render with this seed traces
         for sample `sample` of each pixel, bit for bit."""
         return lens_rays(self._camera, W, H, seed, sample)
+
+    def projection_rays(self, W: int, H: int, seed: int, xys, centre: bool = False):
+        """octpt_projection_rays of the current camera and its projection: for rows (x, y, sample) the first rays
+        [n, 6] a W x H render with this seed traces, bit for bit, and the paths' RNG states after them [n]; centre:
+        the un-jittered rays of the preview and the guide buffers."""
+        return projection_rays(self._camera, W, H, seed, xys, centre=centre)
+
+    def reproject_coords(self, prev_camera: Camera, W: int, H: int, depth: np.ndarray):
+        """octpt_reproject_coords_ctx for this renderer's camera and frames: reproject_coords, refused (UNSUPPORTED)
+        while the renderer's projection is not pinhole."""
+        depth = np.ascontiguousarray(depth, np.float32)
+        if depth.size != W * H:
+            raise ValueError(f"depth holds {depth.size} pixels, not {W} x {H}")
+        xy = np.zeros((H, W, 2), np.float32)
+        zp = np.zeros((H, W), np.float32)
+        self._check(self._lib.octpt_reproject_coords_ctx(
+            self._ctx, C.byref(_c_camera(self._camera)), C.byref(_c_camera(prev_camera)), W, H,
+            depth.ctypes.data_as(C.c_void_p), xy.ctypes.data_as(C.c_void_p), zp.ctypes.data_as(C.c_void_p)))
+        return xy, zp
 
     def render_aov(self, settings: RenderSettings, which=_lib.AOV_NAMES, shard=(0, 1), compact: bool = False,
                    out: dict | None = None) -> dict:
@@ -845,10 +898,33 @@ def lens_rays(camera: Camera, W: int, H: int, seed: int, sample: int) -> np.ndar
     return rays
 
 
-def _c_camera(camera: Camera) -> "_lib.Camera":
+def frame_samples(W: int, H: int, sample: int) -> np.ndarray:
+    """Rows (x, y, sample) for every pixel of a W x H frame in image order: projection_rays' xys for one sample."""
+    ys, xs = np.mgrid[0:H, 0:W]
+    return np.stack([xs.ravel(), ys.ravel(), np.full(W * H, sample)], 1).astype(np.uint32)
+
+
+def projection_rays(camera: Camera, W: int, H: int, seed: int, xys, centre: bool = False):
+    """octpt_projection_rays: for rows (x, y, sample) of `xys` the first rays [n, 6] f32 (origin, unit direction) that
+    a W x H render with this seed traces under camera.projection, and the paths' RNG states after them [n] u32
+    (host-only, no context).  centre: the un-jittered pixel-centre rays of the preview and the guide buffers."""
+    xys = np.ascontiguousarray(xys, np.uint32).reshape(-1, 3)
+    c = _c_camera(camera, lens=True)
+    p = _lib.Projection(int(camera.projection[0]), float(camera.projection[1]))
+    rays = np.zeros((len(xys), 6), np.float32)
+    state = np.zeros(len(xys), np.uint32)
+    st = _lib.load().octpt_projection_rays(C.byref(c), C.byref(p), W, H, seed, xys.ctypes.data_as(C.c_void_p), len(xys),
+                                           _lib.PROJECTION_RAYS_CENTRE if centre else 0,
+                                           rays.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p))
+    if st != 0:
+        raise _lib.OctptError(st, "octpt_projection_rays")
+    return rays, state
+
+
+def _c_camera(camera: Camera, lens: bool = False) -> "_lib.Camera":
     # (the temporal entries take the camera without its lens: they refuse an aperture, DESIGN.md C37)
     return _lib.Camera((C.c_float * 3)(*camera.eye), (C.c_float * 3)(*camera.direction), (C.c_float * 3)(*camera.up),
-                       camera.fov, 0.0, 0.0)
+                       camera.fov, camera.aperture if lens else 0.0, camera.focal_distance if lens else 0.0)
 
 
 def reproject_coords(camera: Camera, prev_camera: Camera, W: int, H: int, depth: np.ndarray):

@@ -126,6 +126,23 @@ class Camera:
     # focus, read only with an aperture
     aperture: float = 0.0
     focal_distance: float = 0.0
+    # the projection: (mode, param), mode one of _lib.PROJECTION_*; param is the world-space length
+    # across the longer image side (parallel) or the full angle across it in radians (fisheye, panoramic), unread for
+    # the pinhole.  fov is not read by the three other modes.
+    projection: tuple = (0, 0.0)
+
+    def parallel(self, extent: float) -> "Camera":
+        """A copy with the parallel projection: the longer image side spans `extent` world units (isometric maps)."""
+        return dataclasses_replace(self, projection=(1, float(extent)))
+
+    def fisheye(self, angle: float) -> "Camera":
+        """A copy with the equidistant fisheye projection: `angle` radians across the longer image side."""
+        return dataclasses_replace(self, projection=(2, float(angle)))
+
+    def panoramic(self, angle: float) -> "Camera":
+        """A copy with the equirectangular projection: `angle` radians of longitude across the longer image side
+        (2 pi at width = 2 * height is the full 360 x 180 degree panorama)."""
+        return dataclasses_replace(self, projection=(3, float(angle)))
 
     def focus(self, focal_point, aperture: float) -> "Camera":
         """Camera::focus (camera.rs:69-73), evaluated in f32: a copy focused on focal_point with this aperture."""
