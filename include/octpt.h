@@ -336,6 +336,37 @@ typedef struct octpt_projection {
 octpt_status octpt_set_projection(octpt_ctx *ctx, const octpt_projection *projection);
 octpt_status octpt_get_projection(const octpt_ctx *ctx, octpt_projection *projection);
 
+/* The ray source: a path's first ray read from a buffer the caller fills, so that any camera -- a
+ * stereo panorama, a cube-map face, a distorted lens, a light probe -- is a few lines of host code.  The ray of sample
+ * s of pixel (x, y) is the six floats at d_rays[6 * ((y * width + x) * rays_per_pixel + s % rays_per_pixel)]: origin
+ * xyz, then direction xyz; s is the absolute sample index (spp_start plus the index in the call), so split calls go on
+ * through the list, and samples beyond rays_per_pixel wrap round.  The floats are used as given (the direction is not
+ * renormalised).  A record is valid when all six floats are finite and the direction's squared length, (dx^2 + dy^2) +
+ * dz^2 in f32, lies within 1e-4 of 1; an invalid record is replaced whole by the central ray of the context's camera
+ * (eye, direction), so no bit pattern in the buffer makes anything but an ordinary path.  Only the first ray changes:
+ * a path's random draws are what they are under every other camera (the two jitter draws are made and dropped).
+ * d_rays is memory of the context's device and stays the caller's: it must remain valid and unchanged until every
+ * render that reads it has completed.  The call joins a frame in flight; the setting is read when a render call is
+ * made and holds until it is cleared (a NULL source or NULL d_rays; the other fields are then not read).
+ * Followed by: sync, device, async, tile-list, adaptive and final wavefront renders, strategy ONE emitter sampling
+ * included; OCTPT_RENDER_PREVIEW and the guide buffers (octpt_render_aov*) trace ray 0 of each pixel, the depth guide
+ * being the distance from that ray's origin.  Camera-ray beam starts are off under a source.
+ * INVALID_ARG: a non-zero reserved word, rays_per_pixel, width or height 0, width * height * rays_per_pixel above
+ * 2^28, and a render whose width or height is not the source's.  UNSUPPORTED: a multi-device context; a camera with an
+ * aperture or a projection other than PINHOLE -- and, while a source is set, octpt_set_camera with an aperture and
+ * octpt_set_projection with another mode (whichever comes second is refused, the earlier setting stays); a render with
+ * OCTPT_RENDER_MEGAKERNEL; octpt_temporal* and octpt_reproject_coords_ctx.  Every check comes before any write: a
+ * refused call changes nothing.  With the source cleared every render is bit for bit that of a context that never
+ * had one. */
+typedef struct octpt_ray_source {
+    const float *d_rays;     /* device memory of the context's device; NULL = no ray source (the state of a new context) */
+    uint32_t width, height;  /* the frame the list is for */
+    uint32_t rays_per_pixel; /* R >= 1 */
+    uint32_t reserved[5];    /* 0 */
+} octpt_ray_source;
+octpt_status octpt_set_ray_source(octpt_ctx *ctx, const octpt_ray_source *source);
+octpt_status octpt_get_ray_source(const octpt_ctx *ctx, octpt_ray_source *source);
+
 /* Synchronous render into host memory.  accum_rgba: width*height*4 floats (or the shard's
  * compact tiles), in/out running mean, initialise to F32Color::BLACK (0,0,0,1).
  * out_rgba8 (nullable): tone-mapped U8Color image (colors/mod.rs:408-420) of accum. */
@@ -438,6 +469,17 @@ octpt_status octpt_lens_rays(const octpt_camera *camera, uint32_t width, uint32_
 octpt_status octpt_projection_rays(const octpt_camera *camera, const octpt_projection *projection, uint32_t width,
                                    uint32_t height, uint32_t seed, const uint32_t *xys, uint32_t n, uint32_t flags,
                                    float *rays, uint32_t *rng_state);
+/* The first ray under a ray source, for n chosen samples: `rays` is a host copy of the list
+ * (octpt_ray_source's layout for this width, height and rays_per_pixel), xys[3 * i] = (x, y, sample), and
+ * out_rays[6 * i] = the ray a render with this seed traces for that sample -- the record as given, or, where it is
+ * invalid, the central ray (eye, direction) of `fallback` -- bit for bit (one text, csrc/octpt_lens.h's ray_list_ray).
+ * rng_state (nullable): rng_state[i] = the path's RNG state after the ray, octpt_projection_rays' for the same
+ * (x, y, sample, seed).  `fallback` follows octpt_lens_rays' rules; a zero width, height or rays_per_pixel, more than
+ * 2^28 rays, x >= width or y >= height: INVALID_ARG.  Every check comes before the first write.  Host-only, no
+ * context. */
+octpt_status octpt_ray_source_rays(const octpt_camera *fallback, const float *rays, uint32_t width, uint32_t height,
+                                   uint32_t rays_per_pixel, uint32_t seed, const uint32_t *xys, uint32_t n,
+                                   float *out_rays, uint32_t *rng_state);
 
 /* First-hit guide buffers (AOVs) of the preview's camera ray (C24): one un-jittered ray per pixel, continued
  * through material-0 and alpha-0 hits exactly as RendererMode::Preview continues it (preview_render,

@@ -221,6 +221,12 @@ class Projection(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("param", C.c_float), ("reserved", C.c_uint32 * 6)]
 
 
+class RaySource(C.Structure):
+    """octpt_ray_source (octpt_set_ray_source): the caller's list of first rays and its shape."""
+    _fields_ = [("d_rays", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("rays_per_pixel", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp_start", C.c_uint32), ("spp_count", C.c_uint32),
                 ("max_depth", C.c_uint32), ("branch_count", C.c_uint32), ("seed", C.c_uint32),
@@ -360,6 +366,8 @@ SIGNATURES = {
     "octpt_get_camera": (_i32, [_vp, C.POINTER(Camera)]),
     "octpt_set_projection": (_i32, [_vp, C.POINTER(Projection)]),
     "octpt_get_projection": (_i32, [_vp, C.POINTER(Projection)]),
+    "octpt_set_ray_source": (_i32, [_vp, C.POINTER(RaySource)]),
+    "octpt_get_ray_source": (_i32, [_vp, C.POINTER(RaySource)]),
     "octpt_render": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp]),
     "octpt_render_device": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]),
     "octpt_render_async": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, C.POINTER(_vp)]),
@@ -378,6 +386,7 @@ SIGNATURES = {
     "octpt_lens_rays": (_i32, [C.POINTER(Camera), _u32, _u32, _u32, _u32, _vp]),
     "octpt_projection_rays": (_i32, [C.POINTER(Camera), C.POINTER(Projection), _u32, _u32, _u32, _vp, _u32, _u32, _vp,
                                      _vp]),
+    "octpt_ray_source_rays": (_i32, [C.POINTER(Camera), _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
     "octpt_render_aov": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers)]),
     "octpt_render_aov_device": (_i32, [_vp, C.POINTER(RenderParams), C.POINTER(AovBuffers), _vp]),
     "octpt_denoise_device": (_i32, [_vp, C.POINTER(DenoiseParams), _vp, C.POINTER(AovBuffers), _vp, _vp]),

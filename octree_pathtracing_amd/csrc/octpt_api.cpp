@@ -533,6 +533,13 @@ octpt_status octpt::make_render(octpt_ctx *ctx, const octpt_render_params *p, De
     if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= (1ull << 31))
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "bad resolution");
     if (p->max_depth == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, "max_depth must be >= 1");
+    if (ctx->rays.d_rays) {  // a ray source (C41) is a list for one frame size, and has no megakernel instance
+        if (p->width != ctx->rays.width || p->height != ctx->rays.height)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                        "render size differs from the ray source's (octpt_set_ray_source; NULL clears it)");
+        if ((p->flags & OCTPT_RENDER_MEGAKERNEL) && !(p->flags & OCTPT_RENDER_PREVIEW))
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a ray source is set: it runs on the wavefront path only");
+    }
     if (ctx->emit_strategy == OCTPT_EMITTERS_ONE && !(p->flags & OCTPT_RENDER_PREVIEW)) {  // C38
         const octpt_ctx *gc = ctx->sub.empty() ? ctx : ctx->sub[0];  // a multi-device context: its entries hold the scene
         if (!gc->S.has_blocks)
@@ -811,6 +818,8 @@ octpt_status enqueue_megakernel(octpt_ctx *ctx, const DevRender &R, float4 *d_ac
 octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_accum, uint32_t *d_seg, hipStream_t s,
                                const std::atomic<bool> *cancel, float2 *d_moments = nullptr, uint64_t list = 0) {
     const uint64_t n_px = R.total_items;
+    // the camera as the kernels take it: under a ray source (C41) it carries the caller's list
+    const DevCamera C = ray_source_camera(ctx);
     // the sample clamp (C33) as set when the render call was made: octpt_set_sample_clamp joins a frame in flight
     const float clamp = ctx->sample_clamp;
     // emitter sampling (C38): strategy ONE over a grid that holds emitters, in a scene whose emitters are enabled,
@@ -909,7 +918,8 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     // pyramid from the eye without bound, so the table is not conservative for it
     // A projection other than pinhole (C40) likewise: the table is computed for the pinhole's pyramids, and such rays
     // take the lens's path through the chunk (origins of their own, full records, the general shade's twins)
-    const bool lens = ctx->C.aperture > 0.0f || ctx->C.proj_mode != OCTPT_PROJECTION_PINHOLE;
+    // A ray source (C41) likewise: its camera's proj_mode is kProjModeRays
+    const bool lens = C.aperture > 0.0f || C.proj_mode != OCTPT_PROJECTION_PINHOLE;
     const float *beam = nullptr;
     if (ctx->beam && !lens) {
         const size_t n_tiles = (size_t)R.beam_tx * ((R.H + kBeamTile - 1) / kBeamTile);
@@ -942,7 +952,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             // so the device drains first; a render on the computing stream is ordered by the stream itself
             if (ctx->beam_key.valid && (s != ctx->beam_stream || ctx->beam_shared)) HIP_TRY(ctx, hipDeviceSynchronize());
             ctx->beam_key.valid = false;
-            HIP_TRY(ctx, launch_beam(ctx->S, ctx->C, R, ctx->d_beam.p, s));
+            HIP_TRY(ctx, launch_beam(ctx->S, C, R, ctx->d_beam.p, s));
             HIP_TRY(ctx, hipEventRecord(ctx->beam_ev, s));
             ctx->beam_key = key;
             ctx->beam_stream = s;
@@ -1004,7 +1014,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         if (std::getenv("OCTPT_DEBUG"))  // (tests/test_gpu_sample_group.py and test_gpu_group_refill.py read this line)
             std::fprintf(stderr, "octpt: chunk of %u samples, sample group %u, first-launch refill %u\n", Rc.spp_count,
                          1u << Rc.group_shift, refill_first);
-        HIP_TRY(ctx, launch_wf_seed(ctx->C, Rc, B, n_seed, chunk_items, ctx->d_stats, s));
+        HIP_TRY(ctx, launch_wf_seed(C, Rc, B, n_seed, chunk_items, ctx->d_stats, s));
         for (uint32_t it = 0;; ++it) {
             if (cancel && cancel->load()) return fail(ctx, OCTPT_CANCELLED, "render cancelled");
             const uint32_t q = it & 1u;
@@ -1015,7 +1025,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                                           ctx->d_stats, s));
             if ((st = ktimer_end(ctx, s, 0, ev)) != OCTPT_OK) return st;
             if ((st = ktimer_begin(ctx, s, ev)) != OCTPT_OK) return st;
-            HIP_TRY(ctx, launch_wf_shade(Se, ctx->C, Rc, B, q, chunk_items, it == 0u ? (cam_rec ? 2u : 1u) : 0u,
+            HIP_TRY(ctx, launch_wf_shade(Se, C, Rc, B, q, chunk_items, it == 0u ? (cam_rec ? 2u : 1u) : 0u,
                                          regen, grid_shade, ctx->d_stats, s, emit));
             if ((st = ktimer_end(ctx, s, 1, ev)) != OCTPT_OK) return st;
             // snapshot of the queue iteration `it` produced; the host checks the snapshot of
@@ -1072,7 +1082,7 @@ octpt_status octpt::enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d
     HIP_TRY(ctx, hipEventRecord(ev.start, s));
     octpt_status st = OCTPT_OK;
     if (R.preview) {
-        const hipError_t e = launch_preview(ctx->S, ctx->C, R, d_accum, d_seg, ctx->d_stats, s);
+        const hipError_t e = launch_preview(ctx->S, ray_source_camera(ctx), R, d_accum, d_seg, ctx->d_stats, s);
         if (e != hipSuccess) st = hip_fail(ctx, e, "preview launch");
     } else {
         st = megakernel ? enqueue_megakernel(ctx, R, d_accum, d_seg, s)
@@ -1752,6 +1762,8 @@ octpt_status octpt_set_camera(octpt_ctx *ctx, const octpt_camera *c) {
                     "aperture must be finite and >= 0, and focal_distance finite and > 0 when aperture > 0");
     if (c->aperture > 0.0f && ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "an aperture needs the pinhole projection (octpt_set_projection)");
+    if (c->aperture > 0.0f && ctx->rays.d_rays)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "an aperture while a ray source is set (octpt_set_ray_source)");
     ctx->cam = *c;
     DevCamera C{};
     std::memcpy(C.eye, c->eye, 12);
@@ -1787,6 +1799,8 @@ octpt_status octpt_set_projection(octpt_ctx *ctx, const octpt_projection *p) {
                     "projection param must be finite and > 0, and an angle at most 2 pi");
     if (p->mode != OCTPT_PROJECTION_PINHOLE && ctx->has_camera && ctx->cam.aperture > 0.0f)
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a projection other than pinhole needs a camera without an aperture");
+    if (p->mode != OCTPT_PROJECTION_PINHOLE && ctx->rays.d_rays)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a projection other than pinhole while a ray source is set (octpt_set_ray_source)");
     // (the pinhole's param is not read: every pinhole setting is one state)
     const float param = p->mode == OCTPT_PROJECTION_PINHOLE ? 0.0f : p->param;
     // the setting the context (and with it every entry) already holds: nothing changes, the beam table stays valid
@@ -1808,6 +1822,41 @@ octpt_status octpt_set_projection(octpt_ctx *ctx, const octpt_projection *p) {
 octpt_status octpt_get_projection(const octpt_ctx *ctx, octpt_projection *p) {
     if (!ctx || !p) return OCTPT_ERR_INVALID_ARG;
     *p = ctx->proj;
+    return OCTPT_OK;
+}
+
+// The ray source (C41): the context keeps the caller's pointer and the list's shape; ray_source_camera hands them to the
+// kernels of every later render.  Every check comes before the first write.
+octpt_status octpt_set_ray_source(octpt_ctx *ctx, const octpt_ray_source *r) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!r || !r->d_rays) {  // clear: every later render is the context's own camera's
+        if (!ctx->rays.d_rays) return OCTPT_OK;
+        join_inflight(ctx);  // a frame in flight reads the list
+        ctx->rays = octpt_ray_source{};
+        return OCTPT_OK;
+    }
+    for (uint32_t w : r->reserved)
+        if (w != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "ray source: a reserved word is not zero");
+    if (r->rays_per_pixel == 0u || r->width == 0u || r->height == 0u)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "ray source: width, height and rays_per_pixel must be >= 1");
+    // (three factors below 2^32: the product of two fits 64 bits, and the third is compared by division)
+    const uint64_t px = (uint64_t)r->width * r->height;
+    if (px > kRayListMaxRays || r->rays_per_pixel > kRayListMaxRays / px)
+        return fail(ctx, OCTPT_ERR_INVALID_ARG, "ray source: more than 2^28 rays");
+    if (is_multi(ctx))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a ray source lives on one device: not on a multi-device context");
+    if (ctx->has_camera && ctx->cam.aperture > 0.0f)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a ray source needs a camera without an aperture");
+    if (ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a ray source needs the pinhole projection (octpt_set_projection)");
+    join_inflight(ctx);  // a frame in flight reads the earlier setting
+    ctx->rays = *r;
+    return OCTPT_OK;
+}
+
+octpt_status octpt_get_ray_source(const octpt_ctx *ctx, octpt_ray_source *r) {
+    if (!ctx || !r) return OCTPT_ERR_INVALID_ARG;
+    *r = ctx->rays;
     return OCTPT_OK;
 }
 

@@ -76,6 +76,9 @@ struct octpt_ctx {
     octpt::DevCamera C{};
     // the projection (C40, octpt_set_projection): PINHOLE in a new context; ctx->C carries its mode and half-param
     octpt_projection proj{};
+    // the ray source (C41, octpt_set_ray_source): d_rays NULL = none.  The caller's buffer; ctx->C never carries it
+    // (ray_source_camera below forms the camera a render passes to its kernels)
+    octpt_ray_source rays{};
     // per-context device state
     uint32_t *d_counters = nullptr;  // ring of work counters, one per launch
     // branch schedule of the current render (C20): host copy + grow-only device table
@@ -278,6 +281,14 @@ inline bool is_multi(const octpt_ctx *ctx) { return !ctx->sub.empty(); }
 
 // the 8x8 tiles of a W x H frame
 inline uint32_t frame_tiles(uint32_t W, uint32_t H) { return ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile); }
+
+// the camera a render passes to its kernels: the context's, and under a ray source (C41) that camera carrying the
+// list in the fields the ray-list instances do not read (set_cam_ray_list, octpt_internal.h)
+inline DevCamera ray_source_camera(const octpt_ctx *ctx) {
+    DevCamera C = ctx->C;
+    if (ctx->rays.d_rays) set_cam_ray_list(C, ctx->rays.d_rays, ctx->rays.rays_per_pixel);
+    return C;
+}
 
 // the pixels of a render's accumulation buffer
 inline size_t accum_pixels(const DevRender &R) { return R.compact ? (size_t)R.total_items : (size_t)R.W * R.H; }

@@ -270,6 +270,37 @@ extern "C" octpt_status octpt_projection_rays(const octpt_camera *camera, const 
     return OCTPT_OK;
 }
 
+// The first ray under a ray source for chosen samples: csrc/octpt_lens.h's ray_list_ray, the text the
+// ray-list kernel instances compile, over a host copy of the list.  Every check comes before the first write.
+extern "C" octpt_status octpt_ray_source_rays(const octpt_camera *fallback, const float *rays, uint32_t width,
+                                              uint32_t height, uint32_t rays_per_pixel, uint32_t seed, const uint32_t *xys,
+                                              uint32_t n, float *out_rays, uint32_t *rng_state) {
+    if (!fallback || !rays || !out_rays || (n != 0u && !xys)) return OCTPT_ERR_INVALID_ARG;
+    if (width == 0u || height == 0u || rays_per_pixel == 0u) return OCTPT_ERR_INVALID_ARG;
+    const uint64_t px = (uint64_t)width * height;
+    if (px > octpt::kRayListMaxRays || rays_per_pixel > octpt::kRayListMaxRays / px) return OCTPT_ERR_INVALID_ARG;
+    if (!(fallback->fov > 0.0f && fallback->fov < 3.14159265f)) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::lens_fields_valid(fallback->aperture, fallback->focal_distance)) return OCTPT_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (xys[3u * i] >= width || xys[3u * i + 1u] >= height) return OCTPT_ERR_INVALID_ARG;
+    const octpt::LensCamera L = octpt::lens_camera(fallback->eye, fallback->direction, fallback->up, fallback->fov,
+                                                   fallback->aperture, fallback->focal_distance);
+    octpt::LensFrame F;
+    F.W = width;
+    F.H = height;
+    F.seed = seed;
+    F.dim = (float)(width > height ? width : height);  // make_render's dim, jlo and jhi (not read by this form)
+    F.jlo = -1.0f / F.dim;
+    F.jhi = 1.0f / F.dim;
+    for (uint32_t i = 0; i < n; ++i) {
+        float *o = out_rays + 6u * (size_t)i;
+        const uint32_t st = octpt::ray_list_ray<true>(L, F, rays, rays_per_pixel, xys[3u * i], xys[3u * i + 1u],
+                                                      xys[3u * i + 2u], o, o + 3);
+        if (rng_state) rng_state[i] = st;
+    }
+    return OCTPT_OK;
+}
+
 // The mapping of DESIGN.md C26 alone: csrc/octpt_reproject.h's reproject_pixel, the text temporal_kernel compiles,
 // over the whole frame.
 extern "C" octpt_status octpt_reproject_coords(const octpt_camera *camera, const octpt_camera *prev_camera, uint32_t width,

@@ -142,6 +142,30 @@ struct DevCamera {
 };
 static_assert(sizeof(DevCamera) == 64, "DevCamera fills the 64 bytes it always took as a kernel argument");
 
+// The ray-list camera (octpt_set_ray_source), read by the ray-list instances alone
+// (octpt_kernels_rays.hip).  That form reads eye and dir (its fallback ray) and none of right, up, d_factor, aperture
+// and the union, so the camera a render under a ray source passes to its kernels (ray_source_camera, octpt_ctx.h)
+// carries the list in `right` -- the buffer's address as the bit patterns of right[0..1], rays per pixel as that of
+// right[2] -- and marks itself with a proj_mode no public mode has, which is what the launchers pick the instances by.
+// The struct and every kernel's argument block stay as they are.
+constexpr uint32_t kProjModeRays = 0x80000000u;
+inline void set_cam_ray_list(DevCamera &C, const float *d_rays, uint32_t rpp) {
+    const uint64_t a = reinterpret_cast<uint64_t>(d_rays);
+    __builtin_memcpy(C.right, &a, 8);
+    __builtin_memcpy(C.right + 2, &rpp, 4);
+    C.proj_mode = kProjModeRays;
+}
+__host__ __device__ inline const float *cam_ray_list(const DevCamera &C) {
+    uint64_t a;
+    __builtin_memcpy(&a, C.right, 8);
+    return reinterpret_cast<const float *>(a);
+}
+__host__ __device__ inline uint32_t cam_ray_list_rpp(const DevCamera &C) {
+    uint32_t r;
+    __builtin_memcpy(&r, C.right + 2, 4);
+    return r;
+}
+
 // n / d for a divisor d fixed per launch (Lemire, Kaser & Kurz 2019, "Faster remainder by direct computation"):
 // with c = ceil(2^64 / d), floor(c * n / 2^64) = floor(n / d) for every 32-bit n and 2 <= d < 2^32; c = 0 marks d = 1.
 // Two integer multiplies instead of the ~25-instruction runtime division (item -> pixel maps of seed, shade, resolve).
@@ -373,6 +397,13 @@ const void *proj_shade_kernel(bool nee, bool lds, int mode);
 const void *proj_preview_kernel(int prims);
 const void *proj_gbuffer_kernel(int prims);
 const void *proj_emit_shade_kernel(bool nee, bool lds, int mode);
+// the ray-list instances (C41; octpt_kernels_rays.hip and octpt_kernels_rays_emit.hip, modules of their own), taken
+// for a camera that carries a ray list (kProjModeRays): the same without the megakernel's
+const void *rays_seed_kernel();
+const void *rays_shade_kernel(bool nee, bool lds, int mode);
+const void *rays_preview_kernel(int prims);
+const void *rays_gbuffer_kernel(int prims);
+const void *rays_emit_shade_kernel(bool nee, bool lds, int mode);
 hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t n_seed,
                           uint32_t chunk_items, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q, bool cam, uint32_t refill, int grid,

@@ -1402,13 +1402,25 @@ __device__ inline v3 random_sun_direction(const DevSun &K, uint32_t &rng) {
 // camera ray + fresh path (camera.rs:77-86, tile_renderer.rs:695-703; lens_ray).  kCam, the form of
 // the camera the instance is compiled for: kCamPinhole; kCamLens, the camera has an aperture and the ray leaves its
 // point of the lens (C37); kCamProj, a parallel, fisheye or panoramic projection (projection_ray, C40), the mode a
-// field of the camera, uniform over the launch.  An instance reads only its own form's fields.
-constexpr int kCamPinhole = 0, kCamLens = 1, kCamProj = 2;
+// field of the camera, uniform over the launch; kCamRays, the ray-list camera (ray_list_ray, C41), whose ray is the
+// caller's record for the sample, read with plain global loads: the lanes of a wave that holds one pixel's consecutive
+// samples read consecutive 24-byte records, 1536 contiguous bytes over the six loads.  An instance reads only its own
+// form's fields.
+constexpr int kCamPinhole = 0, kCamLens = 1, kCamProj = 2, kCamRays = 3;
+// The preview and the guide-buffer kernel know two forms per module, the pinhole and (kProj) this one: the ray-list
+// camera in its module (octpt_kernels_rays.hip, OCTPT_RAYS_TU), the projections everywhere else.  A constant of the
+// module and no third template argument, so that every existing instance keeps its name and its code.
+#if defined(OCTPT_RAYS_TU)
+constexpr int kCamCentre = kCamRays;
+#else
+constexpr int kCamCentre = kCamProj;
+#endif
 template <int kCam = kCamPinhole>
 __device__ inline void new_path(const DevCamera &C, const DevRender &R, uint32_t x, uint32_t y, uint32_t sample,
                                 PathState &ps) {
     float o[3], d[3];
-    if constexpr (kCam == kCamProj) ps.rng = projection_ray<true>(C, R, x, y, sample, o, d);
+    if constexpr (kCam == kCamRays) ps.rng = ray_list_ray<true>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, sample, o, d);
+    else if constexpr (kCam == kCamProj) ps.rng = projection_ray<true>(C, R, x, y, sample, o, d);
     else ps.rng = lens_ray<kCam == kCamLens>(C, R, x, y, sample, o, d);
     ps.o = V(o[0], o[1], o[2]);
     ps.d = V(d[0], d[1], d[2]);
@@ -1894,7 +1906,8 @@ __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C,
 // one wave per SIMD above the natural allocation (78 / 86 / 102 VGPRs -> 72 / 80 / 96), as for extend
 #define OCTPT_PREVIEW_WAVES_OF(k) \
     (OCTPT_PREVIEW_BOUNDS ? ((k) == kPrimsSpheres ? 7 : ((k) == kPrimsBoxes || (k) == kPrimsBlocks) ? 6 : 5) : 1)
-// kProj (C40): the un-jittered ray of the camera's projection (projection_ray<false>) in place of get_ray's
+// kProj: the un-jittered ray of the module's camera form (kCamCentre) in place of get_ray's -- the camera's projection
+// (projection_ray<false>, C40), or ray 0 of the pixel in the caller's list (ray_list_ray<false>, C41)
 template <int kPrims, bool kProj = false>
 __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void preview_kernel(DevScene S, DevCamera C, DevRender R,
                                                          float4 *__restrict__ accum, uint32_t *__restrict__ segcount,
@@ -1918,7 +1931,8 @@ __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void previe
         ps.d = vnorm(nd);
         if constexpr (kProj) {
             float po[3], pd[3];
-            (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
+            if constexpr (kCamCentre == kCamRays) (void)ray_list_ray<false>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, 0u, po, pd);
+            else (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
             ps.o = V(po[0], po[1], po[2]);
             ps.d = V(pd[0], pd[1], pd[2]);
         }
@@ -3201,7 +3215,8 @@ __global__ void multi_stage_kernel(DevRender R, uint32_t n_dev, uint32_t stride,
 // the natural allocation)
 #define OCTPT_GBUFFER_WAVES_OF(k) \
     (OCTPT_GBUFFER_BOUNDS ? ((k) == kPrimsSpheres ? 7 : ((k) == kPrimsBoxes || (k) == kPrimsBlocks) ? 6 : 5) : 1)
-// kProj (C40): the preview's projected ray
+// kProj: the preview's ray of the module's camera form (kCamCentre): projected (C40), or ray 0 of the pixel in the
+// caller's list (C41), the distance then that from the ray's own origin
 template <int kPrims, bool kProj = false>
 __global__ __launch_bounds__(kBlock, OCTPT_GBUFFER_WAVES_OF(kPrims)) void gbuffer_kernel(DevScene S, DevCamera C, DevRender R,
                                                                                          DevAov out,
@@ -3224,7 +3239,8 @@ __global__ __launch_bounds__(kBlock, OCTPT_GBUFFER_WAVES_OF(kPrims)) void gbuffe
         ps.d = vnorm(nd);
         if constexpr (kProj) {
             float po[3], pd[3];
-            (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
+            if constexpr (kCamCentre == kCamRays) (void)ray_list_ray<false>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, 0u, po, pd);
+            else (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
             ps.o = V(po[0], po[1], po[2]);
             ps.d = V(pd[0], pd[1], pd[2]);
         }
@@ -3738,7 +3754,45 @@ __global__ __launch_bounds__(256) void atrous_var_kernel(DevDenoiseVar D, uint32
 
 }  // namespace
 
-#if defined(OCTPT_PROJ_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_proj_emit.hip alone: not a build switch)
+#if defined(OCTPT_RAYS_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_rays_emit.hip alone: not a build switch)
+// The emitter instances (C38) of the general shade for the ray-list camera (C41), a module of their own like every
+// other family.
+template <bool kNee, bool kLds>
+static const void *rays_emit_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamRays>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamRays>);
+}
+const void *rays_emit_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? rays_emit_shade_of<true, true>(mode) : rays_emit_shade_of<true, false>(mode))
+               : (lds ? rays_emit_shade_of<false, true>(mode) : rays_emit_shade_of<false, false>(mode));
+}
+#elif defined(OCTPT_RAYS_TU)  // (set by octpt_kernels_rays.hip alone: not a build switch)
+// The ray-list instances (C41) of the seed, the general shade, the preview and the guide-buffer kernel, for
+// octpt_kernels_rays.hip, which compiles this text for them alone (a module of their own, as the lens and the projected
+// instances below are, and for their reason).  No megakernel instance: such a render is refused.
+const void *rays_seed_kernel() { return reinterpret_cast<const void *>(wf_seed_kernel<kCamRays>); }
+template <bool kNee, bool kLds>
+static const void *rays_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamRays>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamRays>);
+}
+const void *rays_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? rays_shade_of<true, true>(mode) : rays_shade_of<true, false>(mode))
+               : (lds ? rays_shade_of<false, true>(mode) : rays_shade_of<false, false>(mode));
+}
+const void *rays_preview_kernel(int prims) {
+    return prims == kPrimsBlocks   ? reinterpret_cast<const void *>(preview_kernel<kPrimsBlocks, true>)
+           : prims == kPrimsModels ? reinterpret_cast<const void *>(preview_kernel<kPrimsModels, true>)
+           : prims == kPrimsBoxes  ? reinterpret_cast<const void *>(preview_kernel<kPrimsBoxes, true>)
+                                   : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres, true>);
+}
+const void *rays_gbuffer_kernel(int prims) {
+    return prims == kPrimsBlocks   ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBlocks, true>)
+           : prims == kPrimsModels ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsModels, true>)
+           : prims == kPrimsBoxes  ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBoxes, true>)
+                                   : reinterpret_cast<const void *>(gbuffer_kernel<kPrimsSpheres, true>);
+}
+#elif defined(OCTPT_PROJ_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_proj_emit.hip alone: not a build switch)
 // The emitter instances (C38) of the general shade for a projected camera (C40), a module of their own like every
 // other family, so that octpt_kernels_emit.hip's instances stay the code they are.
 template <bool kNee, bool kLds>
@@ -3869,6 +3923,7 @@ hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRende
                      : S.has_cuboids ? reinterpret_cast<const void *>(preview_kernel<kPrimsBoxes>)
                                      : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres>);
     if (C.proj_mode != 0u) fn = proj_preview_kernel(scene_prims(S));  // the projected instance (C40)
+    if (C.proj_mode == kProjModeRays) fn = rays_preview_kernel(scene_prims(S));  // the ray-list instance (C41)
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), &accum,
                     &segcount, &stats};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args,
@@ -3886,6 +3941,7 @@ hipError_t launch_gbuffer(const DevScene &S, const DevCamera &C, const DevRender
                      : S.has_cuboids ? reinterpret_cast<const void *>(gbuffer_kernel<kPrimsBoxes>)
                                      : reinterpret_cast<const void *>(gbuffer_kernel<kPrimsSpheres>);
     if (C.proj_mode != 0u) fn = proj_gbuffer_kernel(scene_prims(S));  // the projected instance (C40)
+    if (C.proj_mode == kProjModeRays) fn = rays_gbuffer_kernel(scene_prims(S));  // the ray-list instance (C41)
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
                     const_cast<DevAov *>(&out), &stats};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, render_lds_bytes(S.depth), stream);
@@ -3965,8 +4021,10 @@ hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuff
     if (C.aperture > 0.0f || C.proj_mode != 0u) {  // the lens instance (C37) or the projected one (C40)
         void *args[] = {const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), const_cast<WaveBuffers *>(&B), &n_seed,
                         &chunk_items, &stats};
-        const hipError_t e = hipLaunchKernel(C.proj_mode != 0u ? proj_seed_kernel() : lens_seed_kernel(), grid,
-                                             dim3(kBlock), args, 0, stream);
+        const void *fn = C.proj_mode == kProjModeRays ? rays_seed_kernel()  // the ray-list instance (C41)
+                         : C.proj_mode != 0u          ? proj_seed_kernel()
+                                                      : lens_seed_kernel();
+        const hipError_t e = hipLaunchKernel(fn, grid, dim3(kBlock), args, 0, stream);
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
@@ -4013,10 +4071,12 @@ static const void *shade_instance(const DevScene &S, int mode, bool first = fals
     const bool lds = shade_lds_tables(S);
     // emitter sampling (C38): the general instances' emitter twins (such chunks never take the lean state)
     if (emit)
-        return cam == kCamProj ? proj_emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode)
-                               : emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode, cam == kCamLens);
-    // a lens camera (C37) or a projection (C40): the general instances' twins (enqueue_wavefront keeps such chunks
-    // off the lean state)
+        return cam == kCamRays   ? rays_emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode)
+               : cam == kCamProj ? proj_emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode)
+                                 : emit_shade_kernel(S.sun.sun_sampling != 0, lds, mode, cam == kCamLens);
+    // a lens camera (C37), a projection (C40) or a ray list (C41): the general instances' twins (enqueue_wavefront
+    // keeps such chunks off the lean state)
+    if (cam == kCamRays) return rays_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
     if (cam == kCamProj) return proj_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
     if (cam == kCamLens) return lens_shade_kernel(S.sun.sun_sampling != 0, lds, mode);
     const int prims = S.has_blocks    ? kPrimsBlocks
@@ -4042,7 +4102,10 @@ hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRende
     uint32_t first_u = first;
     void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
                     const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
-    const int cam = C.proj_mode != 0u ? kCamProj : C.aperture > 0.0f ? kCamLens : kCamPinhole;
+    const int cam = C.proj_mode == kProjModeRays ? kCamRays
+                    : C.proj_mode != 0u          ? kCamProj
+                    : C.aperture > 0.0f          ? kCamLens
+                                                 : kCamPinhole;
     const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, cam, emit),
                                          dim3(grid), dim3(kBlock), args, 0, stream);
     if (e != hipSuccess) return e;

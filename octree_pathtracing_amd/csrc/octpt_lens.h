@@ -215,4 +215,44 @@ OCTPT_LENS_FN uint32_t projection_ray(const Cam &C, const Frame &R, uint32_t x, 
     return st;
 }
 
+// ---------------------------------------------------------------------------
+// the ray-list camera: the first ray of every sample read from a buffer the caller fills
+// ---------------------------------------------------------------------------
+constexpr uint64_t kRayListMaxRays = 1ull << 28;  // width * height * rays_per_pixel at most (octpt_set_ray_source)
+constexpr float kRayListUnitBand = 1e-4f;         // a direction's squared length lies within this of 1
+
+// where the ray of sample `sample` of pixel (x, y) starts in the list, in floats: 64-bit, R records per pixel in
+// image order, the samples beyond R wrapping round (sample is absolute, spp_start included)
+OCTPT_LENS_FN uint64_t ray_list_index(uint32_t W, uint32_t x, uint32_t y, uint32_t rpp, uint32_t sample) {
+    return 6ull * ((uint64_t)(y * W + x) * rpp + sample % rpp);
+}
+
+// The first ray of a ray-list camera: the six floats of the list as given (origin, direction; not renormalised).  An
+// invalid record -- a non-finite float, or a direction whose squared length is not within kRayListUnitBand of 1: the
+// negated <= is true for NaN, zero and infinite directions as well -- is replaced whole by the camera's central ray
+// (eye, dir), so that no bit pattern in the buffer makes anything but an ordinary path.  st0 and the two jitter draws
+// are lens_ray's (drawn and discarded): the returned state is lens_ray's, so a path's later draws are what they are
+// under every other camera.  kJitter false: ray 0 of the pixel for the preview and the guide buffers (no draw; st0).
+template <bool kJitter, class Cam, class Frame>
+OCTPT_LENS_FN uint32_t ray_list_ray(const Cam &C, const Frame &R, const float *rays, uint32_t rpp, uint32_t x, uint32_t y,
+                                    uint32_t sample, float o[3], float d[3]) {
+    const uint32_t st0 = path_state(R.seed, y * R.W + x, sample);
+    uint32_t st = st0;
+    if (kJitter) {
+        (void)rng_next(st);
+        (void)rng_next(st);
+    }
+    const float *r = rays + ray_list_index(R.W, x, y, rpp, kJitter ? sample : 0u);
+    float v[6];
+    for (int i = 0; i < 6; ++i) v[i] = r[i];
+    const float len2 = (v[3] * v[3] + v[4] * v[4]) + v[5] * v[5];  // (a non-finite direction makes this inf or NaN)
+    bool bad = !(fabsf(len2 - 1.0f) <= kRayListUnitBand);
+    for (int i = 0; i < 3; ++i) bad = bad || !(fabsf(v[i]) < INFINITY);
+    for (int i = 0; i < 3; ++i) {
+        o[i] = bad ? C.eye[i] : v[i];
+        d[i] = bad ? C.dir[i] : v[3 + i];
+    }
+    return st;
+}
+
 }  // namespace octpt

@@ -52,7 +52,7 @@ octpt_status enqueue_aov(octpt_ctx *ctx, const DevRender &R, const octpt_aov_buf
     HIP_TRY(ctx, hipEventRecord(ev.start, s));
     const DevAov out{reinterpret_cast<float4 *>(dev.albedo), reinterpret_cast<float4 *>(dev.normal), dev.depth, dev.prim,
                      dev.material};
-    const hipError_t e = launch_gbuffer(ctx->S, ctx->C, R, out, ctx->d_stats, s);
+    const hipError_t e = launch_gbuffer(ctx->S, ray_source_camera(ctx), R, out, ctx->d_stats, s);
     HIP_TRY(ctx, hipEventRecord(ev.stop, s));
     if (e != hipSuccess) return hip_fail(ctx, e, "guide buffer launch");
     ctx->launches++;
@@ -190,6 +190,9 @@ octpt_status check_temporal(octpt_ctx *ctx, const char *who, bool moments, const
     // the mapping is the pinhole camera's: a context whose renders are projected otherwise has no history to carry (C40)
     if (ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + "the context's projection is not pinhole (octpt_set_projection)");
+    // ... nor has one whose first rays are the caller's (C41)
+    if (ctx->rays.d_rays)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, w + "the context has a ray source (octpt_set_ray_source)");
     if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, std::string(who) + " params NULL");
     if (p->width == 0 || p->height == 0) return fail(ctx, OCTPT_ERR_INVALID_ARG, w + "zero frame size");
     if ((uint64_t)p->width * p->height >= (1ull << 31) || p->height > 8u * 65535u)
@@ -358,6 +361,8 @@ octpt_status octpt_reproject_coords_ctx(octpt_ctx *ctx, const octpt_camera *came
     if (!ctx) return OCTPT_ERR_INVALID_ARG;
     if (ctx->proj.mode != OCTPT_PROJECTION_PINHOLE)
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "reproject_coords: the context's projection is not pinhole (octpt_set_projection)");
+    if (ctx->rays.d_rays)
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "reproject_coords: the context has a ray source (octpt_set_ray_source)");
     const octpt_status st = octpt_reproject_coords(camera, prev_camera, width, height, depth, prev_xy, prev_depth);
     return st == OCTPT_OK ? st : fail(ctx, st, "reproject_coords: refused (octpt_reproject_coords' rules)");
 }

@@ -119,6 +119,7 @@ class HipRenderer:
         self._accum = None
         self._spp = 0
         self._in_flight = None
+        self._ray_source = None  # (the tensor set_ray_source keeps alive, (H, W, R)) while a ray source is set
         self.set_camera(self._camera)
 
     # ------------------------------------------------------------ lifecycle
@@ -185,6 +186,46 @@ class HipRenderer:
         p = _lib.Projection()
         self._check(self._lib.octpt_get_projection(self._ctx, C.byref(p)))
         return int(p.mode), float(p.param)
+
+    def set_ray_source(self, rays, rays_per_pixel: int | None = None) -> None:
+        """octpt_set_ray_source: every later render of this renderer takes the first ray of sample s
+        of pixel (x, y) from rays[y, x, s % R] = (origin xyz, direction xyz), a unit direction used as given; an
+        invalid record (non-finite, or not of unit length) renders as the camera's central ray.  `rays`: a float32
+        torch tensor on this renderer's device or a numpy array (uploaded), of shape (H, W, R, 6); the renderer holds
+        it until clear_ray_source or the next set_ray_source, and it must not be written while renders read it.
+        Renders must then be H x W; the preview and the guide buffers trace rays[y, x, 0]."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        t = torch.from_numpy(np.ascontiguousarray(rays, np.float32)).to(dev) if isinstance(rays, np.ndarray) else rays
+        if t.dim() != 4 or t.shape[3] != 6:
+            raise ValueError(f"rays has shape {tuple(t.shape)}, not (H, W, R, 6)")
+        if rays_per_pixel is not None and int(rays_per_pixel) != t.shape[2]:
+            raise ValueError(f"rays holds {t.shape[2]} rays per pixel, not {rays_per_pixel}")
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"rays must be a contiguous float32 tensor on {dev}")
+        H, W, R = (int(v) for v in t.shape[:3])
+        src = _lib.RaySource(t.data_ptr(), W, H, R)
+        self._check(self._lib.octpt_set_ray_source(self._ctx, C.byref(src)))
+        self._ray_source = (t, (H, W, R))
+        self.reset_render()
+
+    def clear_ray_source(self) -> None:
+        """Back to the renderer's own camera: renders are bit for bit those of a renderer that never had a source."""
+        self._check(self._lib.octpt_set_ray_source(self._ctx, None))
+        self._ray_source = None
+        self.reset_render()
+
+    def get_ray_source(self):
+        """octpt_get_ray_source: (device pointer or None, width, height, rays_per_pixel)."""
+        src = _lib.RaySource()
+        self._check(self._lib.octpt_get_ray_source(self._ctx, C.byref(src)))
+        return src.d_rays, int(src.width), int(src.height), int(src.rays_per_pixel)
+
+    def ray_source_rays(self, rays: np.ndarray, seed: int, xys):
+        """octpt_ray_source_rays with this renderer's camera as the fallback: for rows (x, y, sample) the first rays
+        [n, 6] a render under the list `rays` (H, W, R, 6) traces, bit for bit, and the paths' RNG states [n]."""
+        return ray_source_rays(self._camera, rays, seed, xys)
 
     def which_backend(self) -> str:
         return "HIP (gfx950)"
@@ -919,6 +960,25 @@ def projection_rays(camera: Camera, W: int, H: int, seed: int, xys, centre: bool
     if st != 0:
         raise _lib.OctptError(st, "octpt_projection_rays")
     return rays, state
+
+
+def ray_source_rays(fallback: Camera, rays: np.ndarray, seed: int, xys):
+    """octpt_ray_source_rays: for rows (x, y, sample) of `xys` the first rays [n, 6] f32 that a render under the ray
+    list `rays` (H, W, R, 6) traces -- the record as given, or `fallback`'s central ray where it is invalid -- and the
+    paths' RNG states after them [n] u32 (host-only, no context)."""
+    rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim != 4 or rays.shape[3] != 6:
+        raise ValueError(f"rays has shape {rays.shape}, not (H, W, R, 6)")
+    H, W, R = rays.shape[:3]
+    xys = np.ascontiguousarray(xys, np.uint32).reshape(-1, 3)
+    out = np.zeros((len(xys), 6), np.float32)
+    state = np.zeros(len(xys), np.uint32)
+    st = _lib.load().octpt_ray_source_rays(C.byref(_c_camera(fallback, lens=True)), rays.ctypes.data_as(C.c_void_p), W, H,
+                                           R, seed, xys.ctypes.data_as(C.c_void_p), len(xys),
+                                           out.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p))
+    if st != 0:
+        raise _lib.OctptError(st, "octpt_ray_source_rays")
+    return out, state
 
 
 def _c_camera(camera: Camera, lens: bool = False) -> "_lib.Camera":
