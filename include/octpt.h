@@ -367,6 +367,65 @@ typedef struct octpt_ray_source {
 octpt_status octpt_set_ray_source(octpt_ctx *ctx, const octpt_ray_source *source);
 octpt_status octpt_get_ray_source(const octpt_ctx *ctx, octpt_ray_source *source);
 
+/* The sky: the base colour a ray that leaves the world adds, at every depth, in the drain and in the
+ * preview, where every render used to add the constant (0.5, 0.7, 1.0).  The sun's texture, its diffuse term and
+ * next-event estimation are untouched and add on top.  A sky changes no random draw: a path's geometry is the same
+ * under every sky.  For a unit direction d in world axes, +y up (one text, csrc/octpt_sky.h, compiled by the kernels
+ * and by octpt_sky_radiance):
+ *   DEFAULT   (0.5, 0.7, 1.0), the state of a new context; no other field is read
+ *   COLOR     color * scale
+ *   GRADIENT  (horizon + (zenith - horizon) * max(d.y, 0)) * scale: horizon * scale below the horizon
+ *   MAP       an equirectangular map of width x height texels of four floats each (RGBA; alpha is not read), row 0 the
+ *             zenith: lon = atan2(d.z, d.x) + yaw, u = lon / 2pi + 0.5 wrapped into [0, 1), v = acos(d.y) / pi; bilinear
+ *             between the texels at floor and floor + 1 of (u * width - 0.5, v * height - 0.5), wrapped in x and clamped
+ *             in y, each lerp a + w * (b - a), then times scale.  +x is the map's centre column at yaw 0.  At the poles
+ *             the value is the top or bottom row's at the column of longitude `yaw`.
+ * The context copies a MAP's texels into a buffer of its own before the call returns (the caller may free its own), and
+ * sanitises them once: NaN and negative become 0, +inf becomes FLT_MAX; a lookup is held at FLT_MAX after the scale.
+ * color, horizon and zenith are used as given.  octpt_set_sky takes host texels, octpt_set_sky_device texels in memory
+ * of the context's device (copied on `hip_stream`, which the call drains); texels is read for MAP alone.
+ * octpt_clear_sky is DEFAULT again, and every render is then bit for bit that of a context that never had a sky.
+ * The call joins a frame in flight and the setting holds for every later render of the context: sync, device, async,
+ * tile-list, adaptive and final renders under every camera (pinhole, aperture, projection, ray source), with and without
+ * sun sampling and strategy ONE emitter sampling, and OCTPT_RENDER_PREVIEW.  The guide buffers (octpt_render_aov*)
+ * describe hits and write zeros and an infinite depth for a miss under every sky.  Under a sky other than DEFAULT a
+ * render takes the general path state (never the lean one) through the sky's own kernel instances.
+ * INVALID_ARG, the previous sky staying in force: an unknown mode, a non-zero reserved word, a scale that is NaN,
+ * negative or infinite, a yaw that is not finite, MAP with NULL texels, with width or height 0, or with width * height
+ * above 2^26.  UNSUPPORTED: a mode other than DEFAULT on a multi-device context (the setting stays DEFAULT), and a
+ * render with OCTPT_RENDER_MEGAKERNEL while the sky is not DEFAULT (the caller's buffers are not touched). */
+#define OCTPT_SKY_DEFAULT 0u /* the state of a new context */
+#define OCTPT_SKY_COLOR 1u
+#define OCTPT_SKY_GRADIENT 2u
+#define OCTPT_SKY_MAP 3u
+typedef struct octpt_sky {
+    uint32_t mode;
+    float color[3];   /* COLOR */
+    float horizon[3]; /* GRADIENT */
+    float zenith[3];  /* GRADIENT */
+    float scale;      /* every mode but DEFAULT */
+    float yaw;        /* MAP: radians added to the longitude */
+    uint32_t width, height; /* MAP */
+    uint32_t reserved[2];   /* 0 */
+} octpt_sky;
+octpt_status octpt_set_sky(octpt_ctx *ctx, const octpt_sky *sky, const float *texels);
+octpt_status octpt_set_sky_device(octpt_ctx *ctx, const octpt_sky *sky, const float *d_texels, void *hip_stream);
+octpt_status octpt_clear_sky(octpt_ctx *ctx);
+octpt_status octpt_get_sky(const octpt_ctx *ctx, octpt_sky *sky);
+/* The colour a render adds for n unit directions (dirs[3 * i], out[3 * i]; the sun's terms excluded).
+ * octpt_sky_radiance is host-only and knows no context: it runs csrc/octpt_sky.h on the CPU for `sky` and host texels
+ * (sanitised as octpt_set_sky sanitises them; octpt_set_sky's argument rules, every check before the first write).
+ * octpt_sky_radiance_device runs a kernel of the same text for the context's sky (device buffers, on `hip_stream`),
+ * octpt_sky_radiance_ctx is its host-pointer form.  The three agree bit for bit. */
+octpt_status octpt_sky_radiance(const octpt_sky *sky, const float *texels, const float *dirs, uint32_t n, float *out);
+octpt_status octpt_sky_radiance_device(octpt_ctx *ctx, const float *d_dirs, uint32_t n, float *d_out, void *hip_stream);
+octpt_status octpt_sky_radiance_ctx(octpt_ctx *ctx, const float *dirs, uint32_t n, float *out);
+/* DIAGNOSTIC, not part of the stable surface (it may change or go with the lookup's arithmetic; hosts have no use for
+ * it).  A MAP's lookup position alone: out_xy[2 * i] = (u * width - 0.5, v * height - 0.5) of direction i in f32, as the
+ * lookup forms it (mode MAP, width, height and yaw are read; no texels).  Host-only; what the error bound of the
+ * lookup against a float64 restatement is measured from. */
+octpt_status octpt_sky_map_position(const octpt_sky *sky, const float *dirs, uint32_t n, float *out_xy);
+
 /* Synchronous render into host memory.  accum_rgba: width*height*4 floats (or the shard's
  * compact tiles), in/out running mean, initialise to F32Color::BLACK (0,0,0,1).
  * out_rgba8 (nullable): tone-mapped U8Color image (colors/mod.rs:408-420) of accum. */

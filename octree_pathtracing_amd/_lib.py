@@ -227,6 +227,16 @@ class RaySource(C.Structure):
                 ("rays_per_pixel", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+SKY_DEFAULT, SKY_COLOR, SKY_GRADIENT, SKY_MAP = 0, 1, 2, 3  # OCTPT_SKY_* 
+
+
+class SkyDesc(C.Structure):
+    """octpt_sky (octpt_set_sky): the sky's mode and the fields it reads."""
+    _fields_ = [("mode", C.c_uint32), ("color", C.c_float * 3), ("horizon", C.c_float * 3), ("zenith", C.c_float * 3),
+                ("scale", C.c_float), ("yaw", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp_start", C.c_uint32), ("spp_count", C.c_uint32),
                 ("max_depth", C.c_uint32), ("branch_count", C.c_uint32), ("seed", C.c_uint32),
@@ -368,6 +378,14 @@ SIGNATURES = {
     "octpt_get_projection": (_i32, [_vp, C.POINTER(Projection)]),
     "octpt_set_ray_source": (_i32, [_vp, C.POINTER(RaySource)]),
     "octpt_get_ray_source": (_i32, [_vp, C.POINTER(RaySource)]),
+    "octpt_set_sky": (_i32, [_vp, C.POINTER(SkyDesc), _vp]),
+    "octpt_set_sky_device": (_i32, [_vp, C.POINTER(SkyDesc), _vp, _vp]),
+    "octpt_clear_sky": (_i32, [_vp]),
+    "octpt_get_sky": (_i32, [_vp, C.POINTER(SkyDesc)]),
+    "octpt_sky_radiance": (_i32, [C.POINTER(SkyDesc), _vp, _vp, _u32, _vp]),
+    "octpt_sky_radiance_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "octpt_sky_radiance_ctx": (_i32, [_vp, _vp, _u32, _vp]),
+    "octpt_sky_map_position": (_i32, [C.POINTER(SkyDesc), _vp, _u32, _vp]),
     "octpt_render": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp]),
     "octpt_render_device": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]),
     "octpt_render_async": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, C.POINTER(_vp)]),

@@ -540,6 +540,9 @@ octpt_status octpt::make_render(octpt_ctx *ctx, const octpt_render_params *p, De
         if ((p->flags & OCTPT_RENDER_MEGAKERNEL) && !(p->flags & OCTPT_RENDER_PREVIEW))
             return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a ray source is set: it runs on the wavefront path only");
     }
+    // a sky other than DEFAULT (C42) has wavefront instances only
+    if (ctx->sky.mode != kSkyDefault && (p->flags & OCTPT_RENDER_MEGAKERNEL) && !(p->flags & OCTPT_RENDER_PREVIEW))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a sky is set (octpt_set_sky): it runs on the wavefront path only");
     if (ctx->emit_strategy == OCTPT_EMITTERS_ONE && !(p->flags & OCTPT_RENDER_PREVIEW)) {  // C38
         const octpt_ctx *gc = ctx->sub.empty() ? ctx : ctx->sub[0];  // a multi-device context: its entries hold the scene
         if (!gc->S.has_blocks)
@@ -827,6 +830,10 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     // the ordinary ones
     const bool emit = ctx->emit_strategy == OCTPT_EMITTERS_ONE && ctx->grid_valid && ctx->emit_grid.n_emitters != 0u &&
                       ctx->S.emitters != 0 && ctx->S.has_blocks != 0u;
+    // the sky (C42) as set when the render call was made (octpt_set_sky joins a frame in flight): other than DEFAULT,
+    // shade and the drain are the sky instances and the chunks keep the general path state
+    const Sky sky_rec = ctx->sky;
+    const Sky *sky = sky_rec.mode != kSkyDefault ? &sky_rec : nullptr;
     DevScene Se = ctx->S;  // what shade and the drain take
     if (emit) {
         const DeviceEmitterGrid &g = ctx->emit_grid;
@@ -995,7 +1002,8 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
         // the lean 24-B path state: L stays 0 until the path ends, item = slot
         // (and no branch schedule: the lean shade instances carry no first-reflection split)
         // (nor a lens: its shade instances are the general ones' twins, C37)
-        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs && !lens && !emit) ? 1u : 0u;
+        // (nor a sky other than DEFAULT: its shade instances are the general ones' too, C42)
+        ctx->wb.lean = (!regen && ctx->lean_scene && !ctx->no_lean && !R.subs && !lens && !emit && !sky) ? 1u : 0u;
         const int grid_shade = grid_shade_of(shade_mode(regen, ctx->wb.lean != 0u));
         // the seed writes its camera rays as 16-B records (store_cam_ray) when every item has its pixel: the first
         // extend (cam) and shade (first = 2) decode them
@@ -1026,7 +1034,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             if ((st = ktimer_end(ctx, s, 0, ev)) != OCTPT_OK) return st;
             if ((st = ktimer_begin(ctx, s, ev)) != OCTPT_OK) return st;
             HIP_TRY(ctx, launch_wf_shade(Se, C, Rc, B, q, chunk_items, it == 0u ? (cam_rec ? 2u : 1u) : 0u,
-                                         regen, grid_shade, ctx->d_stats, s, emit));
+                                         regen, grid_shade, ctx->d_stats, s, emit, sky));
             if ((st = ktimer_end(ctx, s, 1, ev)) != OCTPT_OK) return st;
             // snapshot of the queue iteration `it` produced; the host checks the snapshot of
             // iteration it - kLookahead, so the GPU always has kLookahead iterations queued (an
@@ -1058,7 +1066,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                     if (exhausted) {
                         // one path per wave (wf_drain_kernel), four waves per block
                         const int grid = (int)std::min<uint64_t>((queued + 3) / 4 + 1, (uint64_t)ctx->num_cu * 16u);
-                        HIP_TRY(ctx, launch_wf_drain(Se, Rc, B, q ^ 1u, grid, ctx->d_stats, s, emit));
+                        HIP_TRY(ctx, launch_wf_drain(Se, Rc, B, q ^ 1u, grid, ctx->d_stats, s, emit, sky));
                         break;
                     }
                 }
@@ -1082,7 +1090,8 @@ octpt_status octpt::enqueue_render(octpt_ctx *ctx, const DevRender &R, float4 *d
     HIP_TRY(ctx, hipEventRecord(ev.start, s));
     octpt_status st = OCTPT_OK;
     if (R.preview) {
-        const hipError_t e = launch_preview(ctx->S, ray_source_camera(ctx), R, d_accum, d_seg, ctx->d_stats, s);
+        const hipError_t e = launch_preview(ctx->S, ray_source_camera(ctx), R, d_accum, d_seg, ctx->d_stats, s,
+                                            ctx->sky.mode != kSkyDefault ? &ctx->sky : nullptr);
         if (e != hipSuccess) st = hip_fail(ctx, e, "preview launch");
     } else {
         st = megakernel ? enqueue_megakernel(ctx, R, d_accum, d_seg, s)
@@ -1612,6 +1621,7 @@ void octpt_destroy(octpt_ctx *ctx) {
     free_scene(ctx);
     free_wave(ctx);
     if (ctx->d_emit_hdr) (void)hipFree(ctx->d_emit_hdr);
+    if (ctx->sky_map) (void)hipFree(ctx->sky_map);
     ctx->build_scratch.release();
     if (ctx->h_count) (void)hipHostFree(ctx->h_count);
     for (auto &ev : ctx->count_ev)
@@ -1858,6 +1868,133 @@ octpt_status octpt_get_ray_source(const octpt_ctx *ctx, octpt_ray_source *r) {
     if (!ctx || !r) return OCTPT_ERR_INVALID_ARG;
     *r = ctx->rays;
     return OCTPT_OK;
+}
+
+// The sky (C42).  Every check comes before the first write, so a refused call leaves the previous sky in force; a MAP is
+// copied into a buffer of the context's own and sanitised there (sky_sanitise), and the call returns with the copy made,
+// so the caller may free its texels.
+namespace {
+octpt_status check_sky(octpt_ctx *ctx, const octpt_sky *k, bool texels) {
+    if (!k) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky NULL");
+    for (uint32_t w : k->reserved)
+        if (w != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky: a reserved word is not zero");
+    if (!sky_mode_known(k->mode)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky: unknown mode");
+    if (!sky_fields_valid(k->mode, k->scale, k->yaw, k->width, k->height, texels))
+        return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                    "sky: scale must be finite and >= 0, yaw finite, and a MAP needs texels, width and height >= 1 and "
+                    "width * height <= 2^26");
+    if (k->mode != OCTPT_SKY_DEFAULT && is_multi(ctx))
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a sky other than DEFAULT: not on a multi-device context");
+    return OCTPT_OK;
+}
+}  // namespace
+
+octpt_status octpt_set_sky_device(octpt_ctx *ctx, const octpt_sky *k, const float *d_texels, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_sky(ctx, k, d_texels != nullptr);
+    if (st != OCTPT_OK) return st;
+    return guarded(ctx, "set_sky", [&]() -> octpt_status {
+        join_inflight(ctx);  // a frame in flight reads the earlier sky
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        Sky s{};
+        s.mode = k->mode;
+        float *map = nullptr;
+        if (k->mode != OCTPT_SKY_DEFAULT) {
+            std::memcpy(s.color, k->color, 12);
+            std::memcpy(s.horizon, k->horizon, 12);
+            std::memcpy(s.zenith, k->zenith, 12);
+            s.scale = k->scale;
+            s.yaw = k->yaw;
+        }
+        if (k->mode == OCTPT_SKY_MAP) {
+            hipStream_t hs = static_cast<hipStream_t>(stream);
+            const size_t n = (size_t)k->width * k->height * 4u;
+            HIP_TRY(ctx, hipMalloc(&map, n * sizeof(float)));
+            hipError_t e = hipMemcpyAsync(map, d_texels, n * sizeof(float), hipMemcpyDeviceToDevice, hs);
+            if (e == hipSuccess) e = launch_sky_sanitise(map, n, hs);
+            if (e == hipSuccess) e = hipStreamSynchronize(hs);
+            if (e != hipSuccess) {
+                (void)hipFree(map);
+                return hip_fail(ctx, e, "set_sky: map copy");
+            }
+            s.width = k->width;
+            s.height = k->height;
+            s.texels = map;
+        }
+        // an earlier render on any stream may still read the map this call replaces
+        if (ctx->sky_map) {
+            const hipError_t e = hipDeviceSynchronize();
+            if (e != hipSuccess) {
+                if (map) (void)hipFree(map);
+                return hip_fail(ctx, e, "set_sky");
+            }
+            (void)hipFree(ctx->sky_map);
+        }
+        ctx->sky_map = map;
+        ctx->sky = s;
+        ctx->sky_pub = *k;
+        if (k->mode == OCTPT_SKY_DEFAULT) ctx->sky_pub = octpt_sky{};
+        return OCTPT_OK;
+    });
+}
+
+octpt_status octpt_set_sky(octpt_ctx *ctx, const octpt_sky *k, const float *texels) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    octpt_status st = check_sky(ctx, k, texels != nullptr);
+    if (st != OCTPT_OK) return st;
+    return guarded(ctx, "set_sky", [&]() -> octpt_status {
+        join_inflight(ctx);
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HostStage hs(ctx->stream);
+        const bool map = k->mode == OCTPT_SKY_MAP;
+        const float *d_texels = map ? hs.in(texels, (size_t)k->width * k->height * 4u) : nullptr;
+        if (hs.ok() && (st = octpt_set_sky_device(ctx, k, d_texels, ctx->stream)) != OCTPT_OK) return st;
+        if (hs.finish() != hipSuccess) return hip_fail(ctx, hs.error(), "set_sky");
+        return OCTPT_OK;
+    });
+}
+
+octpt_status octpt_clear_sky(octpt_ctx *ctx) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    const octpt_sky none{};
+    return octpt_set_sky_device(ctx, &none, nullptr, nullptr);
+}
+
+octpt_status octpt_get_sky(const octpt_ctx *ctx, octpt_sky *k) {
+    if (!ctx || !k) return OCTPT_ERR_INVALID_ARG;
+    *k = ctx->sky_pub;
+    return OCTPT_OK;
+}
+
+octpt_status octpt_sky_radiance_device(octpt_ctx *ctx, const float *d_dirs, uint32_t n, float *d_out, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (n != 0u && (!d_dirs || !d_out)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky_radiance: NULL buffer");
+    return guarded(ctx, "sky_radiance", [&]() -> octpt_status {
+        join_inflight(ctx);
+        if (is_multi(ctx)) return forwarded(ctx, octpt_sky_radiance_device(ctx->sub[0], d_dirs, n, d_out, stream));
+        if (n == 0u) return OCTPT_OK;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, launch_sky_radiance(ctx->sky, d_dirs, n, d_out, static_cast<hipStream_t>(stream)));
+        return OCTPT_OK;
+    });
+}
+
+octpt_status octpt_sky_radiance_ctx(octpt_ctx *ctx, const float *dirs, uint32_t n, float *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (n != 0u && (!dirs || !out)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky_radiance: NULL buffer");
+    return guarded(ctx, "sky_radiance", [&]() -> octpt_status {
+        join_inflight(ctx);
+        if (is_multi(ctx)) return forwarded(ctx, octpt_sky_radiance_ctx(ctx->sub[0], dirs, n, out));
+        if (n == 0u) return OCTPT_OK;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HostStage hs(ctx->stream);
+        const float *d_dirs = hs.in(dirs, 3u * (size_t)n);
+        float *d_out = hs.out(out, 3u * (size_t)n);
+        octpt_status st = OCTPT_OK;
+        if (hs.ok() && (st = octpt_sky_radiance_device(ctx, d_dirs, n, d_out, ctx->stream)) != OCTPT_OK) return st;
+        if (hs.finish() != hipSuccess) return hip_fail(ctx, hs.error(), "sky_radiance");
+        return OCTPT_OK;
+    });
 }
 
 octpt_status octpt_get_camera(const octpt_ctx *ctx, octpt_camera *c) {

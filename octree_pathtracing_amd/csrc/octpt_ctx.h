@@ -79,6 +79,11 @@ struct octpt_ctx {
     // the ray source (C41, octpt_set_ray_source): d_rays NULL = none.  The caller's buffer; ctx->C never carries it
     // (ray_source_camera below forms the camera a render passes to its kernels)
     octpt_ray_source rays{};
+    // the sky (C42, octpt_set_sky): mode kSkyDefault in a new context.  A MAP's texels are the context's own copy
+    // (sky_map, replaced whole by every MAP setting and freed by any other), which sky.texels points into
+    octpt::Sky sky{};
+    float *sky_map = nullptr;
+    octpt_sky sky_pub{};  // the setting as octpt_get_sky returns it
     // per-context device state
     uint32_t *d_counters = nullptr;  // ring of work counters, one per launch
     // branch schedule of the current render (C20): host copy + grow-only device table

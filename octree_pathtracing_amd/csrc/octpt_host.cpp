@@ -19,6 +19,7 @@
 #include "octpt_emitter.h"
 #include "octpt_mask.h"
 #include "octpt_reproject.h"
+#include "octpt_sky.h"
 
 namespace {
 constexpr uint32_t kMaxScale = 23u;   // OCTREE_MAX_SCALE, octree_traversal.rs:14
@@ -298,6 +299,69 @@ extern "C" octpt_status octpt_ray_source_rays(const octpt_camera *fallback, cons
                                                       xys[3u * i + 2u], o, o + 3);
         if (rng_state) rng_state[i] = st;
     }
+    return OCTPT_OK;
+}
+
+// The sky's colour for n directions: csrc/octpt_sky.h's sky_radiance, the text the sky instances of
+// shade, the drain and the preview compile, over a sanitised host copy of the map.  Every check comes before the
+// first write.
+namespace {
+octpt_status host_sky(const octpt_sky *sky, const float *texels, octpt::Sky &K, std::vector<float> &map) {
+    if (!sky) return OCTPT_ERR_INVALID_ARG;
+    for (uint32_t w : sky->reserved)
+        if (w != 0u) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::sky_mode_known(sky->mode)) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::sky_fields_valid(sky->mode, sky->scale, sky->yaw, sky->width, sky->height, texels != nullptr))
+        return OCTPT_ERR_INVALID_ARG;
+    K = octpt::Sky{};
+    K.mode = sky->mode;
+    if (sky->mode == OCTPT_SKY_DEFAULT) return OCTPT_OK;
+    std::memcpy(K.color, sky->color, 12);
+    std::memcpy(K.horizon, sky->horizon, 12);
+    std::memcpy(K.zenith, sky->zenith, 12);
+    K.scale = sky->scale;
+    K.yaw = sky->yaw;
+    if (sky->mode == OCTPT_SKY_MAP) {
+        const size_t n = (size_t)sky->width * sky->height * 4u;
+        try {
+            map.resize(n);
+        } catch (const std::bad_alloc &) {
+            return OCTPT_ERR_OOM;
+        }
+        for (size_t i = 0; i < n; ++i) map[i] = octpt::sky_sanitise(texels[i]);
+        K.width = sky->width;
+        K.height = sky->height;
+        K.texels = map.data();
+    }
+    return OCTPT_OK;
+}
+}  // namespace
+
+extern "C" octpt_status octpt_sky_radiance(const octpt_sky *sky, const float *texels, const float *dirs, uint32_t n,
+                                           float *out) {
+    if (n != 0u && (!dirs || !out)) return OCTPT_ERR_INVALID_ARG;
+    octpt::Sky K;
+    std::vector<float> map;
+    const octpt_status st = host_sky(sky, texels, K, map);
+    if (st != OCTPT_OK) return st;
+    for (uint32_t i = 0; i < n; ++i) octpt::sky_radiance(K, dirs + 3u * (size_t)i, out + 3u * (size_t)i);
+    return OCTPT_OK;
+}
+
+// ... and a MAP's lookup position alone, in texels (sky_map_position): what the bound of the lookup's error is
+// measured from
+extern "C" octpt_status octpt_sky_map_position(const octpt_sky *sky, const float *dirs, uint32_t n, float *out_xy) {
+    if (n != 0u && (!dirs || !out_xy)) return OCTPT_ERR_INVALID_ARG;
+    if (!sky || sky->mode != OCTPT_SKY_MAP) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::sky_fields_valid(sky->mode, sky->scale, sky->yaw, sky->width, sky->height, true))
+        return OCTPT_ERR_INVALID_ARG;
+    octpt::Sky K{};
+    K.mode = sky->mode;
+    K.yaw = sky->yaw;
+    K.width = sky->width;
+    K.height = sky->height;
+    for (uint32_t i = 0; i < n; ++i)
+        octpt::sky_map_position(K, dirs + 3u * (size_t)i, out_xy[2u * (size_t)i], out_xy[2u * (size_t)i + 1u]);
     return OCTPT_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/octpt.h"
+#include "octpt_sky.h"
 
 namespace octpt {
 
@@ -123,6 +124,13 @@ struct DevScene {
     DevSun sun;
     int32_t emitters;
     uint32_t has_images;  // some texture is an image (shade's colour-only instance when not)
+};
+
+// What a sky instance (octpt_kernels_sky.hip, octpt_kernels_sky_emit.hip) takes in the scene's place:
+// the scene record as it is, the context's sky behind it.  The instances launched under the DEFAULT sky take DevScene
+// as they always did; no struct of theirs changes.
+struct SkyScene : DevScene {
+    Sky sky;
 };
 
 struct DevCamera {
@@ -378,8 +386,10 @@ __host__ __device__ inline bool multi_slot(uint32_t W, uint32_t H, uint32_t tile
 }
 
 // kernel launchers (octpt_kernels.hip)
+// sky (here, launch_wf_shade and launch_wf_drain; C42): NULL = the DEFAULT sky, the instances as they always were;
+// else the sky instances, which take the scene with *sky behind it (SkyScene)
 hipError_t launch_preview(const DevScene &S, const DevCamera &C, const DevRender &R, float4 *accum,
-                          uint32_t *segcount, unsigned long long *stats, hipStream_t stream);
+                          uint32_t *segcount, unsigned long long *stats, hipStream_t stream, const Sky *sky = nullptr);
 hipError_t launch_render(const DevScene &S, const DevCamera &C, const DevRender &R, float4 *accum,
                          uint32_t *segcount, uint32_t *counter, unsigned long long *stats, int grid,
                          hipStream_t stream);
@@ -404,6 +414,19 @@ const void *rays_shade_kernel(bool nee, bool lds, int mode);
 const void *rays_preview_kernel(int prims);
 const void *rays_gbuffer_kernel(int prims);
 const void *rays_emit_shade_kernel(bool nee, bool lds, int mode);
+// the sky instances (C42; octpt_kernels_sky.hip and octpt_kernels_sky_emit.hip, modules of their own), taken under a
+// sky other than DEFAULT: the general shade (mode 0 or 1; such chunks never take the lean state), the drain and the
+// preview, whose camera form -- pinhole, lens, projection, ray list -- is a launch-uniform run-time switch on the camera
+// record, and the emitter twins of shade and the block scene's drain.  The seed is the camera's own, as without a sky.
+const void *sky_shade_kernel(bool nee, bool lds, int mode);
+const void *sky_drain_kernel(int prims, bool nee);
+const void *sky_preview_kernel(int prims);
+const void *sky_emit_shade_kernel(bool nee, bool lds, int mode);
+const void *sky_emit_drain_kernel(bool nee);
+// octpt_set_sky's pass over a map (sky_sanitise on each of n floats, in place) and octpt_sky_radiance_device's kernel
+// (sky_radiance for n directions of three floats)
+hipError_t launch_sky_sanitise(float *texels, size_t n, hipStream_t stream);
+hipError_t launch_sky_radiance(const Sky &sky, const float *dirs, uint32_t n, float *out, hipStream_t stream);
 hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t n_seed,
                           uint32_t chunk_items, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q, bool cam, uint32_t refill, int grid,
@@ -412,7 +435,7 @@ hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q,
 // smaller than the chunk, finished paths regenerate their slots (the instance with regeneration)
 hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t q,
                            uint32_t chunk_items, uint32_t first, bool regen, int grid, unsigned long long *stats,
-                           hipStream_t stream, bool emit = false);
+                           hipStream_t stream, bool emit = false, const Sky *sky = nullptr);
 // the emitter instances (C38; octpt_kernels_emit.hip, a module of its own), which launch_wf_shade and launch_wf_drain
 // take with `emit`: S is then a block-value scene whose leaf_sph holds the device address of the render's EmitGrid
 // (csrc/octpt_emitter.h), and the pd planes number six
@@ -424,7 +447,7 @@ int shade_blocks_per_cu(const DevScene &S, int mode);
 bool shade_lds_tables(const DevScene &S);
 // the drain of a chunk's last queued rays (every chunk item claimed): one launch, paths finished in-lane
 hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuffers &B, uint32_t q, int grid,
-                           unsigned long long *stats, hipStream_t stream, bool emit = false);
+                           unsigned long long *stats, hipStream_t stream, bool emit = false, const Sky *sky = nullptr);
 // the host's snapshot of an iteration's counters: queue q's kSegs segment counts, then the kSegs item
 // counters, written by one 128-thread block into pinned host memory (enqueue_wavefront's steering)
 hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_out, hipStream_t stream);

@@ -17,6 +17,8 @@
 // implements as `forward_accumulation`.
 #include "octpt_internal.h"
 #include "octpt_lens.h"
+#include "octpt_math.h"
+#include "octpt_sky.h"
 #include "octpt_emitter.h"
 #include "octpt_rcp.h"
 #include "octpt_reproject.h"
@@ -92,67 +94,7 @@ __device__ __forceinline__ float signum_(float f) { return (__float_as_uint(f) >
 // (dm_sincos: csrc/octpt_lens.h, the text the host's lens rays compile too)
 __device__ __forceinline__ float dm_cos(float x) { float s, c; dm_sincos(x, s, c); return c; }
 
-__device__ inline float dm_asin(float x) {
-    const float a = fabsf(x);
-    float z, xx;
-    bool flag = false;
-    if (a > 0.5f) {
-        z = 0.5f * (1.0f - a);
-        xx = sqrtf(z);
-        flag = true;
-    } else {
-        xx = a;
-        z = a * a;
-    }
-    float r;
-    if (a < 1.0e-4f && !flag) {
-        r = xx;
-    } else {
-        r = ((((4.2163199048e-2f * z + 2.4181311049e-2f) * z + 4.5470025998e-2f) * z + 7.4953002686e-2f) * z +
-             1.6666752422e-1f) * z * xx + xx;
-    }
-    if (flag) {
-        r = r + r;
-        r = 1.5707963267948966f - r;
-    }
-    return x < 0.0f ? -r : r;
-}
-__device__ inline float dm_acos(float x) {
-    if (x < -0.5f) return PI_F - 2.0f * dm_asin(sqrtf(0.5f * (1.0f + x)));
-    if (x > 0.5f) return 2.0f * dm_asin(sqrtf(0.5f * (1.0f - x)));
-    return 1.5707963267948966f - dm_asin(x);
-}
-__device__ inline float dm_atan_core(float x) {
-    float sgn = 1.0f, y;
-    if (x < 0.0f) { sgn = -1.0f; x = -x; }
-    if (x > 2.414213562373095f) {
-        y = 1.5707963267948966f;
-        x = -1.0f / x;
-    } else if (x > 0.4142135623730950f) {
-        y = 0.7853981633974483f;
-        x = (x - 1.0f) / (x + 1.0f);
-    } else {
-        y = 0.0f;
-    }
-    const float z = x * x;
-    y = y + ((((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z - 3.33329491539e-1f) * z * x + x);
-    return sgn < 0.0f ? -y : y;
-}
-__device__ inline float dm_atan2(float y, float x) {
-    int code = 0;
-    if (x < 0.0f) code = 2;
-    if (y < 0.0f) code |= 1;
-    if (x == 0.0f) {
-        if (code & 1) return -1.5707963267948966f;
-        if (y == 0.0f) return 0.0f;
-        return 1.5707963267948966f;
-    }
-    if (y == 0.0f) return (code & 2) ? PI_F : 0.0f;
-    float w = 0.0f;
-    if (code == 2) w = PI_F;
-    else if (code == 3) w = -PI_F;
-    return w + dm_atan_core(y / x);
-}
+// (dm_asin, dm_acos, dm_atan2: csrc/octpt_math.h, the text the host's sky lookup compiles too)
 __device__ __forceinline__ float dm_hypot(float x, float y) { return sqrtf(x * x + y * y); }
 
 // ---------------------------------------------------------------------------
@@ -1240,8 +1182,25 @@ __device__ inline int esvo_step(const DevScene &S, const TraceRay &ray, Esvo &E,
 // ---------------------------------------------------------------------------
 // sky + sun (scene/mod.rs:216-268, 384-426)
 // ---------------------------------------------------------------------------
+// The sky: OCTPT_SKY_TU is defined by octpt_kernels_sky.hip and octpt_kernels_sky_emit.hip alone, which
+// compile this text for the sky instances of the general shade, the drain and the preview; everywhere else every line
+// under it is absent and the text is what it was.  Such an instance takes a SkyScene where the others take a DevScene
+// (KernelScene): the scene record with the context's sky behind it, which sky_base reads back through the reference
+// the shared functions pass on.  sky_base puts the base colour (csrc/octpt_sky.h) where sky_color starts from the
+// constant everywhere else; the sun's terms add on top as they always did.
+#if defined(OCTPT_SKY_TU)
+using KernelScene = SkyScene;
+__device__ __forceinline__ void sky_base(const DevScene &S, v3 d, float out[3]) {
+    const float dd[3] = {d.x, d.y, d.z};
+    sky_radiance(static_cast<const SkyScene &>(S).sky, dd, out);
+}
+#else
+using KernelScene = DevScene;
+#endif
 __device__ inline void sky_color(const DevSun &K, const PathState &r, float out[3]) {
+#if !defined(OCTPT_SKY_TU)  // (a sky instance's caller has put the sky's colour there: sky_base)
     out[0] = 0.5f; out[1] = 0.7f; out[2] = 1.0f;
+#endif
     const v3 d = r.d;
     const bool textured = (r.depth == 0u) || r.specular;  // get_sky_color_interp / get_sky_color(true)
     if (textured ? !K.draw_texture : !K.diffuse_sun) return;
@@ -1407,6 +1366,8 @@ __device__ inline v3 random_sun_direction(const DevSun &K, uint32_t &rng) {
 // samples read consecutive 24-byte records, 1536 contiguous bytes over the six loads.  An instance reads only its own
 // form's fields.
 constexpr int kCamPinhole = 0, kCamLens = 1, kCamProj = 2, kCamRays = 3;
+// kCamAny, the sky instances' alone (C42, OCTPT_SKY_TU): whichever of the four the camera record says, at run time
+constexpr int kCamAny = 4;
 // The preview and the guide-buffer kernel know two forms per module, the pinhole and (kProj) this one: the ray-list
 // camera in its module (octpt_kernels_rays.hip, OCTPT_RAYS_TU), the projections everywhere else.  A constant of the
 // module and no third template argument, so that every existing instance keeps its name and its code.
@@ -1419,7 +1380,12 @@ template <int kCam = kCamPinhole>
 __device__ inline void new_path(const DevCamera &C, const DevRender &R, uint32_t x, uint32_t y, uint32_t sample,
                                 PathState &ps) {
     float o[3], d[3];
-    if constexpr (kCam == kCamRays) ps.rng = ray_list_ray<true>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, sample, o, d);
+    if constexpr (kCam == kCamAny) {  // a sky instance (C42): the same four texts behind a launch-uniform switch
+        if (C.proj_mode == kProjModeRays) ps.rng = ray_list_ray<true>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, sample, o, d);
+        else if (C.proj_mode != 0u) ps.rng = projection_ray<true>(C, R, x, y, sample, o, d);
+        else if (C.aperture > 0.0f) ps.rng = lens_ray<true>(C, R, x, y, sample, o, d);
+        else ps.rng = lens_ray<false>(C, R, x, y, sample, o, d);
+    } else if constexpr (kCam == kCamRays) ps.rng = ray_list_ray<true>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, sample, o, d);
     else if constexpr (kCam == kCamProj) ps.rng = projection_ray<true>(C, R, x, y, sample, o, d);
     else ps.rng = lens_ray<kCam == kCamLens>(C, R, x, y, sample, o, d);
     ps.o = V(o[0], o[1], o[2]);
@@ -1599,6 +1565,9 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
 #endif
     if (!hit) {
         float sky[3];
+#if defined(OCTPT_SKY_TU)
+        sky_base(S, ray.d, sky);
+#endif
         sky_color(S.sun, ray, sky);
         ray.L = V(ray.L.x + ray.T.x * sky[0], ray.L.y + ray.T.y * sky[1], ray.L.z + ray.T.z * sky[2]);
         return false;
@@ -1908,8 +1877,20 @@ __global__ __launch_bounds__(kBlock) void render_kernel(DevScene S, DevCamera C,
     (OCTPT_PREVIEW_BOUNDS ? ((k) == kPrimsSpheres ? 7 : ((k) == kPrimsBoxes || (k) == kPrimsBlocks) ? 6 : 5) : 1)
 // kProj: the un-jittered ray of the module's camera form (kCamCentre) in place of get_ray's -- the camera's projection
 // (projection_ray<false>, C40), or ray 0 of the pixel in the caller's list (ray_list_ray<false>, C41)
+#if defined(OCTPT_SKY_TU)
+// a sky instance's un-jittered ray (C42): the pinhole ray the caller formed, or the camera's own form, a launch-uniform
+// switch over the same texts
+__device__ inline void centre_ray_any(const DevCamera &C, const DevRender &R, uint32_t x, uint32_t y, PathState &ps) {
+    if (C.proj_mode == 0u) return;
+    float po[3], pd[3];
+    if (C.proj_mode == kProjModeRays) (void)ray_list_ray<false>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, 0u, po, pd);
+    else (void)projection_ray<false>(C, R, x, y, 0u, po, pd);
+    ps.o = V(po[0], po[1], po[2]);
+    ps.d = V(pd[0], pd[1], pd[2]);
+}
+#endif
 template <int kPrims, bool kProj = false>
-__global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void preview_kernel(DevScene S, DevCamera C, DevRender R,
+__global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void preview_kernel(KernelScene S, DevCamera C, DevRender R,
                                                          float4 *__restrict__ accum, uint32_t *__restrict__ segcount,
                                                          unsigned long long *__restrict__ stats) {
     extern __shared__ uint2 lds_stack[];
@@ -1929,6 +1910,9 @@ __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void previe
                            vscale(V(C.up[0], C.up[1], C.up[2]), yn));
         ps.o = V(C.eye[0], C.eye[1], C.eye[2]);
         ps.d = vnorm(nd);
+#if defined(OCTPT_SKY_TU)
+        if constexpr (kProj) centre_ray_any(C, R, x, y, ps);
+#else
         if constexpr (kProj) {
             float po[3], pd[3];
             if constexpr (kCamCentre == kCamRays) (void)ray_list_ray<false>(C, R, cam_ray_list(C), cam_ray_list_rpp(C), x, y, 0u, po, pd);
@@ -1936,6 +1920,7 @@ __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void previe
             ps.o = V(po[0], po[1], po[2]);
             ps.d = V(pd[0], pd[1], pd[2]);
         }
+#endif
         ps.n = V(0.0f, 0.0f, 0.0f);
         ps.col[0] = ps.col[1] = ps.col[2] = ps.col[3] = 0.0f;
         ps.T = V(1.0f, 1.0f, 1.0f);
@@ -1967,6 +1952,9 @@ __global__ __launch_bounds__(kBlock, OCTPT_PREVIEW_WAVES_OF(kPrims)) void previe
         }
         float out[3];
         if (ps.cur == 0u) {
+#if defined(OCTPT_SKY_TU)
+            sky_base(S, ps.d, out);
+#endif
             sky_color(S.sun, ps, out);  // depth 0: get_sky_color_inner + add_sun_color
         } else {
             const float shading = fmaxf(0.3f, vdot(ps.n, V(S.sun.sw[0], S.sun.sw[1], S.sun.sw[2])));  // AMBIENT
@@ -2601,7 +2589,7 @@ constexpr uint32_t kShadeLdsBlocks = OCTPT_SHADE_LDS_BLOCKS;
 // kCam (C37, C40): the camera has an aperture or a projection (the first launch's rebuild and the regeneration form
 // its rays); the general instances (kMode 0 and 1) alone, such a camera's chunks do not take the lean state
 template <bool kNee, bool kLdsMats, int kMode, bool kNoFirst = false, int kSP = kPrimsModels, int kCam = kCamPinhole>
-__global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT_SHADE_WAVES) void wf_shade_kernel(DevScene Sg, DevCamera C, DevRender R, WaveBuffers B,
+__global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT_SHADE_WAVES) void wf_shade_kernel(KernelScene Sg, DevCamera C, DevRender R, WaveBuffers B,
                                                           uint32_t q, uint32_t chunk_items, uint32_t first_arg,
                                                           unsigned long long *__restrict__ stats) {
     const uint32_t first = kNoFirst ? 0u : first_arg;
@@ -2610,7 +2598,7 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT
     __shared__ DevTexture stexs[kT];
     __shared__ float slut[kLdsMats ? 256 : 1];
     __shared__ uint32_t sblk[kLdsMats ? 6u * kShadeLdsBlocks : 1];
-    DevScene S = Sg;
+    KernelScene S = Sg;
     if constexpr (kLdsMats) {
         for (uint32_t m = threadIdx.x; m < Sg.n_mats; m += kBlock) smats[m] = Sg.mats[m];
         for (uint32_t t = threadIdx.x; t < Sg.n_texs; t += kBlock) stexs[t] = Sg.texs[t];
@@ -2676,7 +2664,7 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? OCTPT_SHADE_LEAN_WAVES : OCTPT
 // esvo_step and hit record, shade_lane, the ray record as store_ray writes it), so results and
 // statistics equal the extend / shade iterations it replaces.  No regeneration: items are exhausted.
 template <int kPrims, bool kNee>
-__global__ __launch_bounds__(kBlock) void wf_drain_kernel(DevScene S, DevRender R, WaveBuffers B, uint32_t q,
+__global__ __launch_bounds__(kBlock) void wf_drain_kernel(KernelScene S, DevRender R, WaveBuffers B, uint32_t q,
                                                           unsigned long long *__restrict__ stats) {
     extern __shared__ uint2 lds_stack[];
     const Stack stk = stack_of(lds_stack, S.depth);
@@ -3754,7 +3742,54 @@ __global__ __launch_bounds__(256) void atrous_var_kernel(DevDenoiseVar D, uint32
 
 }  // namespace
 
-#if defined(OCTPT_RAYS_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_rays_emit.hip alone: not a build switch)
+#if defined(OCTPT_SKY_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_sky_emit.hip alone: not a build switch)
+// The emitter instances (C38) of the general shade and the block scene's drain under a sky (C42), a module of their
+// own like every other family.
+template <bool kNee, bool kLds>
+static const void *sky_emit_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamAny>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamAny>);
+}
+const void *sky_emit_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? sky_emit_shade_of<true, true>(mode) : sky_emit_shade_of<true, false>(mode))
+               : (lds ? sky_emit_shade_of<false, true>(mode) : sky_emit_shade_of<false, false>(mode));
+}
+const void *sky_emit_drain_kernel(bool nee) {
+    return nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
+               : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, false>);
+}
+#elif defined(OCTPT_SKY_TU)  // (set by octpt_kernels_sky.hip alone: not a build switch)
+// The sky instances (C42) of the general shade, the drain and the preview, for octpt_kernels_sky.hip, which compiles
+// this text for them alone (a module of their own, as every other family is, and for their reason: the instances
+// launched under the DEFAULT sky stay the code they are).  One shade family serves the four camera forms (kCamAny); the
+// seed is the camera's own.  No megakernel instance: such a render is refused.
+template <bool kNee, bool kLds>
+static const void *sky_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamAny>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamAny>);
+}
+const void *sky_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? sky_shade_of<true, true>(mode) : sky_shade_of<true, false>(mode))
+               : (lds ? sky_shade_of<false, true>(mode) : sky_shade_of<false, false>(mode));
+}
+template <int kPrims>
+static const void *sky_drain_of(bool nee) {
+    return nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrims, true>)
+               : reinterpret_cast<const void *>(wf_drain_kernel<kPrims, false>);
+}
+const void *sky_drain_kernel(int prims, bool nee) {
+    return prims == kPrimsBlocks   ? sky_drain_of<kPrimsBlocks>(nee)
+           : prims == kPrimsModels ? sky_drain_of<kPrimsModels>(nee)
+           : prims == kPrimsBoxes  ? sky_drain_of<kPrimsBoxes>(nee)
+                                   : sky_drain_of<kPrimsSpheres>(nee);
+}
+const void *sky_preview_kernel(int prims) {
+    return prims == kPrimsBlocks   ? reinterpret_cast<const void *>(preview_kernel<kPrimsBlocks, true>)
+           : prims == kPrimsModels ? reinterpret_cast<const void *>(preview_kernel<kPrimsModels, true>)
+           : prims == kPrimsBoxes  ? reinterpret_cast<const void *>(preview_kernel<kPrimsBoxes, true>)
+                                   : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres, true>);
+}
+#elif defined(OCTPT_RAYS_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_rays_emit.hip alone: not a build switch)
 // The emitter instances (C38) of the general shade for the ray-list camera (C41), a module of their own like every
 // other family.
 template <bool kNee, bool kLds>
@@ -3913,8 +3948,16 @@ static int scene_prims(const DevScene &S) {
     return S.has_blocks ? kPrimsBlocks : S.has_models ? kPrimsModels : S.has_cuboids ? kPrimsBoxes : kPrimsSpheres;
 }
 
+// what a sky instance takes in the scene's place (C42)
+static SkyScene sky_scene(const DevScene &S, const Sky &sky) {
+    SkyScene SS{};
+    static_cast<DevScene &>(SS) = S;
+    SS.sky = sky;
+    return SS;
+}
+
 hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRender &R, float4 *accum,
-                          uint32_t *segcount, unsigned long long *stats, hipStream_t stream) {
+                          uint32_t *segcount, unsigned long long *stats, hipStream_t stream, const Sky *sky) {
     const DevScene &S = S0;
     const uint32_t grid = (R.total_items + kBlock - 1u) / kBlock;
     // the primitive kinds of the scene pick the instance, as for wf_extend_kernel
@@ -3924,8 +3967,13 @@ hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRende
                                      : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres>);
     if (C.proj_mode != 0u) fn = proj_preview_kernel(scene_prims(S));  // the projected instance (C40)
     if (C.proj_mode == kProjModeRays) fn = rays_preview_kernel(scene_prims(S));  // the ray-list instance (C41)
-    void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R), &accum,
-                    &segcount, &stats};
+    SkyScene SS{};
+    if (sky) {  // the sky instance (C42), whatever the camera: it takes the scene with the sky behind it
+        fn = sky_preview_kernel(scene_prims(S));
+        SS = sky_scene(S, *sky);
+    }
+    void *args[] = {sky ? static_cast<void *>(&SS) : const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C),
+                    const_cast<DevRender *>(&R), &accum, &segcount, &stats};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args,
                                          render_lds_bytes(S.depth), stream);
     if (e != hipSuccess) return e;
@@ -4098,24 +4146,32 @@ int shade_blocks_per_cu(const DevScene &S, int mode) {
 
 hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t q,
                            uint32_t chunk_items, uint32_t first, bool regen, int grid, unsigned long long *stats,
-                           hipStream_t stream, bool emit) {
+                           hipStream_t stream, bool emit, const Sky *sky) {
     uint32_t first_u = first;
-    void *args[] = {const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C), const_cast<DevRender *>(&R),
-                    const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
+    SkyScene SS{};
+    if (sky) SS = sky_scene(S, *sky);
+    void *args[] = {sky ? static_cast<void *>(&SS) : const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C),
+                    const_cast<DevRender *>(&R), const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
     const int cam = C.proj_mode == kProjModeRays ? kCamRays
                     : C.proj_mode != 0u          ? kCamProj
                     : C.aperture > 0.0f          ? kCamLens
                                                  : kCamPinhole;
-    const hipError_t e = hipLaunchKernel(shade_instance(S, shade_mode(regen, B.lean != 0u), first != 0u, cam, emit),
-                                         dim3(grid), dim3(kBlock), args, 0, stream);
+    const int mode = shade_mode(regen, B.lean != 0u);
+    // a sky (C42): the sky instances, one family for every camera form (such chunks never take the lean state)
+    const void *fn = !sky   ? shade_instance(S, mode, first != 0u, cam, emit)
+                     : emit ? sky_emit_shade_kernel(S.sun.sun_sampling != 0, shade_lds_tables(S), mode)
+                            : sky_shade_kernel(S.sun.sun_sampling != 0, shade_lds_tables(S), mode);
+    const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, stream);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
 hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuffers &B, uint32_t q, int grid,
-                           unsigned long long *stats, hipStream_t stream, bool emit) {
+                           unsigned long long *stats, hipStream_t stream, bool emit, const Sky *sky) {
     const bool nee = S.sun.sun_sampling != 0;
-    const void *fn = emit ? emit_drain_kernel(nee) : S.has_blocks ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
+    SkyScene SS{};
+    if (sky) SS = sky_scene(S, *sky);
+    const void *fn = sky ? (emit ? sky_emit_drain_kernel(nee) : sky_drain_kernel(scene_prims(S), nee)) : emit ? emit_drain_kernel(nee) : S.has_blocks ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
                                          : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, false>))
                      : S.has_models ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsModels, true>)
                                          : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsModels, false>))
@@ -4123,7 +4179,8 @@ hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuff
                                             : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBoxes, false>))
                                      : (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsSpheres, true>)
                                             : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsSpheres, false>));
-    void *args[] = {const_cast<DevScene *>(&S), const_cast<DevRender *>(&R), const_cast<WaveBuffers *>(&B), &q, &stats};
+    void *args[] = {sky ? static_cast<void *>(&SS) : const_cast<DevScene *>(&S), const_cast<DevRender *>(&R),
+                    const_cast<WaveBuffers *>(&B), &q, &stats};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, render_lds_bytes(S.depth), stream);
     if (e != hipSuccess) return e;
     return hipGetLastError();
@@ -4239,6 +4296,37 @@ hipError_t launch_unshard(uint32_t W, uint32_t H, uint32_t shard_count, const ui
                           uint32_t stride, float4 *frame, hipStream_t stream) {
     hipLaunchKernelGGL(unshard_kernel, dim3((W * H + 255u) / 256u), dim3(256), 0, stream, W, H, shard_count, tile_pos,
                        shards, stride, frame);
+    return hipGetLastError();
+}
+
+// The sky's two small kernels, this module's alone.  A map's floats through sky_sanitise, in place,
+// grid-stride; and csrc/octpt_sky.h's sky_radiance for n directions, one thread each (octpt_sky_radiance_device).
+namespace {
+__global__ __launch_bounds__(256) void sky_sanitise_kernel(float *__restrict__ texels, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u)
+        texels[i] = sky_sanitise(texels[i]);
+}
+__global__ __launch_bounds__(256) void sky_radiance_kernel(Sky sky, const float *__restrict__ dirs, uint32_t n,
+                                                           float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float d[3] = {dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]};
+    float c[3];
+    sky_radiance(sky, d, c);
+    for (int k = 0; k < 3; ++k) out[3u * (size_t)i + k] = c[k];
+}
+}  // namespace
+
+hipError_t launch_sky_sanitise(float *texels, size_t n, hipStream_t stream) {
+    const size_t blocks = (n + 255u) / 256u;
+    const uint32_t grid = blocks < 65536u ? (uint32_t)blocks : 65536u;
+    hipLaunchKernelGGL(sky_sanitise_kernel, dim3(grid), dim3(256), 0, stream, texels, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_sky_radiance(const Sky &sky, const float *dirs, uint32_t n, float *out, hipStream_t stream) {
+    const uint32_t grid = (uint32_t)(((uint64_t)n + 255u) / 256u);  // (in 64 bits: n + 255 wraps above 2^32 - 256)
+    hipLaunchKernelGGL(sky_radiance_kernel, dim3(grid), dim3(256), 0, stream, sky, dirs, n, out);
     return hipGetLastError();
 }
 

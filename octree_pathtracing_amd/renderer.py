@@ -14,7 +14,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from .scene import Camera, RenderSettings, Scene
+from .scene import Camera, RenderSettings, Scene, Sky
 
 
 class RendererStatus(enum.IntEnum):  # tile_renderer.rs:30-60
@@ -120,6 +120,7 @@ class HipRenderer:
         self._spp = 0
         self._in_flight = None
         self._ray_source = None  # (the tensor set_ray_source keeps alive, (H, W, R)) while a ray source is set
+        self._sky = Sky()  # the sky in force (set_sky)
         self.set_camera(self._camera)
 
     # ------------------------------------------------------------ lifecycle
@@ -226,6 +227,47 @@ class HipRenderer:
         """octpt_ray_source_rays with this renderer's camera as the fallback: for rows (x, y, sample) the first rays
         [n, 6] a render under the list `rays` (H, W, R, 6) traces, bit for bit, and the paths' RNG states [n]."""
         return ray_source_rays(self._camera, rays, seed, xys)
+
+    def set_sky(self, sky: Sky) -> None:
+        """octpt_set_sky: the base colour every later render of this renderer adds where a ray leaves
+        the world -- scene.Sky.color / gradient / map, or Sky() for the default constant.  The library copies a map
+        (a numpy array is staged, a tensor on this renderer's device is copied there), so the caller's stays its own.
+        A refused setting (OctptError) leaves the previous sky in force."""
+        d = sky.desc()
+        tex = sky.texels
+        if tex is None or isinstance(tex, np.ndarray):
+            host = np.ascontiguousarray(tex, np.float32) if tex is not None else None
+            st = self._lib.octpt_set_sky(self._ctx, C.byref(d), host.ctypes.data if host is not None else None)
+        else:
+            import torch
+
+            dev = torch.device("cuda", self._device)
+            if tex.dtype != torch.float32 or tex.device != dev or not tex.is_contiguous():
+                raise ValueError(f"a sky map tensor must be contiguous float32 on {dev}")
+            st = self._lib.octpt_set_sky_device(self._ctx, C.byref(d), tex.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream)
+        self._check(st)
+        self._sky = sky
+        self.reset_render()
+
+    def clear_sky(self) -> None:
+        """Back to the default sky: renders are bit for bit those of a renderer that never had one."""
+        self._check(self._lib.octpt_clear_sky(self._ctx))
+        self._sky = Sky()
+        self.reset_render()
+
+    def get_sky(self) -> Sky:
+        """The setting in force (the last accepted set_sky's, or Sky())."""
+        return self._sky
+
+    def sky_radiance(self, dirs) -> np.ndarray:
+        """octpt_sky_radiance_ctx: the colour [n, 3] this renderer's sky adds for unit directions [n, 3] (the sun's
+        terms excluded), computed on the device by the kernels' text.  scene.Sky.radiance is the CPU form; the two
+        agree bit for bit."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros_like(dirs)
+        self._check(self._lib.octpt_sky_radiance_ctx(self._ctx, dirs.ctypes.data, len(dirs), out.ctypes.data))
+        return out
 
     def which_backend(self) -> str:
         return "HIP (gfx950)"

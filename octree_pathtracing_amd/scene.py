@@ -169,6 +169,78 @@ class Camera:
 
 
 @dataclass
+class Sky:
+    """The sky of a renderer (octpt_sky): what a ray that leaves the world adds before the sun's terms.
+    Sky() is the default constant (0.5, 0.7, 1.0); the constructors below make the three other modes.  `texels` is a
+    MAP's (H, W, 4) float32 array -- numpy, or a torch tensor on the renderer's device -- row 0 the zenith, +x the
+    centre column at yaw 0."""
+    mode: int = 0
+    rgb: tuple = (0.0, 0.0, 0.0)
+    horizon: tuple = (0.0, 0.0, 0.0)
+    zenith: tuple = (0.0, 0.0, 0.0)
+    scale: float = 1.0
+    yaw: float = 0.0
+    texels: object = None
+
+    @staticmethod
+    def color(rgb, scale: float = 1.0) -> "Sky":
+        """One colour in every direction: rgb * scale."""
+        return Sky(mode=1, rgb=tuple(map(float, rgb)), scale=float(scale))
+
+    @staticmethod
+    def gradient(horizon, zenith, scale: float = 1.0) -> "Sky":
+        """horizon at and below the horizon, blending linearly in d.y to zenith straight up; times scale."""
+        return Sky(mode=2, horizon=tuple(map(float, horizon)), zenith=tuple(map(float, zenith)), scale=float(scale))
+
+    @staticmethod
+    def map(array, yaw: float = 0.0, scale: float = 1.0) -> "Sky":
+        """An equirectangular map: a numpy array or a torch tensor of shape (H, W, 3) or (H, W, 4), linear radiance
+        (sky.read_hdr reads Radiance .hdr files into one).  Three channels get an alpha of 1, which is not read."""
+        shape = tuple(int(v) for v in array.shape)
+        if len(shape) != 3 or shape[2] not in (3, 4) or shape[0] == 0 or shape[1] == 0:
+            raise ValueError(f"a sky map has shape (H, W, 3) or (H, W, 4), not {shape}")
+        if isinstance(array, np.ndarray):
+            t = np.ones(shape[:2] + (4,), np.float32)
+            t[..., :shape[2]] = array
+        else:
+            import torch
+
+            t = torch.ones(shape[:2] + (4,), dtype=torch.float32, device=array.device)
+            t[..., :shape[2]] = array.to(torch.float32)
+            t = t.contiguous()
+        return Sky(mode=3, yaw=float(yaw), scale=float(scale), texels=t)
+
+    def desc(self) -> "_lib.SkyDesc":
+        """The octpt_sky of this setting (width and height from the map)."""
+        d = _lib.SkyDesc()
+        d.mode = int(self.mode)
+        d.color[:] = self.rgb
+        d.horizon[:] = self.horizon
+        d.zenith[:] = self.zenith
+        d.scale = float(self.scale)
+        d.yaw = float(self.yaw)
+        if self.texels is not None:
+            d.height, d.width = int(self.texels.shape[0]), int(self.texels.shape[1])
+        return d
+
+    def radiance(self, dirs) -> np.ndarray:
+        """octpt_sky_radiance: the colour [n, 3] a render under this sky adds for unit directions [n, 3] (the sun's
+        terms excluded), computed on the CPU by the text the kernels compile -- bit for bit what they add."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros_like(dirs)
+        tex = None
+        if self.texels is not None:
+            tex = self.texels if isinstance(self.texels, np.ndarray) else self.texels.cpu().numpy()
+            tex = np.ascontiguousarray(tex, np.float32)
+        d = self.desc()
+        st = _lib.load().octpt_sky_radiance(C.byref(d), tex.ctypes.data if tex is not None else None, dirs.ctypes.data,
+                                            len(dirs), out.ctypes.data)
+        if st != 0:
+            raise ValueError(f"octpt_sky_radiance: status {st}")
+        return out
+
+
+@dataclass
 class Octree:
     """new_octree::Octree (new_octree.rs:13-19) + leaf payload -> primitive lists."""
     octant_mask: np.ndarray      # uint16 [n]

@@ -2,14 +2,17 @@
 # Registers, scratch, LDS and occupancy of the wavefront (resolve included), preview, guide-buffer, denoise, temporal, variance and tile-error kernels (octpt_kernels.hip),
 # of the megakernel, of the thin-lens instances of megakernel, seed and shade (octpt_kernels_lens.hip: the template
 # arguments' last is Lb1) and of the
+# sky instances of shade, the drain and the preview (octpt_kernels_sky.hip, octpt_kernels_sky_emit.hip) and of the
 # section builder's count and emit kernels (octpt_build.hip) as the compiler reports them (kernel-resource-usage
 # remarks): tools/resource_usage.sh [-DFLAG ...].  CPU only (device-only compiles).
 cd "$(dirname "$0")/.."
 FLAGS=$(python3 -c "import __graft_entry__ as g; print(' '.join(f for f in g.HIPCC_FLAGS if f not in ('-shared', '-fPIC')))")
-for SRC in octpt_kernels.hip octpt_kernels_lens.hip octpt_build.hip; do
+for SRC in octpt_kernels.hip octpt_kernels_lens.hip octpt_kernels_sky.hip octpt_kernels_sky_emit.hip octpt_build.hip; do
 # the lens module compiles the whole text: only its own instances are listed
 PAT='extend|shade|seed|drain|resolve|beam|preview|gbuffer|atrous|denoise|temporal|variance|tile_error|section_count|section_emit|render_kernel'
 [ "$SRC" = octpt_kernels_lens.hip ] && PAT='render_kernel|wf_seed_kernel|wf_shade_kernel'
+# the sky modules compile the whole text too: their own instances take a SkyScene
+case "$SRC" in octpt_kernels_sky*) PAT='SkyScene';; esac
 /opt/rocm/bin/hipcc $FLAGS "$@" -c octree_pathtracing_amd/csrc/$SRC -o /tmp/octpt_res.o --offload-device-only \
     -Rpass-analysis=kernel-resource-usage 2>&1 | sed 's/ \[-Rpass-analysis=kernel-resource-usage\]//' | awk -v pat="$PAT" '
   /Function Name:/ {n = $NF}
