@@ -426,6 +426,81 @@ octpt_status octpt_sky_radiance_ctx(octpt_ctx *ctx, const float *dirs, uint32_t 
  * lookup against a float64 restatement is measured from. */
 octpt_status octpt_sky_map_position(const octpt_sky *sky, const float *dirs, uint32_t n, float *out_xy);
 
+/* Importance sampling of the sky map: next-event estimation toward the map's bright texels.  Off by
+ * default; with it off every render is bit for bit what it is without this call.
+ * The distribution (one text, csrc/octpt_sky_sample.h, compiled by the host builder, the device builder and the
+ * kernels) is piecewise constant over the texels of the sanitised map and made of integers:
+ *   lum(x, y) = min((0.2126 r + 0.7152 g) + 0.0722 b, FLT_MAX);  m = the maximum of lum over the 3 x 3 neighbourhood,
+ *   wrapped in x and clamped in y (the bilinear lookup's footprint: the weight is non-zero wherever the lookup can be);
+ *   w = min(m * row[y], FLT_MAX), row[y] = (float)sin(pi (y + 0.5) / height) computed in double;  wmax = max w;
+ *   q = 0 where w == 0, else clamp((uint32)ceilf((w / wmax) * 65536), 1, 65536);
+ *   col_cdf[y * width + x] (uint32) the inclusive sum of q along row y, row_cdf[y] (uint64) the inclusive sum of the
+ *   rows' totals, total = row_cdf[height - 1] (0: an all-black map).
+ * octpt_build_sky_distribution is the definition: host-only, no context; texels as octpt_set_sky takes them
+ * (sanitised the same way), row_cdf[height] and col_cdf[width * height] the caller's.  INVALID_ARG: a NULL pointer,
+ * width or height 0, width * height above 2^26.  UNSUPPORTED: width above 32768 (a row's total must fit 32 bits).
+ * The setting: mode NONE (the default) or MAP, reserved words 0; an unknown mode or a non-zero reserved word is
+ * INVALID_ARG and the setting stays.  The call joins a frame in flight, holds for later renders and may come before
+ * or after the sky.  While the mode is MAP and the context's sky is a MAP, the context holds the map's distribution,
+ * built on its device from the texels resident there (equal to octpt_build_sky_distribution's integer for integer):
+ * built by whichever of the two calls comes second, rebuilt by a new map, dropped by octpt_clear_sky, a sky of another
+ * mode or the mode NONE.  scale and yaw do not enter it.  When the build itself fails (OOM, DEVICE) the call that
+ * asked for it returns that status: octpt_set_sky has then installed the new sky, octpt_set_sky_sampling keeps its
+ * previous mode, and the context holds no distribution -- renders follow the sky unsampled until a later call builds one.
+ * The estimator (sync, device, async, tile-list, adaptive and final renders, every camera form): at every diffuse
+ * reflection a texel is picked from an RNG stream of its own (no draw of the path changes), a direction d inside it,
+ * and, when d lies above the surface, one shadow segment is traced from hit + n * OFFSET along d (counted like the
+ * sun's; any reported hit blocks it); when it leaves the world, L += T_before * albedo * sky_radiance(d) *
+ * (d.n / pi) / pdf.  The bounce drawn at that reflection adds no base sky colour when its own segment leaves the world
+ * (the sun's terms add as ever); a camera ray, a specular chain and a bounce that passed a transparent surface see the
+ * map as before.  With sun sampling the sky segment runs first, then the sun's, then the bounce.
+ * Inert, bit for bit the unsampled render through the instances it takes today: MAP sampling under a DEFAULT, COLOR
+ * or GRADIENT sky and under an all-black map.  The preview and the guide buffers ignore the setting.
+ * UNSUPPORTED (the setting stays; a refused render leaves the caller's buffers untouched): MAP on a multi-device
+ * context; MAP while emitter sampling is ONE, and octpt_set_emitter_sampling(ONE) while the mode is MAP (whichever call
+ * comes second; and the render call); a render with OCTPT_RENDER_MEGAKERNEL while the mode is MAP; MAP while the
+ * resident map is wider than 32768.  A map wider than that set while the mode is MAP is accepted and renders
+ * unsampled. */
+#define OCTPT_SKY_SAMPLING_NONE 0u /* the state of a new context */
+#define OCTPT_SKY_SAMPLING_MAP 1u
+typedef struct octpt_sky_sampling {
+    uint32_t mode;
+    uint32_t reserved[7]; /* 0 */
+} octpt_sky_sampling;
+octpt_status octpt_set_sky_sampling(octpt_ctx *ctx, const octpt_sky_sampling *sampling);
+octpt_status octpt_get_sky_sampling(const octpt_ctx *ctx, octpt_sky_sampling *sampling);
+octpt_status octpt_build_sky_distribution(const float *texels, uint32_t width, uint32_t height, uint64_t *row_cdf,
+                                          uint32_t *col_cdf);
+/* The context's distribution, copied back from its device in count-then-fill form (as octpt_emitter_grid_arrays):
+ * width and height are always received (0 when the context holds none -- sampling off, no MAP, or a dropped one -- and
+ * on an error; nothing is written then and the call is OK).  With both pointers NULL the call only counts.  Otherwise
+ * both must be set with capacities (in elements) of at least height and width * height, else nothing is written and
+ * the call is INVALID_ARG.  build_ms: the device's time for the last build. */
+typedef struct octpt_sky_distribution_arrays {
+    uint64_t *row_cdf;
+    uint64_t row_cdf_capacity;
+    uint32_t *col_cdf;
+    uint64_t col_cdf_capacity;
+    uint32_t width, height;
+    float build_ms;
+    uint32_t reserved;
+} octpt_sky_distribution_arrays;
+octpt_status octpt_sky_distribution(octpt_ctx *ctx, octpt_sky_distribution_arrays *out);
+/* The sample of n tuples of four draws u[4 * i .. 4 * i + 4) in [0, 1), as the estimator takes it from its stream
+ * (csrc/octpt_sky_sample.h): row t = min((uint64)(u0 * (float)total), total - 1), the first y with t < row_cdf[y];
+ * column s = min((uint32)(u1 * (float)rowsum), rowsum - 1), the first x with s < col_cdf[y * width + x]; u = (x + u2) /
+ * width, v = (y + u3) / height, theta = pi v, lon = 2 pi (u - 0.5) - yaw brought into [-pi, pi]; d = (sin theta cos
+ * lon, cos theta, sin theta sin lon); pdf = ((float)q / (float)total) * ((float)width * (float)height) / (2 pi^2 sin
+ * theta) by solid angle.  out[8 * i ..]: d.xyz, pdf, then four 32-bit integers stored by bit pattern in the float
+ * slots: x, y, q and 1 (a sample) or 0 (none -- total 0, sin theta <= 0 or a pdf not finite and positive -- with d and
+ * pdf 0).  octpt_sky_sample is host-only: dist holds filled arrays of a width x height distribution, and of sky the
+ * fields width, height and yaw are read (mode must be MAP).  octpt_sky_sample_device runs a kernel of the same text
+ * over the context's distribution and sky (device buffers, on `hip_stream`; INVALID_ARG when the context holds no
+ * distribution).  The two agree bit for bit. */
+octpt_status octpt_sky_sample(const octpt_sky_distribution_arrays *dist, const octpt_sky *sky, uint32_t n,
+                              const float *u, float *out);
+octpt_status octpt_sky_sample_device(octpt_ctx *ctx, const float *d_u, uint32_t n, float *d_out, void *hip_stream);
+
 /* Synchronous render into host memory.  accum_rgba: width*height*4 floats (or the shard's
  * compact tiles), in/out running mean, initialise to F32Color::BLACK (0,0,0,1).
  * out_rgba8 (nullable): tone-mapped U8Color image (colors/mod.rs:408-420) of accum. */

@@ -237,6 +237,21 @@ class SkyDesc(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+SKY_SAMPLING_NONE, SKY_SAMPLING_MAP = 0, 1  # OCTPT_SKY_SAMPLING_* 
+
+
+class SkySampling(C.Structure):
+    """octpt_sky_sampling (octpt_set_sky_sampling)."""
+    _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class SkyDistributionArrays(C.Structure):
+    """octpt_sky_distribution_arrays: the sky map's distribution, count-then-fill."""
+    _fields_ = [("row_cdf", C.c_void_p), ("row_cdf_capacity", C.c_uint64), ("col_cdf", C.c_void_p),
+                ("col_cdf_capacity", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("build_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp_start", C.c_uint32), ("spp_count", C.c_uint32),
                 ("max_depth", C.c_uint32), ("branch_count", C.c_uint32), ("seed", C.c_uint32),
@@ -386,6 +401,12 @@ SIGNATURES = {
     "octpt_sky_radiance_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "octpt_sky_radiance_ctx": (_i32, [_vp, _vp, _u32, _vp]),
     "octpt_sky_map_position": (_i32, [C.POINTER(SkyDesc), _vp, _u32, _vp]),
+    "octpt_set_sky_sampling": (_i32, [_vp, C.POINTER(SkySampling)]),
+    "octpt_get_sky_sampling": (_i32, [_vp, C.POINTER(SkySampling)]),
+    "octpt_build_sky_distribution": (_i32, [_vp, _u32, _u32, _vp, _vp]),
+    "octpt_sky_distribution": (_i32, [_vp, C.POINTER(SkyDistributionArrays)]),
+    "octpt_sky_sample": (_i32, [C.POINTER(SkyDistributionArrays), C.POINTER(SkyDesc), _u32, _vp, _vp]),
+    "octpt_sky_sample_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "octpt_render": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp]),
     "octpt_render_device": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, _vp]),
     "octpt_render_async": (_i32, [_vp, C.POINTER(RenderParams), _vp, _vp, C.POINTER(_vp)]),

@@ -543,6 +543,13 @@ octpt_status octpt::make_render(octpt_ctx *ctx, const octpt_render_params *p, De
     // a sky other than DEFAULT (C42) has wavefront instances only
     if (ctx->sky.mode != kSkyDefault && (p->flags & OCTPT_RENDER_MEGAKERNEL) && !(p->flags & OCTPT_RENDER_PREVIEW))
         return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a sky is set (octpt_set_sky): it runs on the wavefront path only");
+    // sky sampling (C43) has wavefront instances only, and none together with emitter sampling
+    if (ctx->sky_sampling == OCTPT_SKY_SAMPLING_MAP && !(p->flags & OCTPT_RENDER_PREVIEW)) {
+        if (p->flags & OCTPT_RENDER_MEGAKERNEL)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "sky sampling is on (octpt_set_sky_sampling): it runs on the wavefront path only");
+        if (ctx->emit_strategy == OCTPT_EMITTERS_ONE)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "sky sampling together with emitter sampling ONE (DESIGN.md C43)");
+    }
     if (ctx->emit_strategy == OCTPT_EMITTERS_ONE && !(p->flags & OCTPT_RENDER_PREVIEW)) {  // C38
         const octpt_ctx *gc = ctx->sub.empty() ? ctx : ctx->sub[0];  // a multi-device context: its entries hold the scene
         if (!gc->S.has_blocks)
@@ -834,6 +841,14 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
     // shade and the drain are the sky instances and the chunks keep the general path state
     const Sky sky_rec = ctx->sky;
     const Sky *sky = sky_rec.mode != kSkyDefault ? &sky_rec : nullptr;
+    // sky sampling (C43): on, the sky a MAP and its distribution's total not 0 -- shade and the drain are the
+    // sky-sampling instances then, which read the distribution behind the sky record; every other case renders through
+    // the instances it takes without the setting
+    const SkyDist dist_rec{ctx->sky_dist.row_cdf, ctx->sky_dist.col_cdf, ctx->sky_dist.total};
+    const SkyDist *dist = (sky && sky_rec.mode == kSkyMap && ctx->sky_sampling == OCTPT_SKY_SAMPLING_MAP && !emit &&
+                           ctx->sky_dist.row_cdf && ctx->sky_dist.total != 0ull)
+                              ? &dist_rec
+                              : nullptr;
     DevScene Se = ctx->S;  // what shade and the drain take
     if (emit) {
         const DeviceEmitterGrid &g = ctx->emit_grid;
@@ -867,7 +882,8 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             return fail(ctx, OCTPT_ERR_UNSUPPORTED, "a branch-schedule pass exceeds the 2^31-item chunk limit");
         OomPart part = kOomNone;
         st = ensure_wave(ctx, (size_t)std::min<uint64_t>(ctx->pool_cap, chunk_max), chunk_max,
-                         ctx->S.sun.sun_sampling != 0, ctx->S.has_blocks != 0, &part, emit);
+                         ctx->S.sun.sun_sampling != 0, ctx->S.has_blocks != 0, &part,
+                         emit || dist);  // (the sky segment rides the emitter segment's six planes)
         if (st == OCTPT_OK) break;
         if (st != OCTPT_ERR_OOM) return st;
         // out of device memory past the queues: a smaller chunk (colour records) or pool (planes), kept
@@ -1034,7 +1050,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
             if ((st = ktimer_end(ctx, s, 0, ev)) != OCTPT_OK) return st;
             if ((st = ktimer_begin(ctx, s, ev)) != OCTPT_OK) return st;
             HIP_TRY(ctx, launch_wf_shade(Se, C, Rc, B, q, chunk_items, it == 0u ? (cam_rec ? 2u : 1u) : 0u,
-                                         regen, grid_shade, ctx->d_stats, s, emit, sky));
+                                         regen, grid_shade, ctx->d_stats, s, emit, sky, dist));
             if ((st = ktimer_end(ctx, s, 1, ev)) != OCTPT_OK) return st;
             // snapshot of the queue iteration `it` produced; the host checks the snapshot of
             // iteration it - kLookahead, so the GPU always has kLookahead iterations queued (an
@@ -1066,7 +1082,7 @@ octpt_status enqueue_wavefront(octpt_ctx *ctx, const DevRender &R, float4 *d_acc
                     if (exhausted) {
                         // one path per wave (wf_drain_kernel), four waves per block
                         const int grid = (int)std::min<uint64_t>((queued + 3) / 4 + 1, (uint64_t)ctx->num_cu * 16u);
-                        HIP_TRY(ctx, launch_wf_drain(Se, Rc, B, q ^ 1u, grid, ctx->d_stats, s, emit, sky));
+                        HIP_TRY(ctx, launch_wf_drain(Se, Rc, B, q ^ 1u, grid, ctx->d_stats, s, emit, sky, dist));
                         break;
                     }
                 }
@@ -1622,6 +1638,8 @@ void octpt_destroy(octpt_ctx *ctx) {
     free_wave(ctx);
     if (ctx->d_emit_hdr) (void)hipFree(ctx->d_emit_hdr);
     if (ctx->sky_map) (void)hipFree(ctx->sky_map);
+    if (ctx->sky_dist.row_cdf) (void)hipFree(ctx->sky_dist.row_cdf);
+    if (ctx->sky_dist.col_cdf) (void)hipFree(ctx->sky_dist.col_cdf);
     ctx->build_scratch.release();
     if (ctx->h_count) (void)hipHostFree(ctx->h_count);
     for (auto &ev : ctx->count_ev)
@@ -1874,6 +1892,23 @@ octpt_status octpt_get_ray_source(const octpt_ctx *ctx, octpt_ray_source *r) {
 // copied into a buffer of the context's own and sanitised there (sky_sanitise), and the call returns with the copy made,
 // so the caller may free its texels.
 namespace {
+// The distribution's lifetime (C43): the context holds one exactly while sampling is MAP and the sky a MAP no wider than
+// kSkySampleMaxWidth.  Whatever it held is dropped first (an earlier render on any stream may still read it).
+octpt_status refresh_sky_distribution(octpt_ctx *ctx) {
+    if (ctx->sky_dist.row_cdf || ctx->sky_dist.col_cdf) {
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        if (ctx->sky_dist.row_cdf) (void)hipFree(ctx->sky_dist.row_cdf);
+        if (ctx->sky_dist.col_cdf) (void)hipFree(ctx->sky_dist.col_cdf);
+    }
+    ctx->sky_dist = DeviceSkyDist{};
+    if (ctx->sky_sampling != OCTPT_SKY_SAMPLING_MAP || ctx->sky.mode != kSkyMap || ctx->sky.width > kSkySampleMaxWidth)
+        return OCTPT_OK;
+    std::vector<float> row(ctx->sky.height);
+    for (uint32_t y = 0; y < ctx->sky.height; ++y) row[y] = sky_row_factor(y, ctx->sky.height);
+    HIP_TRY(ctx, build_sky_distribution_gpu(ctx->stream, ctx->sky, row.data(), ctx->sky_dist));
+    return OCTPT_OK;
+}
+
 octpt_status check_sky(octpt_ctx *ctx, const octpt_sky *k, bool texels) {
     if (!k) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky NULL");
     for (uint32_t w : k->reserved)
@@ -1934,7 +1969,11 @@ octpt_status octpt_set_sky_device(octpt_ctx *ctx, const octpt_sky *k, const floa
         ctx->sky = s;
         ctx->sky_pub = *k;
         if (k->mode == OCTPT_SKY_DEFAULT) ctx->sky_pub = octpt_sky{};
-        return OCTPT_OK;
+        // sky sampling (C43): a new map rebuilds the distribution, any other sky drops it; a sky that keeps the map's
+        // texels out of it (scale and yaw do not enter the distribution) never comes this way -- every MAP call copies.
+        // A build that fails (out of device memory, a device error) is this call's status, with the new sky in force
+        // and no distribution held: renders follow the sky unsampled until a later call builds one
+        return refresh_sky_distribution(ctx);
     });
 }
 
@@ -1993,6 +2032,85 @@ octpt_status octpt_sky_radiance_ctx(octpt_ctx *ctx, const float *dirs, uint32_t 
         octpt_status st = OCTPT_OK;
         if (hs.ok() && (st = octpt_sky_radiance_device(ctx, d_dirs, n, d_out, ctx->stream)) != OCTPT_OK) return st;
         if (hs.finish() != hipSuccess) return hip_fail(ctx, hs.error(), "sky_radiance");
+        return OCTPT_OK;
+    });
+}
+
+// Sky sampling (C43): the setting, the distribution's read-back and the sample's device form.  Every check comes before
+// the first write, so a refused call leaves the previous setting in force.
+octpt_status octpt_set_sky_sampling(octpt_ctx *ctx, const octpt_sky_sampling *p) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!p) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky sampling NULL");
+    for (uint32_t w : p->reserved)
+        if (w != 0u) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky sampling: a reserved word is not zero");
+    if (p->mode > OCTPT_SKY_SAMPLING_MAP) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky sampling: unknown mode");
+    if (p->mode == OCTPT_SKY_SAMPLING_MAP) {
+        if (is_multi(ctx)) return fail(ctx, OCTPT_ERR_UNSUPPORTED, "sky sampling: not on a multi-device context");
+        if (ctx->emit_strategy == OCTPT_EMITTERS_ONE)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "sky sampling together with emitter sampling ONE (DESIGN.md C43)");
+    }
+    return guarded(ctx, "set_sky_sampling", [&]() -> octpt_status {
+        join_inflight(ctx);  // a frame in flight keeps the setting its call was made with
+        if (p->mode == OCTPT_SKY_SAMPLING_MAP && ctx->sky.mode == kSkyMap && ctx->sky.width > kSkySampleMaxWidth)
+            return fail(ctx, OCTPT_ERR_UNSUPPORTED, "sky sampling: the map is wider than 32768 texels");
+        if (p->mode == ctx->sky_sampling) return OCTPT_OK;
+        if (is_multi(ctx)) {  // (NONE: nothing to drop)
+            ctx->sky_sampling = p->mode;
+            return OCTPT_OK;
+        }
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const uint32_t old = ctx->sky_sampling;
+        ctx->sky_sampling = p->mode;
+        const octpt_status st = refresh_sky_distribution(ctx);
+        if (st != OCTPT_OK) ctx->sky_sampling = old;  // (the distribution is dropped either way: NONE holds none)
+        return st;
+    });
+}
+
+octpt_status octpt_get_sky_sampling(const octpt_ctx *ctx, octpt_sky_sampling *p) {
+    if (!ctx || !p) return OCTPT_ERR_INVALID_ARG;
+    *p = octpt_sky_sampling{};
+    p->mode = ctx->sky_sampling;
+    return OCTPT_OK;
+}
+
+octpt_status octpt_sky_distribution(octpt_ctx *ctx, octpt_sky_distribution_arrays *out) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (!out) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky distribution arrays NULL");
+    out->width = out->height = 0u;
+    out->build_ms = 0.0f;
+    return guarded(ctx, "sky_distribution", [&]() -> octpt_status {
+        join_inflight(ctx);
+        const DeviceSkyDist &g = ctx->sky_dist;
+        if (is_multi(ctx) || !g.row_cdf) return OCTPT_OK;  // the context holds none: the counts are 0
+        if (!out->row_cdf != !out->col_cdf)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky distribution: set both arrays, or neither to count");
+        if (out->row_cdf && (out->row_cdf_capacity < g.height || out->col_cdf_capacity < (uint64_t)g.width * g.height))
+            return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky distribution: an array's capacity is below its count");
+        if (out->row_cdf) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipMemcpy(out->row_cdf, g.row_cdf, (size_t)g.height * 8u, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(out->col_cdf, g.col_cdf, (size_t)g.width * g.height * 4u, hipMemcpyDeviceToHost));
+        }
+        out->width = g.width;
+        out->height = g.height;
+        out->build_ms = g.build_ms;
+        return OCTPT_OK;
+    });
+}
+
+octpt_status octpt_sky_sample_device(octpt_ctx *ctx, const float *d_u, uint32_t n, float *d_out, void *stream) {
+    if (!ctx) return OCTPT_ERR_INVALID_ARG;
+    if (n != 0u && (!d_u || !d_out)) return fail(ctx, OCTPT_ERR_INVALID_ARG, "sky_sample: NULL buffer");
+    return guarded(ctx, "sky_sample", [&]() -> octpt_status {
+        join_inflight(ctx);
+        if (is_multi(ctx) || !ctx->sky_dist.row_cdf)
+            return fail(ctx, OCTPT_ERR_INVALID_ARG,
+                        "the context holds no sky distribution (sky sampling MAP and a MAP sky build it)");
+        if (n == 0u) return OCTPT_OK;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const SkyDist D{ctx->sky_dist.row_cdf, ctx->sky_dist.col_cdf, ctx->sky_dist.total};
+        HIP_TRY(ctx, launch_sky_sample(ctx->sky, D, d_u, n, d_out, static_cast<hipStream_t>(stream)));
         return OCTPT_OK;
     });
 }
@@ -2339,6 +2457,8 @@ octpt_status octpt_set_emitter_sampling(octpt_ctx *ctx, const octpt_emitter_para
     if (p->grid_size == 0u || (p->grid_size & (p->grid_size - 1u)) || p->grid_size > (1u << kMaxDepth))
         return fail(ctx, OCTPT_ERR_INVALID_ARG, "emitter grid_size must be a power of two, 1 .. 2^21");
     join_inflight(ctx);  // a frame in flight keeps the setting its call was made with
+    if (p->strategy == OCTPT_EMITTERS_ONE && ctx->sky_sampling == OCTPT_SKY_SAMPLING_MAP)  // C43
+        return fail(ctx, OCTPT_ERR_UNSUPPORTED, "emitter sampling ONE together with sky sampling (DESIGN.md C43)");
     if (p->strategy == OCTPT_EMITTERS_ONE && ctx->has_scene) {
         const octpt_ctx *sc = is_multi(ctx) ? ctx->sub[0] : ctx;
         if (!sc->S.has_blocks)

@@ -1478,4 +1478,144 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
     return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------
+// The sky map's distribution (csrc/octpt_sky_sample.h is its definition and the host builder's text):
+//   weight    one thread per texel: the 3 x 3 maximum of the luminance times the row's factor       -> w
+//   max       hipcub::DeviceReduce::Max over w (a maximum is the same in every order)               -> wmax
+//   quantise  one thread per texel: q = sky_quantise(w, wmax), an integer                           -> q
+//   row scan  one block per row: the inclusive sum of q along the row, 256 texels per step with the
+//             block's running total carried over                                                    -> col_cdf
+//   marginal  the rows' totals (col_cdf's last column) widened to 64 bits, then their inclusive sum  -> row_cdf
+// Positions and sums come from scans and reductions alone; every store is a plain vector store; the sums are integer,
+// so no order of addition shows in them.
+namespace {
+
+__global__ __launch_bounds__(kBuildBlock) void sky_weight_kernel(Sky K, const float *__restrict__ row,
+                                                                 float *__restrict__ w, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t y = (uint32_t)(i / K.width), x = (uint32_t)(i - (uint64_t)y * K.width);
+    w[i] = sky_weight(K, x, y, row[y]);
+}
+
+__global__ __launch_bounds__(kBuildBlock) void sky_quantise_kernel(const float *__restrict__ w,
+                                                                   const float *__restrict__ wmax,
+                                                                   uint32_t *__restrict__ q, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+    if (i >= n) return;
+    q[i] = sky_quantise(w[i], *wmax);
+}
+
+// in place: q of row blockIdx.x becomes its inclusive sum (a row's total is at most 32768 * 65536 = 2^31)
+__global__ __launch_bounds__(kBuildBlock) void sky_row_scan_kernel(uint32_t *__restrict__ q, uint32_t W) {
+    using Scan = hipcub::BlockScan<uint32_t, kBuildBlock>;
+    __shared__ typename Scan::TempStorage tmp;
+    uint32_t *row = q + (size_t)blockIdx.x * W;
+    uint32_t carry = 0u;
+    for (uint32_t x0 = 0u; x0 < W; x0 += kBuildBlock) {  // (block-uniform trip count)
+        const uint32_t x = x0 + threadIdx.x;
+        const uint32_t v = x < W ? row[x] : 0u;
+        uint32_t incl, sum;
+        Scan(tmp).InclusiveSum(v, incl, sum);
+        if (x < W) row[x] = carry + incl;
+        carry += sum;
+        __syncthreads();  // tmp is used again
+    }
+}
+
+__global__ __launch_bounds__(kBuildBlock) void sky_row_totals_kernel(const uint32_t *__restrict__ col_cdf, uint32_t W,
+                                                                     uint32_t H, uint64_t *__restrict__ totals) {
+    const uint32_t y = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (y >= H) return;
+    totals[y] = col_cdf[(size_t)y * W + (W - 1u)];
+}
+
+__global__ __launch_bounds__(kBuildBlock) void sky_sample_kernel(Sky K, SkyDist D, const float *__restrict__ u,
+                                                                 uint32_t n, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * kBuildBlock + threadIdx.x;
+    if (i >= n) return;
+    const float uu[4] = {u[4u * (size_t)i], u[4u * (size_t)i + 1u], u[4u * (size_t)i + 2u], u[4u * (size_t)i + 3u]};
+    SkyShot s;
+    const bool ok = sky_sample_draws(D, K, uu, s);
+    float o[8];
+    sky_sample_pack(s, ok, o);
+    for (int k = 0; k < 8; ++k) out[8u * (size_t)i + k] = o[k];
+}
+
+}  // namespace
+
+hipError_t build_sky_distribution_gpu(hipStream_t stream, const Sky &sky, const float *row, DeviceSkyDist &out) {
+    out = DeviceSkyDist{};
+    const uint32_t W = sky.width, H = sky.height;
+    const uint64_t n = (uint64_t)W * H;
+    float *d_row = nullptr, *d_w = nullptr, *d_max = nullptr;
+    uint64_t *d_tot = nullptr, *d_rowcdf = nullptr;
+    uint32_t *d_col = nullptr;
+    char *d_tmp = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto drop = [&](hipError_t e) {
+        for (void *p : {(void *)d_row, (void *)d_w, (void *)d_max, (void *)d_tot, (void *)d_tmp})
+            if (p) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (e != hipSuccess) {
+            if (d_col) (void)hipFree(d_col);
+            if (d_rowcdf) (void)hipFree(d_rowcdf);
+        }
+        return e;
+    };
+#define STRY(expr)                             \
+    do {                                       \
+        const hipError_t _e = (expr);          \
+        if (_e != hipSuccess) return drop(_e); \
+    } while (0)
+    STRY(hipMalloc(&d_row, (size_t)H * sizeof(float)));
+    STRY(hipMalloc(&d_w, n * sizeof(float)));
+    STRY(hipMalloc(&d_max, sizeof(float)));
+    STRY(hipMalloc(&d_tot, (size_t)H * sizeof(uint64_t)));
+    STRY(hipMalloc(&d_rowcdf, (size_t)H * sizeof(uint64_t)));
+    STRY(hipMalloc(&d_col, n * sizeof(uint32_t)));
+    size_t max_bytes = 0, scan_bytes = 0;
+    STRY(hipcub::DeviceReduce::Max(nullptr, max_bytes, d_w, d_max, (int)n, stream));
+    STRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, d_tot, d_rowcdf, (int)H, stream));
+    const size_t tmp_bytes = std::max<size_t>(std::max(max_bytes, scan_bytes), 1);
+    STRY(hipMalloc(&d_tmp, tmp_bytes));
+    STRY(hipEventCreate(&e0));
+    STRY(hipEventCreate(&e1));
+    STRY(hipMemcpyAsync(d_row, row, (size_t)H * sizeof(float), hipMemcpyHostToDevice, stream));
+    STRY(hipEventRecord(e0, stream));
+    hipLaunchKernelGGL(sky_weight_kernel, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, sky, d_row, d_w, n);
+    STRY(hipGetLastError());
+    size_t bytes = tmp_bytes;
+    STRY(hipcub::DeviceReduce::Max(d_tmp, bytes, d_w, d_max, (int)n, stream));
+    hipLaunchKernelGGL(sky_quantise_kernel, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, d_w, d_max, d_col, n);
+    STRY(hipGetLastError());
+    hipLaunchKernelGGL(sky_row_scan_kernel, dim3(H), dim3(kBuildBlock), 0, stream, d_col, W);
+    STRY(hipGetLastError());
+    hipLaunchKernelGGL(sky_row_totals_kernel, dim3(blocks(H)), dim3(kBuildBlock), 0, stream, d_col, W, H, d_tot);
+    STRY(hipGetLastError());
+    bytes = tmp_bytes;
+    STRY(hipcub::DeviceScan::InclusiveSum(d_tmp, bytes, d_tot, d_rowcdf, (int)H, stream));
+    STRY(hipEventRecord(e1, stream));
+    uint64_t total = 0;
+    STRY(hipMemcpyAsync(&total, d_rowcdf + (H - 1u), sizeof total, hipMemcpyDeviceToHost, stream));
+    STRY(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    STRY(hipEventElapsedTime(&ms, e0, e1));
+#undef STRY
+    out.row_cdf = d_rowcdf;
+    out.col_cdf = d_col;
+    out.total = total;
+    out.width = W;
+    out.height = H;
+    out.build_ms = ms;
+    return drop(hipSuccess);
+}
+
+hipError_t launch_sky_sample(const Sky &sky, const SkyDist &dist, const float *u, uint32_t n, float *out,
+                             hipStream_t stream) {
+    hipLaunchKernelGGL(sky_sample_kernel, dim3(blocks(n)), dim3(kBuildBlock), 0, stream, sky, dist, u, n, out);
+    return hipGetLastError();
+}
+
 }  // namespace octpt

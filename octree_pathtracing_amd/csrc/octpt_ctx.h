@@ -84,6 +84,10 @@ struct octpt_ctx {
     octpt::Sky sky{};
     float *sky_map = nullptr;
     octpt_sky sky_pub{};  // the setting as octpt_get_sky returns it
+    // sky sampling (C43, octpt_set_sky_sampling): the mode, and the map's distribution on the device while the mode is
+    // MAP and the sky a MAP no wider than 32768 (row_cdf NULL else; refresh_sky_distribution keeps the rule)
+    uint32_t sky_sampling = OCTPT_SKY_SAMPLING_NONE;
+    octpt::DeviceSkyDist sky_dist{};
     // per-context device state
     uint32_t *d_counters = nullptr;  // ring of work counters, one per launch
     // branch schedule of the current render (C20): host copy + grow-only device table

@@ -20,6 +20,7 @@
 #include "octpt_mask.h"
 #include "octpt_reproject.h"
 #include "octpt_sky.h"
+#include "octpt_sky_sample.h"
 
 namespace {
 constexpr uint32_t kMaxScale = 23u;   // OCTREE_MAX_SCALE, octree_traversal.rs:14
@@ -362,6 +363,74 @@ extern "C" octpt_status octpt_sky_map_position(const octpt_sky *sky, const float
     K.height = sky->height;
     for (uint32_t i = 0; i < n; ++i)
         octpt::sky_map_position(K, dirs + 3u * (size_t)i, out_xy[2u * (size_t)i], out_xy[2u * (size_t)i + 1u]);
+    return OCTPT_OK;
+}
+
+// The sky map's distribution: csrc/octpt_sky_sample.h's weight and quantum over a sanitised host copy of
+// the map, summed in integers.  The definition the device builder (octpt_build.hip) is compared with.
+extern "C" octpt_status octpt_build_sky_distribution(const float *texels, uint32_t width, uint32_t height,
+                                                     uint64_t *row_cdf, uint32_t *col_cdf) {
+    if (!texels || !row_cdf || !col_cdf) return OCTPT_ERR_INVALID_ARG;
+    if (width == 0u || height == 0u || (uint64_t)width * height > octpt::kSkyMaxTexels) return OCTPT_ERR_INVALID_ARG;
+    if (width > octpt::kSkySampleMaxWidth) return OCTPT_ERR_UNSUPPORTED;
+    const size_t n = (size_t)width * height;
+    std::vector<float> map, w;
+    try {
+        map.resize(n * 4u);
+        w.resize(n);
+    } catch (const std::bad_alloc &) {
+        return OCTPT_ERR_OOM;
+    }
+    for (size_t i = 0; i < n * 4u; ++i) map[i] = octpt::sky_sanitise(texels[i]);
+    octpt::Sky K{};
+    K.mode = octpt::kSkyMap;
+    K.width = width;
+    K.height = height;
+    K.texels = map.data();
+    float wmax = 0.0f;
+    for (uint32_t y = 0; y < height; ++y) {
+        const float row = octpt::sky_row_factor(y, height);
+        for (uint32_t x = 0; x < width; ++x) {
+            const float v = octpt::sky_weight(K, x, y, row);
+            w[(size_t)y * width + x] = v;
+            wmax = v > wmax ? v : wmax;
+        }
+    }
+    uint64_t total = 0;
+    for (uint32_t y = 0; y < height; ++y) {
+        uint32_t sum = 0;
+        for (uint32_t x = 0; x < width; ++x) {
+            sum += octpt::sky_quantise(w[(size_t)y * width + x], wmax);
+            col_cdf[(size_t)y * width + x] = sum;
+        }
+        total += sum;
+        row_cdf[y] = total;
+    }
+    return OCTPT_OK;
+}
+
+// ... and its sample for n tuples of draws: sky_sample_draws, the text the sky-sampling instances of shade compile
+extern "C" octpt_status octpt_sky_sample(const octpt_sky_distribution_arrays *dist, const octpt_sky *sky, uint32_t n,
+                                         const float *u, float *out) {
+    if (!dist || !sky || (n != 0u && (!u || !out))) return OCTPT_ERR_INVALID_ARG;
+    if (sky->mode != OCTPT_SKY_MAP || !dist->row_cdf || !dist->col_cdf) return OCTPT_ERR_INVALID_ARG;
+    if (!octpt::sky_fields_valid(sky->mode, sky->scale, sky->yaw, sky->width, sky->height, true))
+        return OCTPT_ERR_INVALID_ARG;
+    if (sky->width > octpt::kSkySampleMaxWidth) return OCTPT_ERR_UNSUPPORTED;
+    if (dist->width != sky->width || dist->height != sky->height || dist->row_cdf_capacity < sky->height ||
+        dist->col_cdf_capacity < (uint64_t)sky->width * sky->height)
+        return OCTPT_ERR_INVALID_ARG;
+    octpt::Sky K{};
+    K.mode = sky->mode;
+    K.yaw = sky->yaw;
+    K.width = sky->width;
+    K.height = sky->height;
+    const octpt::SkyDist D{dist->row_cdf, dist->col_cdf, dist->row_cdf[sky->height - 1u]};
+    for (uint32_t i = 0; i < n; ++i) {
+        octpt::SkyShot s;
+        const bool ok = octpt::sky_sample_draws(D, K, u + 4u * (size_t)i, s);
+        octpt::sky_sample_pack(s, ok, out + 8u * (size_t)i);
+    }
     return OCTPT_OK;
 }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/octpt.h"
 #include "octpt_sky.h"
+#include "octpt_sky_sample.h"
 
 namespace octpt {
 
@@ -131,6 +132,11 @@ struct DevScene {
 // as they always did; no struct of theirs changes.
 struct SkyScene : DevScene {
     Sky sky;
+};
+// ... and what a sky-sampling instance (C43; octpt_kernels_skysample.hip) takes: the same, the map's distribution
+// (device arrays, csrc/octpt_sky_sample.h) behind it.  SkyScene is what it was.
+struct SkySampleScene : SkyScene {
+    SkyDist dist;
 };
 
 struct DevCamera {
@@ -425,6 +431,10 @@ const void *sky_emit_shade_kernel(bool nee, bool lds, int mode);
 const void *sky_emit_drain_kernel(bool nee);
 // octpt_set_sky's pass over a map (sky_sanitise on each of n floats, in place) and octpt_sky_radiance_device's kernel
 // (sky_radiance for n directions of three floats)
+// the sky-sampling instances (C43; octpt_kernels_skysample.hip, a module of its own), which launch_wf_shade and
+// launch_wf_drain take with `dist`: sky sampling on, the sky a MAP and the distribution's total not 0
+const void *skysample_shade_kernel(bool nee, bool lds, int mode);
+const void *skysample_drain_kernel(int prims, bool nee);
 hipError_t launch_sky_sanitise(float *texels, size_t n, hipStream_t stream);
 hipError_t launch_sky_radiance(const Sky &sky, const float *dirs, uint32_t n, float *out, hipStream_t stream);
 hipError_t launch_wf_seed(const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t n_seed,
@@ -435,7 +445,8 @@ hipError_t launch_wf_extend(const DevScene &S, const WaveBuffers &B, uint32_t q,
 // smaller than the chunk, finished paths regenerate their slots (the instance with regeneration)
 hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t q,
                            uint32_t chunk_items, uint32_t first, bool regen, int grid, unsigned long long *stats,
-                           hipStream_t stream, bool emit = false, const Sky *sky = nullptr);
+                           hipStream_t stream, bool emit = false, const Sky *sky = nullptr,
+                           const SkyDist *dist = nullptr);
 // the emitter instances (C38; octpt_kernels_emit.hip, a module of its own), which launch_wf_shade and launch_wf_drain
 // take with `emit`: S is then a block-value scene whose leaf_sph holds the device address of the render's EmitGrid
 // (csrc/octpt_emitter.h), and the pd planes number six
@@ -447,7 +458,8 @@ int shade_blocks_per_cu(const DevScene &S, int mode);
 bool shade_lds_tables(const DevScene &S);
 // the drain of a chunk's last queued rays (every chunk item claimed): one launch, paths finished in-lane
 hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuffers &B, uint32_t q, int grid,
-                           unsigned long long *stats, hipStream_t stream, bool emit = false, const Sky *sky = nullptr);
+                           unsigned long long *stats, hipStream_t stream, bool emit = false, const Sky *sky = nullptr,
+                           const SkyDist *dist = nullptr);
 // the host's snapshot of an iteration's counters: queue q's kSegs segment counts, then the kSegs item
 // counters, written by one 128-thread block into pinned host memory (enqueue_wavefront's steering)
 hipError_t launch_wf_snapshot(const WaveBuffers &B, uint32_t q, uint32_t *host_out, hipStream_t stream);
@@ -667,6 +679,23 @@ hipError_t build_emitter_grid_gpu(hipStream_t stream, BuildScratch &scratch, con
                                   const uint32_t *emissive, uint32_t grid_shift, DeviceEmitterGrid &out,
                                   octpt_status &refusal, const uint8_t *model_emissive = nullptr,
                                   uint32_t n_models = 0u);
+
+
+// The sky map's distribution on the device (C43, octpt_build.hip): the arrays of csrc/octpt_sky_sample.h built from the
+// map the context holds (sky.texels: sanitised device texels) -- a weight kernel, a max reduction, a quantise kernel,
+// one scan per row and the scan of the rows' totals -- equal to octpt_build_sky_distribution's integer for integer.
+// row: the host's table of sin(pi (y + 0.5) / H), height floats.  The arrays are the caller's to free.
+struct DeviceSkyDist {
+    uint64_t *row_cdf = nullptr;
+    uint32_t *col_cdf = nullptr;
+    uint64_t total = 0;
+    uint32_t width = 0, height = 0;
+    float build_ms = 0.0f;  // the device's time from the weight kernel to the marginal scan
+};
+hipError_t build_sky_distribution_gpu(hipStream_t stream, const Sky &sky, const float *row, DeviceSkyDist &out);
+// octpt_sky_sample_device's kernel: sky_sample_draws for n tuples of four draws, eight floats out each
+hipError_t launch_sky_sample(const Sky &sky, const SkyDist &dist, const float *u, uint32_t n, float *out,
+                             hipStream_t stream);
 
 }  // namespace octpt
 

@@ -20,6 +20,14 @@
 #include "octpt_math.h"
 #include "octpt_sky.h"
 #include "octpt_emitter.h"
+#if defined(OCTPT_SKYSAMPLE_TU)  // (octpt_kernels_skysample.hip alone, on top of OCTPT_SKY_TU: C43)
+#include "octpt_sky_sample.h"
+#endif
+// a module whose shade has a sampled light's shadow segment with a sun sample waiting behind it: the emitter modules
+// (C38) and the sky-sampling one (C43).  Never both: the two settings refuse each other.
+#if defined(OCTPT_EMIT_TU) || defined(OCTPT_SKYSAMPLE_TU)
+#define OCTPT_PEND_TU 1
+#endif
 #include "octpt_rcp.h"
 #include "octpt_reproject.h"
 #include "octpt_resolve_map.h"
@@ -159,7 +167,7 @@ struct PathState {
     float mult;
     v3 co, cd, cn;
     uint32_t clast, ccur;
-#if defined(OCTPT_EMIT_TU)
+#if defined(OCTPT_PEND_TU)
     // emitter sampling (C38), the emitter instances' module only (the struct stays what it is everywhere else): a shadow segment with att[3] < 0 is the emitter
     // segment (att[0..2] = T_before * albedo, mult = the shot's geometric factor, -att[3] = the cell list's length);
     // a sun sample drawn at the same hit waits behind it in (sd, so, smult) while sun_pend is set; emit_to_sun
@@ -167,6 +175,13 @@ struct PathState {
     bool sun_pend, emit_to_sun;
     v3 sd, so;  // the waiting sun sample's direction and origin (the hit point, or OFFSET behind the surface)
     float smult;
+#endif
+#if defined(OCTPT_SKYSAMPLE_TU)
+    // sky sampling (C43), its module only: a shadow segment with att[3] < 0 is the sky segment (att[0..2] = T_before *
+    // albedo, mult = e = (cosn / pi) / pdf; its direction is the sample's); a sun sample drawn at the same hit waits
+    // behind it in the fields above.  sky_nee: the path's last shade event was a diffuse reflection, where a sky
+    // sample was taken -- a miss of the segment that starts there adds no base colour (the sample covered it)
+    bool sky_nee;
 #endif
 };
 
@@ -1189,7 +1204,11 @@ __device__ inline int esvo_step(const DevScene &S, const TraceRay &ray, Esvo &E,
 // the shared functions pass on.  sky_base puts the base colour (csrc/octpt_sky.h) where sky_color starts from the
 // constant everywhere else; the sun's terms add on top as they always did.
 #if defined(OCTPT_SKY_TU)
+#if defined(OCTPT_SKYSAMPLE_TU)  // (C43: the map's distribution behind the sky record)
+using KernelScene = SkySampleScene;
+#else
 using KernelScene = SkyScene;
+#endif
 __device__ __forceinline__ void sky_base(const DevScene &S, v3 d, float out[3]) {
     const float dd[3] = {d.x, d.y, d.z};
     sky_radiance(static_cast<const SkyScene &>(S).sky, dd, out);
@@ -1402,6 +1421,9 @@ __device__ inline void new_path(const DevCamera &C, const DevRender &R, uint32_t
     ps.branch = 0u;
     ps.seg_base = 0u;
     ps.beam = 0.0f;
+#if defined(OCTPT_SKYSAMPLE_TU)
+    ps.sky_nee = false;
+#endif
 }
 
 // next_intersection prologue (path_tracer.rs:438-446) + Scene::hit direction guard
@@ -1543,6 +1565,98 @@ __device__ inline void emitter_segment_done(const DevScene &S, PathState &ray, b
 }
 #endif
 
+// Sky sampling: OCTPT_SKYSAMPLE_TU is defined by octpt_kernels_skysample.hip alone, which compiles this
+// text (with OCTPT_SKY_TU) for the sky-sampling instances of the general shade and the drain, as a module of its own;
+// everywhere else every line under it is absent.  Such an instance takes a SkySampleScene -- the SkyScene with the
+// distribution's device arrays behind it -- and is launched only for a MAP with a non-zero total.
+#if defined(OCTPT_SKYSAMPLE_TU)
+// The sky sample of a diffuse hit (csrc/octpt_sky_sample.h), taken before the bounce, at every diffuse reflection.
+// Where a sample exists the path is marked (sky_nee), so that the bounce's own miss adds no base colour -- also when
+// the sample lies behind the surface: it is a sample whose contribution is 0.  Without a sample (a pole, a pdf that is
+// not finite and positive) the mark stays clear and the bounce adds the sky as it does unsampled.  false when nothing
+// is to be traced (the caller goes on as without sampling).  Else the bounce -- and with sun
+// sampling the sun sample, in the reference's draw order -- is drawn now and waits, as emitter_shot has it, and the ray
+// becomes the sky's shadow segment: one next_intersection from p = hit + n * OFFSET along d with the surface's
+// self-hit key.
+template <bool kNee>
+__device__ inline bool sky_shot(const DevScene &S, const DevMaterial &m, PathState &ray, uint32_t key_rng) {
+    const SkySampleScene &SS = static_cast<const SkySampleScene &>(S);
+    const v3 n = ray.n;
+    SkyShot sh;
+    if (!sky_sample(SS.dist, SS.sky, key_rng, sh)) return false;
+    ray.sky_nee = true;
+    const v3 d = V(sh.d[0], sh.d[1], sh.d[2]);
+    const float cosn = vdot(d, n);
+    if (!(cosn > 0.0f)) return false;
+    v3 &T = ray.T;
+    const float c0 = ray.col[0], c1 = ray.col[1], c2 = ray.col[2];
+    ray.att[0] = T.x * c0;  // T_before * albedo
+    ray.att[1] = T.y * c1;
+    ray.att[2] = T.z * c2;
+    ray.att[3] = -1.0f;
+    ray.sun_pend = false;
+    const uint32_t scur = ray.prev;
+    const v3 p = vadd(ray.o, vscale(n, RAY_OFFSET));
+    if (kNee && S.sun.sun_sampling) {
+        const v3 sd = random_sun_direction(S.sun, ray.rng);
+        const bool front = vdot(sd, n) > 0.0f;
+        ray.sun_pend = front || ((m.flags & MAT_FLAG_SUBSURFACE) && rng_next(ray.rng) < S.sun.f_sub_surface);
+        ray.so = front ? ray.o : vadd(ray.o, vscale(n, -RAY_OFFSET));
+        ray.sd = sd;
+        ray.smult = fabsf(vdot(sd, n)) * S.sun.lum_a;
+        const float w = diffuse_reflection(S.sun, ray);
+        T = V(T.x * (c0 * w), T.y * (c1 * w), T.z * (c2 * w));
+    } else {
+        T = V(T.x * c0, T.y * c1, T.z * c2);
+        diffuse_reflection(S.sun, ray);
+    }
+    ray.co = ray.o;
+    ray.cd = ray.d;
+    ray.cn = n;
+    ray.clast = ray.last_prim;
+    ray.ccur = ray.cur;
+    ray.mult = sky_sample_scale(cosn, sh.pdf);
+    ray.shadow = true;
+    ray.o = p;
+    ray.d = d;
+    ray.n = n;
+    ray.cur = scur;
+    return true;
+}
+
+// ... and after that segment: any reported hit blocks it; when it left the world, the map's radiance in its direction
+// (the four taps come now, after the segment; nothing of them waited in the state) times e.  Then the waiting sun
+// sample's shadow segments start, or the waiting bounce resumes.
+template <bool kNee>
+__device__ inline void sky_segment_done(const DevScene &S, PathState &ray, bool hit) {
+    if (!hit) {
+        float rad[3];
+        sky_base(S, ray.d, rad);
+        const float e = ray.mult;
+        ray.L = V(ray.L.x + ray.att[0] * (rad[0] * e), ray.L.y + ray.att[1] * (rad[1] * e),
+                  ray.L.z + ray.att[2] * (rad[2] * e));
+    }
+    if (kNee && ray.sun_pend) {  // the sun sample drawn at the same hit: shade_segment's sun branch from `cast` on
+        ray.mult = ray.smult;
+        ray.att[0] = ray.att[1] = ray.att[2] = ray.att[3] = 1.0f;
+        ray.o = vadd(ray.so, vscale(ray.sd, RAY_OFFSET));
+        ray.d = ray.sd;
+        ray.n = ray.cn;
+        ray.last_prim = ray.clast;
+        ray.cur = ray.prev;
+        ray.sun_pend = false;
+        ray.emit_to_sun = true;
+        return;
+    }
+    ray.shadow = false;
+    ray.o = ray.co;
+    ray.d = ray.cd;
+    ray.n = ray.cn;
+    ray.last_prim = ray.clast;
+    ray.cur = ray.ccur;
+}
+#endif
+
 // path_tracer.rs:15-135 in forward-throughput form, from a finished segment to either the
 // next segment's ray (returns true) or the end of the path (returns false).  kNee: the scene may
 // sample the sun; shadow segments run between a diffuse hit and its bounce.
@@ -1557,6 +1671,12 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
         else shadow_segment_done(S, ray, hit);
         return true;
     }
+#elif defined(OCTPT_SKYSAMPLE_TU)
+    if (ray.shadow) {
+        if (ray.att[3] < 0.0f) sky_segment_done<kNee>(S, ray, hit);
+        else shadow_segment_done(S, ray, hit);
+        return true;
+    }
 #else
     if (kNee && ray.shadow) {
         shadow_segment_done(S, ray, hit);
@@ -1565,13 +1685,20 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
 #endif
     if (!hit) {
         float sky[3];
-#if defined(OCTPT_SKY_TU)
+#if defined(OCTPT_SKYSAMPLE_TU)
+        // a segment that starts at a diffuse reflection: the sky sample taken there covered the map (C43)
+        if (ray.sky_nee) sky[0] = sky[1] = sky[2] = 0.0f;
+        else sky_base(S, ray.d, sky);
+#elif defined(OCTPT_SKY_TU)
         sky_base(S, ray.d, sky);
 #endif
         sky_color(S.sun, ray, sky);
         ray.L = V(ray.L.x + ray.T.x * sky[0], ray.L.y + ray.T.y * sky[1], ray.L.z + ray.T.z * sky[2]);
         return false;
     }
+#if defined(OCTPT_SKYSAMPLE_TU)
+    ray.sky_nee = false;  // every other shade event clears the mark, the pass-through of C4 included
+#endif
     const DevMaterial m = S.mats[ray.cur];
     const float ior2 = S.mats[ray.prev].ior;
     const float specular = m.specular, diffuse = ray.col[3], absorb = ray.col[3];
@@ -1588,8 +1715,9 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
     }
     cnt.shade++;
     v3 &T = ray.T;
-#if defined(OCTPT_EMIT_TU)
+#if defined(OCTPT_PEND_TU)
     const uint32_t emit_rng = ray.rng;  // the emitter stream's key: the state before any draw of this hit (C38)
+                                        // (and the sky stream's, C43)
 #endif
     const float metal = m.metalness;
     const bool do_metal = metal > RAY_EPSILON && rng_next(ray.rng) < metal;
@@ -1615,6 +1743,9 @@ __device__ inline bool shade_segment(const DevScene &S, const DevRender &R, Path
         if (S.emitters && !(ray.depth == 1u && m.emittance > RAY_EPSILON)) {  // the reference's `else if`
             if (emitter_shot<kNee>(S, m, ray, emit_rng)) return true;
         }
+#endif
+#if defined(OCTPT_SKYSAMPLE_TU)
+        if (sky_shot<kNee>(S, m, ray, emit_rng)) return true;  // the sky sample of every diffuse reflection (C43)
 #endif
         if (kNee && S.sun.sun_sampling) {
             // do_diffuse_reflection's sun-sampling branch (path_tracer.rs:225-291).  Draw order:
@@ -2019,6 +2150,9 @@ __device__ __forceinline__ void pack_path(const PathState &ps, uint32_t item, fl
     b = make_float4(ps.L.y, ps.L.z, __uint_as_float(ps.rng), __uint_as_float(item));
     c = make_uint2(ps.cur, ps.depth | (ps.specular ? 1u << 8 : 0u) | (ps.shadow ? 1u << 9 : 0u) | (ps.branch << 10) |
                                (ps.path_segs << 16) | (ps.seg_base << 23));
+#if defined(OCTPT_SKYSAMPLE_TU)  // (seg_base <= MAX_PATH_SEGMENTS = 64: bits 23 .. 29; the mark rides bit 31)
+    c.y |= ps.sky_nee ? 1u << 31 : 0u;
+#endif
 }
 __device__ __forceinline__ void store_path(const WaveBuffers &B, uint32_t slot, const PathState &ps, uint32_t item) {
     float4 a, b;
@@ -2065,8 +2199,9 @@ __device__ __forceinline__ void load_nee(const WaveBuffers &B, uint32_t slot, Pa
     ps.att[0] = d.x; ps.att[1] = d.y; ps.att[2] = d.z; ps.att[3] = d.w;
 }
 
-#if defined(OCTPT_EMIT_TU)
+#if defined(OCTPT_PEND_TU)
 // a sun sample waiting behind an emitter segment (C38; planes 4 and 5 of pd, allocated for the emitter instances)
+// or behind a sky segment (C43; allocated for the sky-sampling instances alike)
 __device__ __forceinline__ void store_sun_pend(const WaveBuffers &B, uint32_t slot, const PathState &ps) {
     B.pd[4u * B.pool + slot] = make_float4(ps.sd.x, ps.sd.y, ps.sd.z, ps.smult);
     B.pd[5u * B.pool + slot] = make_float4(ps.so.x, ps.so.y, ps.so.z, ps.sun_pend ? 1.0f : 0.0f);
@@ -2097,7 +2232,12 @@ __device__ __forceinline__ void unpack_path(float4 a, float4 b, uint2 c, float4 
     ps.shadow = (c.y >> 9) & 1u;
     ps.branch = (c.y >> 10) & 63u;
     ps.path_segs = (c.y >> 16) & 127u;
+#if defined(OCTPT_SKYSAMPLE_TU)
+    ps.seg_base = (c.y >> 23) & 255u;
+    ps.sky_nee = (c.y >> 31) != 0u;
+#else
     ps.seg_base = c.y >> 23;
+#endif
 }
 __device__ __forceinline__ void load_path(const WaveBuffers &B, uint32_t slot, float4 r0, float4 r1, PathState &ps,
                                           uint32_t &item) {
@@ -2510,7 +2650,7 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
         cnt.redo++;
         return true;
     }
-#if defined(OCTPT_EMIT_TU)
+#if defined(OCTPT_PEND_TU)
     const bool was_shadow = ps.shadow;
     if (was_shadow) load_nee(B, slot, ps);
     ps.sun_pend = ps.emit_to_sun = false;
@@ -2538,8 +2678,8 @@ __device__ __forceinline__ bool shade_lane(const DevScene &S, const DevCamera &C
     if (cont) cont = begin_segment(ps);
     if (cont) {
         if (!kLean) store_path(B, slot, ps, item);
-#if defined(OCTPT_EMIT_TU)
-        if (ps.shadow) {  // a shadow segment follows: a new emitter or sun sample, or the next one
+#if defined(OCTPT_PEND_TU)
+        if (ps.shadow) {  // a shadow segment follows: a new emitter (sky, C43) or sun sample, or the next one
             if (!was_shadow || ps.emit_to_sun) store_nee(B, slot, ps);
             store_att(B, slot, ps);
             if (kNee && !was_shadow && ps.att[3] < 0.0f) store_sun_pend(B, slot, ps);  // (waiting or not)
@@ -3742,7 +3882,32 @@ __global__ __launch_bounds__(256) void atrous_var_kernel(DevDenoiseVar D, uint32
 
 }  // namespace
 
-#if defined(OCTPT_SKY_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_sky_emit.hip alone: not a build switch)
+#if defined(OCTPT_SKYSAMPLE_TU)  // (octpt_kernels_skysample.hip alone, with OCTPT_SKY_TU: not a build switch)
+// The sky-sampling instances (C43) of the general shade (sun sampling x LDS tables x regeneration) and the drains: the
+// sky module's instances with the sample's shadow segment, taking a SkySampleScene.  One shade family serves the four
+// camera forms (kCamAny), as under every sky.  No preview instance (it ignores the setting) and no emitter twin (the
+// two settings refuse each other).
+template <bool kNee, bool kLds>
+static const void *skysample_shade_of(int mode) {
+    return mode == 1 ? reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 1, false, kPrimsModels, kCamAny>)
+                     : reinterpret_cast<const void *>(wf_shade_kernel<kNee, kLds, 0, false, kPrimsModels, kCamAny>);
+}
+const void *skysample_shade_kernel(bool nee, bool lds, int mode) {
+    return nee ? (lds ? skysample_shade_of<true, true>(mode) : skysample_shade_of<true, false>(mode))
+               : (lds ? skysample_shade_of<false, true>(mode) : skysample_shade_of<false, false>(mode));
+}
+template <int kPrims>
+static const void *skysample_drain_of(bool nee) {
+    return nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrims, true>)
+               : reinterpret_cast<const void *>(wf_drain_kernel<kPrims, false>);
+}
+const void *skysample_drain_kernel(int prims, bool nee) {
+    return prims == kPrimsBlocks   ? skysample_drain_of<kPrimsBlocks>(nee)
+           : prims == kPrimsModels ? skysample_drain_of<kPrimsModels>(nee)
+           : prims == kPrimsBoxes  ? skysample_drain_of<kPrimsBoxes>(nee)
+                                   : skysample_drain_of<kPrimsSpheres>(nee);
+}
+#elif defined(OCTPT_SKY_TU) && defined(OCTPT_EMIT_TU)  // (octpt_kernels_sky_emit.hip alone: not a build switch)
 // The emitter instances (C38) of the general shade and the block scene's drain under a sky (C42), a module of their
 // own like every other family.
 template <bool kNee, bool kLds>
@@ -3949,10 +4114,11 @@ static int scene_prims(const DevScene &S) {
 }
 
 // what a sky instance takes in the scene's place (C42)
-static SkyScene sky_scene(const DevScene &S, const Sky &sky) {
-    SkyScene SS{};
+static SkySampleScene sky_scene(const DevScene &S, const Sky &sky, const SkyDist *dist = nullptr) {
+    SkySampleScene SS{};  // (a SkyScene first: what the sky instances without sampling read of it)
     static_cast<DevScene &>(SS) = S;
     SS.sky = sky;
+    if (dist) SS.dist = *dist;
     return SS;
 }
 
@@ -3967,7 +4133,7 @@ hipError_t launch_preview(const DevScene &S0, const DevCamera &C, const DevRende
                                      : reinterpret_cast<const void *>(preview_kernel<kPrimsSpheres>);
     if (C.proj_mode != 0u) fn = proj_preview_kernel(scene_prims(S));  // the projected instance (C40)
     if (C.proj_mode == kProjModeRays) fn = rays_preview_kernel(scene_prims(S));  // the ray-list instance (C41)
-    SkyScene SS{};
+    SkySampleScene SS{};
     if (sky) {  // the sky instance (C42), whatever the camera: it takes the scene with the sky behind it
         fn = sky_preview_kernel(scene_prims(S));
         SS = sky_scene(S, *sky);
@@ -4146,10 +4312,10 @@ int shade_blocks_per_cu(const DevScene &S, int mode) {
 
 hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRender &R, const WaveBuffers &B, uint32_t q,
                            uint32_t chunk_items, uint32_t first, bool regen, int grid, unsigned long long *stats,
-                           hipStream_t stream, bool emit, const Sky *sky) {
+                           hipStream_t stream, bool emit, const Sky *sky, const SkyDist *dist) {
     uint32_t first_u = first;
-    SkyScene SS{};
-    if (sky) SS = sky_scene(S, *sky);
+    SkySampleScene SS{};
+    if (sky) SS = sky_scene(S, *sky, dist);
     void *args[] = {sky ? static_cast<void *>(&SS) : const_cast<DevScene *>(&S), const_cast<DevCamera *>(&C),
                     const_cast<DevRender *>(&R), const_cast<WaveBuffers *>(&B), &q, &chunk_items, &first_u, &stats};
     const int cam = C.proj_mode == kProjModeRays ? kCamRays
@@ -4158,7 +4324,9 @@ hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRende
                                                  : kCamPinhole;
     const int mode = shade_mode(regen, B.lean != 0u);
     // a sky (C42): the sky instances, one family for every camera form (such chunks never take the lean state)
+    // ... with sky sampling (C43, dist: a MAP with a non-zero total) its own, which read the distribution behind it
     const void *fn = !sky   ? shade_instance(S, mode, first != 0u, cam, emit)
+                     : dist ? skysample_shade_kernel(S.sun.sun_sampling != 0, shade_lds_tables(S), mode)
                      : emit ? sky_emit_shade_kernel(S.sun.sun_sampling != 0, shade_lds_tables(S), mode)
                             : sky_shade_kernel(S.sun.sun_sampling != 0, shade_lds_tables(S), mode);
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, stream);
@@ -4167,11 +4335,11 @@ hipError_t launch_wf_shade(const DevScene &S, const DevCamera &C, const DevRende
 }
 
 hipError_t launch_wf_drain(const DevScene &S, const DevRender &R, const WaveBuffers &B, uint32_t q, int grid,
-                           unsigned long long *stats, hipStream_t stream, bool emit, const Sky *sky) {
+                           unsigned long long *stats, hipStream_t stream, bool emit, const Sky *sky, const SkyDist *dist) {
     const bool nee = S.sun.sun_sampling != 0;
-    SkyScene SS{};
-    if (sky) SS = sky_scene(S, *sky);
-    const void *fn = sky ? (emit ? sky_emit_drain_kernel(nee) : sky_drain_kernel(scene_prims(S), nee)) : emit ? emit_drain_kernel(nee) : S.has_blocks ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
+    SkySampleScene SS{};
+    if (sky) SS = sky_scene(S, *sky, dist);
+    const void *fn = sky && dist ? skysample_drain_kernel(scene_prims(S), nee) : sky ? (emit ? sky_emit_drain_kernel(nee) : sky_drain_kernel(scene_prims(S), nee)) : emit ? emit_drain_kernel(nee) : S.has_blocks ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, true>)
                                          : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsBlocks, false>))
                      : S.has_models ? (nee ? reinterpret_cast<const void *>(wf_drain_kernel<kPrimsModels, true>)
                                          : reinterpret_cast<const void *>(wf_drain_kernel<kPrimsModels, false>))

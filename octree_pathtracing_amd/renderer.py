@@ -260,6 +260,52 @@ class HipRenderer:
         """The setting in force (the last accepted set_sky's, or Sky())."""
         return self._sky
 
+    def set_sky_sampling(self, on: bool) -> None:
+        """octpt_set_sky_sampling: next-event estimation toward the sky map's bright texels in every
+        later render of this renderer.  It may come before or after set_sky; under a sky that is not a map, or an
+        all-black one, renders are what they are without it.  A refused setting (OctptError) leaves the previous one."""
+        p = _lib.SkySampling()
+        p.mode = _lib.SKY_SAMPLING_MAP if on else _lib.SKY_SAMPLING_NONE
+        self._check(self._lib.octpt_set_sky_sampling(self._ctx, C.byref(p)))
+        self.reset_render()
+
+    @property
+    def sky_sampling(self) -> bool:
+        """The setting in force (octpt_get_sky_sampling)."""
+        p = _lib.SkySampling()
+        self._check(self._lib.octpt_get_sky_sampling(self._ctx, C.byref(p)))
+        return p.mode == _lib.SKY_SAMPLING_MAP
+
+    def sky_distribution(self):
+        """octpt_sky_distribution: the distribution this renderer's device built from its map, copied back --
+        {"row_cdf": uint64 [H], "col_cdf": uint32 [H, W], "total": int, "build_ms": float} -- or None when it holds
+        none (sampling off, no map sky).  scene.build_sky_distribution is the CPU definition; the two are equal."""
+        a = _lib.SkyDistributionArrays()
+        self._check(self._lib.octpt_sky_distribution(self._ctx, C.byref(a)))
+        if a.width == 0:
+            return None
+        row = np.zeros(a.height, np.uint64)
+        col = np.zeros((a.height, a.width), np.uint32)
+        a.row_cdf, a.row_cdf_capacity, a.col_cdf, a.col_cdf_capacity = row.ctypes.data, row.size, col.ctypes.data, col.size
+        self._check(self._lib.octpt_sky_distribution(self._ctx, C.byref(a)))
+        return {"row_cdf": row, "col_cdf": col, "total": int(row[-1]), "build_ms": float(a.build_ms)}
+
+    def sky_samples(self, u) -> dict:
+        """octpt_sky_sample_device: the sky sample of draw tuples u [n, 4] over this renderer's distribution and sky,
+        computed on the device by the kernels' text (scene.sky_samples is the CPU form; the two agree bit for bit)."""
+        import torch
+
+        from .scene import unpack_sky_samples
+
+        dev = torch.device("cuda", self._device)
+        du = torch.from_numpy(np.ascontiguousarray(u, np.float32).reshape(-1, 4)).to(dev)
+        out = torch.zeros((du.shape[0], 8), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        self._check(self._lib.octpt_sky_sample_device(self._ctx, du.data_ptr(), du.shape[0], out.data_ptr(),
+                                                      stream.cuda_stream))
+        stream.synchronize()
+        return unpack_sky_samples(out.cpu().numpy())
+
     def sky_radiance(self, dirs) -> np.ndarray:
         """octpt_sky_radiance_ctx: the colour [n, 3] this renderer's sky adds for unit directions [n, 3] (the sun's
         terms excluded), computed on the device by the kernels' text.  scene.Sky.radiance is the CPU form; the two

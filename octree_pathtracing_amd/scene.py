@@ -240,6 +240,46 @@ class Sky:
         return out
 
 
+def build_sky_distribution(array) -> dict:
+    """octpt_build_sky_distribution: the importance-sampling distribution of an equirectangular map
+    (H, W, 3) or (H, W, 4), on the CPU -- the definition the device build equals.  {"row_cdf": uint64 [H], "col_cdf":
+    uint32 [H, W], "total": int}.  OctptError-style ValueError on a refused map (status 6: wider than 32768)."""
+    tex = np.ascontiguousarray(Sky.map(np.asarray(array)).texels, np.float32)
+    h, w = tex.shape[:2]
+    row = np.zeros(h, np.uint64)
+    col = np.zeros((h, w), np.uint32)
+    st = _lib.load().octpt_build_sky_distribution(tex.ctypes.data, w, h, row.ctypes.data, col.ctypes.data)
+    if st != 0:
+        raise ValueError(f"octpt_build_sky_distribution: status {st}")
+    return {"row_cdf": row, "col_cdf": col, "total": int(row[-1])}
+
+
+def sky_samples(dist: dict, u, yaw: float = 0.0) -> dict:
+    """octpt_sky_sample: the sky sample of draw tuples u [n, 4] over the distribution `dist` (build_sky_distribution's
+    or HipRenderer.sky_distribution's), on the CPU by the text the kernels compile.  {"d": [n, 3], "pdf": [n], "x", "y",
+    "q": uint32 [n], "ok": bool [n]}."""
+    u = np.ascontiguousarray(u, np.float32).reshape(-1, 4)
+    row = np.ascontiguousarray(dist["row_cdf"], np.uint64)
+    col = np.ascontiguousarray(dist["col_cdf"], np.uint32)
+    h, w = col.shape
+    a = _lib.SkyDistributionArrays(row.ctypes.data, row.size, col.ctypes.data, col.size, w, h, 0.0, 0)
+    d = _lib.SkyDesc()
+    d.mode, d.scale, d.yaw, d.width, d.height = 3, 1.0, float(yaw), w, h
+    out = np.zeros((len(u), 8), np.float32)
+    st = _lib.load().octpt_sky_sample(C.byref(a), C.byref(d), len(u), u.ctypes.data, out.ctypes.data)
+    if st != 0:
+        raise ValueError(f"octpt_sky_sample: status {st}")
+    return unpack_sky_samples(out)
+
+
+def unpack_sky_samples(out: np.ndarray) -> dict:
+    """The eight floats per sample of octpt_sky_sample / octpt_sky_sample_device: d.xyz, pdf, then x, y, q and the
+    sample flag as the bit patterns of 32-bit integers."""
+    w = np.ascontiguousarray(out[:, 4:8]).view(np.uint32)
+    return {"d": out[:, 0:3].copy(), "pdf": out[:, 3].copy(), "x": w[:, 0].copy(), "y": w[:, 1].copy(),
+            "q": w[:, 2].copy(), "ok": w[:, 3] != 0}
+
+
 @dataclass
 class Octree:
     """new_octree::Octree (new_octree.rs:13-19) + leaf payload -> primitive lists."""
